@@ -2,6 +2,7 @@
 """Headline benchmark: queries/sec for the fused top-10 of the RAG 2.0 retrieval hot path.
 
     python bench.py --gpus N --steps K --warmup W [--config dense|dense_bm25|triple|triple_rerank|all]
+                    [--dump-outputs DIR]
 
 A step = one pass of the hot path over one batch of ``--queries`` (default 2048) synthetic
 queries, inputs resident in HBM.  The headline line is always BASELINE.json configs[1]
@@ -23,6 +24,11 @@ The JSON line also carries
   latency       the drop-in ``RAG2Retriever.retrieve()`` one query at a time (p50 / p95), and the
                 scan alone for batches of 1 / 32 / 256 queries as HBM GB/s (one pass over the
                 float16 copy: the regime where the HBM roofline applies)
+
+``--dump-outputs DIR`` writes what the LAST timed step of every timed pipeline returned (the
+BatchResult of retrieve_batch: fused ids / scores / counts and every channel's list) as
+``DIR/<pipeline>_<field>.npy``.  The inputs are seeded, so two builds of the library run with the
+same arguments can be compared array by array.
 """
 from __future__ import annotations
 
@@ -46,6 +52,7 @@ CONFIGS = ("dense", "dense_bm25", "triple", "triple_rerank")
 BASELINE_CONFIG = {"dense": "configs[1]", "dense_bm25": "configs[2]", "triple": "configs[3]",
                    "triple_rerank": "configs[4]"}
 PMC_PROFILE = os.path.join(ROOT, "profiles", "r4_scan_f16qs_counters.json")
+DUMP_MAX_BYTES = 64_000_000
 
 
 def parse():
@@ -93,7 +100,13 @@ def parse():
     ap.add_argument("--shortlist", choices=("auto", "f16-inline", "f16", "f32"), default="auto",
                     help="shortlist scan of the timed path (GpuIndex.set_dense): auto = f16 copy; "
                          "results are the same float64-exact bits in every flavour (DESIGN.md 4.1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of every timed pipeline "
+                         "returned as DIR/<pipeline>_<field>.npy (float32 / float64; more than 64 MB in all: "
+                         "the same seeded sample of the query rows of every array)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.preset:
         args.config = {"configs1": "dense", "configs2": "dense_bm25", "configs3": "triple",
                        "configs4": "triple_rerank"}[args.preset]
@@ -102,6 +115,42 @@ def parse():
                 args.docs = 10_000_000
             args.doc_shards = args.doc_shards or args.gpus
     return args
+
+
+def result_arrays(cfg, res):
+    """What a caller of the timed path holds after a step -- the BatchResult of retrieve_batch:
+    the fused (or reranked) ids / scores / counts and every channel's merged list -- copied to
+    the host as ``<pipeline>_<field>`` arrays, one row per query."""
+    fields = {"ids": res.ids, "scores": res.scores, "counts": res.counts}
+    for name, (S, I, cnt) in res.channels.items():
+        fields[name + "_scores"], fields[name + "_ids"] = S, I
+        if cnt is not None:
+            fields[name + "_counts"] = cnt
+    return {f"{cfg}_{k}": v.cpu().numpy() for k, v in fields.items()}
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write ``arrays`` (name -> host array, one row per query) as dirname/<name>.npy.  float32
+    and float64 stay as they are; ids and counts become float64 (exact below 2**53).  When the
+    files would exceed max_bytes in all, every array keeps the same seeded sample of the query
+    rows, and sample_rows.npy holds their numbers."""
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+              for k, a in arrays.items()}
+    n_rows = len(next(iter(arrays.values())))
+    assert all(len(a) == n_rows for a in arrays.values())
+    header = 256 * (len(arrays) + 1)   # (an .npy header is 128 bytes for these shapes)
+    rows = None
+    if sum(a.nbytes for a in arrays.values()) + header > max_bytes:
+        row_bytes = sum(a.nbytes for a in arrays.values()) // n_rows + 8
+        keep = max(0, max_bytes - header) // row_bytes
+        rows = np.sort(np.random.Generator(np.random.PCG64([4321, 64])).choice(n_rows, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "arrays": sorted(arrays), "query_rows": n_rows if rows is None else len(rows),
+            "of": n_rows, "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def event_ms(fn, reps, torch):
@@ -333,6 +382,12 @@ def main():
     primary = index.shortlist
     res, rescued, elapsed = measure(step_fn(run_cfgs[0] if which != "all" else "dense"))
     head_cfg = run_cfgs[0] if which != "all" else "dense"
+    # --dump-outputs: the last timed step's result of every pipeline timed below, copied to the
+    # host as soon as its timed window has closed (rank 0: the merged lists are the same on
+    # every rank of a replica)
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        dumped.update(result_arrays(head_cfg, res))
     qps = args.steps * nq * n_replicas / elapsed   # every replica serves its own batch
     roofline = probe_scan(primary)
     head_ids = res.ids.clone()
@@ -452,6 +507,8 @@ def main():
     if which == "all":
         for cfg in CONFIGS[1:]:
             r2, resc2, el2 = measure(step_fn(cfg))
+            if args.dump_outputs:
+                dumped.update(result_arrays(cfg, r2))
             cfg_out[cfg] = {"baseline_config": BASELINE_CONFIG[cfg] + " pipeline", "docs": args.docs,
                             "gpus": 1, "lexical_mix": args.lexical_mix,
                             "value": round(args.steps * nq / el2, 1), "unit": "queries/s",
@@ -701,6 +758,8 @@ def main():
             out["latency"] = latency
         if check:
             out["parity_check"] = check
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
