@@ -244,6 +244,27 @@ int thr_lexical_build(const int32_t *doc, const int32_t *term, const int32_t *tf
                       int64_t *nnz_out, void *workspace, size_t workspace_bytes,
                       thr_stream_t stream);
 
+/* f2  incremental ingest: append the CSR of a batch of new chunks to a live index.  The reference
+ * inserts rag_child_chunks rows one document at a time (src/voice_agent/rag2/ingest.py:361-470)
+ * and PostgreSQL maintains the `tsv` column + GIN index behind the insert
+ * (database/migrations/20260114_rag2_schema.sql:146-148, 171-172).  Appended chunks get the
+ * largest doc ids and lists are doc-ascending within a row, so the merged list of row t is A's
+ * followed by B's: a segmented concatenation of two CSRs over one row space, no sort over A.
+ *   A: rowptr_a [rows_a + 1] (rowptr_a[rows_a] == nnz_a), payloads a0 / a1 [nnz_a];
+ *   B: rowptr_b [rows_b + 1] (rowptr_b[rows_b] == nnz_b), payloads b0 / b1 [nnz_b];
+ *      rows_b >= rows_a -- the vocabulary may have grown, rows >= rows_a are empty in A;
+ *   out: rowptr_out [rows_b + 1] = rowptr_a[min(t, rows_a)] + rowptr_b[t], out0 / out1 with room
+ *      for out_capacity >= nnz_a + nnz_b elements, buffers of their own (out of place).
+ * Payloads are opaque 4-byte elements (post_doc / post_tf int32; men_chunk int32 / men_conf
+ * float32); the second one is optional (a1 == b1 == out1 == NULL).  rows_a == 0 (rowptr_a may be
+ * NULL) appends to an empty index.  Stream-ordered, no host round trip, no workspace.  The kernel
+ * checks every source index against nnz_a / nnz_b and every destination against nnz_a + nnz_b. */
+int thr_csr_append(const int64_t *rowptr_a, int64_t rows_a, int64_t nnz_a, const void *a0,
+                   const void *a1 /* or NULL */, const int64_t *rowptr_b, int64_t rows_b,
+                   int64_t nnz_b, const void *b0, const void *b1 /* or NULL */,
+                   int64_t *rowptr_out, void *out0, void *out1 /* or NULL */,
+                   int64_t out_capacity, thr_stream_t stream);
+
 /* a3  lexical channel: Okapi BM25 (k1, b) top-k over a CSR inverted index,
  * OR semantics, float64 accumulation in query-term order.
  * Stands where SQL rag2_lexical_search (ts_rank_cd ... ORDER BY rank DESC

@@ -66,6 +66,7 @@ _SIGNATURES = {
     "thr_dense_scan_stamps_f16": (_i32, [_vp, _i64, _i32, _i32, _vp, _sz, _vp, C.POINTER(_i32), _vp]),
     "thr_lexical_build_workspace_bytes": (_sz, [_i64, _i64]),
     "thr_lexical_build": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "thr_csr_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "thr_bm25_block_count": (_sz, [_i64]),
     "thr_bm25_bounds": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "thr_bm25_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -486,6 +487,51 @@ def lexical_build(doc: torch.Tensor, term: torch.Tensor, tf: Optional[torch.Tens
            "thr_lexical_build")
     k = int(nnz.item())
     return rowptr, post_doc[:k].clone(), post_tf[:k].clone(), doclen, df
+
+
+# --------------------------------------------------------------------- f2
+def csr_append(rowptr_a, a0, a1, rowptr_b, b0, b1, out0=None, out1=None):
+    """Segmented concatenation of two CSRs over one row space (thr_csr_append): row t of the
+    result is A's row t followed by B's.  ``rowptr_a`` int64 [rows_a + 1] or None (an empty A),
+    ``rowptr_b`` int64 [rows_b + 1], rows_b >= rows_a; payloads are 4-byte tensors [nnz] (int32 /
+    float32), the second of each pair optional.  ``out0`` / ``out1``: capacity-reserved 1-d
+    destinations of the payloads' dtypes (allocated to size when None) -- the first
+    nnz_a + nnz_b elements are written.  -> (rowptr_out, out0, out1 or None, nnz)."""
+    rows_a = 0 if rowptr_a is None else rowptr_a.shape[0] - 1
+    rows_b = rowptr_b.shape[0] - 1
+    pra = _dev(rowptr_a, torch.int64, "rowptr_a", 1)
+    prb = _dev(rowptr_b, torch.int64, "rowptr_b", 1)
+    if rows_b < max(rows_a, 1):
+        raise NativeError(f"csr_append: B has {rows_b} rows, A has {rows_a} (rows only grow)")
+    if b0.dtype.itemsize != 4 or (a0 is not None and a0.dtype != b0.dtype):
+        raise NativeError("csr_append: payloads are 4-byte elements of one dtype per array")
+    if a0 is not None and (a1 is None) != (b1 is None):
+        raise NativeError("csr_append: A and B carry the same number of payload arrays")
+    if b1 is not None and (b1.dtype.itemsize != 4 or (a1 is not None and a1.dtype != b1.dtype)):
+        raise NativeError("csr_append: payloads are 4-byte elements of one dtype per array")
+    nnz_a = 0 if a0 is None else a0.shape[0]
+    nnz_b = b0.shape[0]
+    if (a1 is not None and a1.shape[0] != nnz_a) or (b1 is not None and b1.shape[0] != nnz_b):
+        raise NativeError("csr_append: the payloads of one CSR have one length")
+    dev = rowptr_b.device
+    nnz = nnz_a + nnz_b
+    if out0 is None:
+        out0 = torch.empty(nnz, dtype=b0.dtype, device=dev)
+    if out1 is None and b1 is not None:
+        out1 = torch.empty(nnz, dtype=b1.dtype, device=dev)
+    if out0.dtype != b0.dtype or out0.shape[0] < nnz or \
+            (b1 is not None and (out1.dtype != b1.dtype or out1.shape[0] < nnz)):
+        raise NativeError("csr_append: destination too small or of another dtype")
+    rowptr_out = torch.empty(rows_b + 1, dtype=torch.int64, device=dev)
+    cap = out0.shape[0] if b1 is None else min(out0.shape[0], out1.shape[0])
+    _check(load().thr_csr_append(pra, rows_a, nnz_a, _dev(a0, b0.dtype, "a0", 1) if nnz_a else None,
+                                 _dev(a1, b1.dtype, "a1", 1) if nnz_a and b1 is not None else None,
+                                 prb, rows_b, nnz_b, _dev(b0, b0.dtype, "b0", 1) if nnz_b else None,
+                                 _dev(b1, b1.dtype, "b1", 1) if nnz_b and b1 is not None else None,
+                                 rowptr_out.data_ptr(), _dev(out0, b0.dtype, "out0", 1) if nnz else None,
+                                 _dev(out1, b1.dtype, "out1", 1) if nnz and b1 is not None else None,
+                                 cap, _stream()), "thr_csr_append")
+    return rowptr_out, out0, (out1 if b1 is not None else None), nnz
 
 
 # --------------------------------------------------------------------- a3

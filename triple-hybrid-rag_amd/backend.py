@@ -14,6 +14,15 @@ the table fetches are answered from ``CorpusStore``, the host-side row payloads
 (ids, text, page, modality, parents) that the SQL rows would carry.
 Rows come back in REQUEST order from ``in_()`` (PostgreSQL's order there is
 unspecified; the reference ranks graph hits by that order, Appendix A.7).
+
+The ingest seam (src/voice_agent/rag2/ingest.py:361-470) is served too:
+
+    client.table("rag_child_chunks").select("content_hash").eq("org_id", o).in_("content_hash", hs).execute().data
+    client.table("rag_child_chunks").insert(row | [rows]).execute().data      -> [{"id": ...}, ...]
+    client.table("rag_parent_chunks").insert(row | [rows]).execute().data
+
+An insert appends to the store AND to the live index (``GpuIndex.append_rows``): the next
+``retrieve()`` sees the chunk.  The reference's ingest never deletes; neither does this.
 """
 from __future__ import annotations
 
@@ -50,9 +59,63 @@ class CorpusStore:
     vocab: Dict[str, int] = field(default_factory=dict)               # term -> id
     entity_names: List[str] = field(default_factory=list)
     doc_base: int = 0
+    content_hashes: Optional[List[Optional[str]]] = None            # the dedup key of the ingest (nullable)
 
     def __post_init__(self):
         self._row_of = {cid: i for i, cid in enumerate(self.child_ids)}
+        self._hashes = {h for h in (self.content_hashes or ()) if h is not None}
+
+    def has_hash(self, content_hash: Optional[str]) -> bool:
+        return content_hash is not None and content_hash in self._hashes
+
+    def append(self, rows: Sequence[Dict[str, Any]], tokenizer=None) -> range:
+        """Append child-chunk rows (the columns ``index_build.from_rows`` reads, plus the
+        optional ``content_hash``) -> the range of their row indices.  ``page`` is nullable, as
+        the SQL column is.  A row whose id or content hash the store already holds -- or that
+        repeats one inside the batch -- raises before anything is changed (the message names
+        the ``duplicate``: what the reference's ingest catches, ingest.py:457-460).
+        ``tokenizer``: unseen terms of the rows' texts get the next vocabulary ids, at the END,
+        so existing term ids never move."""
+        rows = list(rows)
+        ids, hashes = set(), set()
+        for r in rows:
+            if r["id"] in self._row_of or r["id"] in ids:
+                raise ValueError(f"duplicate key value violates unique constraint: id {r['id']!r}")
+            h = r.get("content_hash")
+            if h is not None and (h in self._hashes or h in hashes):
+                raise ValueError(f"duplicate key value violates unique constraint: content_hash {h!r}")
+            ids.add(r["id"])
+            hashes.add(h)
+        n0 = len(self.child_ids)
+        # (a loaded store keeps its columns as read-only blobs: they become lists on the first append)
+        for name in ("child_ids", "parent_ids", "document_ids", "texts", "pages", "modalities"):
+            if not isinstance(getattr(self, name), list):
+                setattr(self, name, list(getattr(self, name)))
+        if self.collections is None and any(r.get("collection") is not None for r in rows):
+            raise ValueError("the store has no collection column: rows cannot carry a collection")
+        if self.collections is not None and not isinstance(self.collections, list):
+            self.collections = list(self.collections)
+        if self.content_hashes is None:
+            self.content_hashes = [None] * n0
+        elif not isinstance(self.content_hashes, list):
+            self.content_hashes = list(self.content_hashes)
+        for i, r in enumerate(rows):
+            self.child_ids.append(r["id"])
+            self.parent_ids.append(r.get("parent_id"))
+            self.document_ids.append(r.get("document_id"))
+            self.texts.append(r.get("text", ""))
+            self.pages.append(r.get("page", 1))
+            self.modalities.append(r.get("modality", "text"))
+            if self.collections is not None:
+                self.collections.append(r.get("collection"))
+            self.content_hashes.append(r.get("content_hash"))
+            self._row_of[r["id"]] = n0 + i
+            if tokenizer is not None:
+                for tok in tokenizer(r.get("text", "")):
+                    if tok not in self.vocab:
+                        self.vocab[tok] = len(self.vocab)
+        self._hashes.update(h for h in hashes if h is not None)
+        return range(n0, n0 + len(rows))
 
     def row_index(self, child_id: str) -> Optional[int]:
         return self._row_of.get(child_id)
@@ -151,15 +214,29 @@ class LazyRows(collections.abc.Sequence):
 
 
 class _TableQuery:
-    def __init__(self, fetch):
+    def __init__(self, fetch, by_hash=None, insert=None, org_id=None):
         self._fetch = fetch
+        self._by_hash = by_hash       # content_hash lookup (rag_child_chunks only)
+        self._insert = insert         # row writer (the two chunk tables)
+        self._org_id = org_id
         self._ids: Optional[List[Any]] = None
+        self._hashes: Optional[List[Any]] = None
+        self._rows: Optional[List[Dict[str, Any]]] = None
         self._limit: Optional[int] = None
+        self._foreign = False         # eq("org_id", another tenant): nothing of this index matches
 
     def select(self, *_cols, **_kw):
         return self
 
-    def eq(self, *_a, **_kw):
+    def eq(self, *a, **_kw):
+        if len(a) == 2 and a[0] == "org_id" and self._org_id is not None and a[1] not in (None, self._org_id):
+            self._foreign = True
+        return self
+
+    def insert(self, rows):
+        if self._insert is None:
+            raise ValueError("this table is read-only in the GPU index")
+        self._rows = [rows] if isinstance(rows, dict) else list(rows)
         return self
 
     def limit(self, n: int):
@@ -167,13 +244,21 @@ class _TableQuery:
         return self
 
     def in_(self, column: str, values: Sequence[Any]):
+        if column == "content_hash" and self._by_hash is not None:
+            self._hashes = list(values)
+            return self
         if column != "id":
-            raise ValueError("only id lookups are served from the GPU index store")
+            raise ValueError("only id (and rag_child_chunks.content_hash) lookups are served from the GPU index store")
         self._ids = list(values)
         return self
 
     def execute(self):
-        rows = self._fetch(self._ids or [])
+        if self._rows is not None:
+            return _Reply(self._insert(self._rows))
+        if self._hashes is not None:
+            rows = [] if self._foreign else self._by_hash(self._hashes)
+        else:
+            rows = self._fetch(self._ids or [])
         return _Reply(rows[: self._limit] if self._limit is not None else rows)
 
 
@@ -206,6 +291,7 @@ class GpuIndexClient:
         self.store = store
         self.org_id = org_id
         self.token_embedder = token_embedder
+        self.tokenizer = tokenize     # what the index's vocabulary was built with (from_rows' default)
         self._pin: Dict[Any, list] = {}   # reusable pinned staging buffers (one query per call)
         # collection names -> ids; the filter itself runs on the device, before the ranking
         self._coll_id: Dict[str, int] = {}
@@ -420,6 +506,102 @@ class GpuIndexClient:
         self._pending_lex = LazyRows(fetch)
         return self._pending_lex
 
+    # -------------------------------------------------------------- ingest
+    def _check_org(self, rows: Sequence[Dict[str, Any]]) -> None:
+        if self.org_id is not None and any(r.get("org_id") not in (None, self.org_id) for r in rows):
+            raise ValueError("insert refused: the rows belong to another org_id than this index "
+                             "(data isolation, as rpc() answers another tenant with no rows)")
+
+    def insert_children(self, rows: Sequence[Dict[str, Any]], embedding_key: str = "embedding_1024"):
+        """``table("rag_child_chunks").insert(rows)``: one append of len(rows) chunks to the store
+        and to the live index -> [{"id": ...}, ...].  A row is stored as ``index_build.from_rows``
+        stores it (float32 embedding; no embedding = a zero vector, outside the dense channel; the
+        text tokenised with ``self.tokenizer``), so a bulk build and an insert hold the same
+        floats.  Everything is checked first (org, duplicate ids / content hashes, what the
+        index's channels need); the index is appended to before the store, so a refused append
+        leaves both as they were."""
+        rows = list(rows)
+        self._check_org(rows)
+        if not rows:
+            return []
+        st, idx = self.store, self.index
+        seen_id, seen_h = set(), set()
+        for r in rows:
+            h = r.get("content_hash")
+            if st.row_index(r["id"]) is not None or r["id"] in seen_id or st.has_hash(h) or (h is not None and h in seen_h):
+                raise ValueError("duplicate key value violates unique constraint on rag_child_chunks "
+                                 f"(id {r['id']!r}, content_hash {h!r})")
+            seen_id.add(r["id"])
+            seen_h.add(h)
+        m = len(rows)
+        parts: Dict[str, Any] = {}
+        if idx.docs is not None:
+            docs = np.zeros((m, idx.dim), dtype=np.float32)
+            for i, r in enumerate(rows):
+                if r.get(embedding_key) is not None:
+                    if len(r[embedding_key]) != idx.dim:
+                        raise ValueError(f"embedding has {len(r[embedding_key])} dims, index has {idx.dim}")
+                    docs[i] = np.asarray(r[embedding_key], dtype=np.float32)
+            parts["docs"] = docs
+        else:
+            parts.update(docs=None, n_rows=m)
+        vocab = st.vocab
+        if getattr(idx, "lex", None) is not None:
+            # term ids of the store's vocabulary; unseen terms get the next ids (committed to the
+            # store only after the index took the rows)
+            grown: Dict[str, int] = {}
+            d_tok, t_tok = [], []
+            for i, r in enumerate(rows):
+                for tok in self.tokenizer(r.get("text", "")):
+                    t = vocab.get(tok)
+                    if t is None:
+                        t = grown.get(tok)
+                        if t is None:
+                            t = grown[tok] = len(vocab) + len(grown)
+                    d_tok.append(i)
+                    t_tok.append(t)
+            parts["lex"] = (np.asarray(d_tok, dtype=np.int32), np.asarray(t_tok, dtype=np.int32), None,
+                            max(len(vocab) + len(grown), 1))
+        if idx.doc_coll is not None:
+            for r in rows:   # a collection no earlier row carries gets the next id (ids never move)
+                c = r.get("collection")
+                if c is not None and c not in self._coll_id:
+                    self._coll_id[c] = max(self._coll_id.values(), default=-1) + 1
+            parts["collections"] = np.array([self._coll_id[r["collection"]] if r.get("collection") is not None
+                                             else -2 for r in rows], dtype=np.int32)
+        if idx.tokens is not None:
+            if any(r.get("tokens") is None for r in rows):
+                raise ValueError("the index has a late-interaction token store: every inserted row needs its "
+                                 "'tokens' matrix [d_tokens, tok_dim]")
+            parts["tokens"] = np.stack([np.asarray(r["tokens"], dtype=np.float16) for r in rows])
+        if idx.graph is not None:
+            me, mc, mw = [], [], []
+            for i, r in enumerate(rows):   # optional per-row mentions: [(entity index, confidence), ...]
+                for e, w in r.get("mentions", ()):
+                    me.append(int(e))
+                    mc.append(i)
+                    mw.append(float(w))
+            parts["mentions"] = (np.asarray(me, dtype=np.int64), np.asarray(mc, dtype=np.int64),
+                                 np.asarray(mw, dtype=np.float32))
+        idx.append_rows(**parts)
+        st.append(rows, tokenizer=self.tokenizer if getattr(idx, "lex", None) is not None else None)
+        if hasattr(self, "_by_text"):
+            del self._by_text
+        return [{"id": r["id"]} for r in rows]
+
+    def insert_parents(self, rows: Sequence[Dict[str, Any]]):
+        rows = list(rows)
+        self._check_org(rows)
+        for p in rows:
+            if p["id"] in self.store.parents:
+                raise ValueError(f"duplicate key value violates unique constraint on rag_parent_chunks (id {p['id']!r})")
+        for p in rows:
+            self.store.parents[p["id"]] = {"id": p["id"], "text": p.get("text", ""),
+                                           "section_heading": p.get("section_heading")}
+        if hasattr(self, "_by_text"):
+            del self._by_text
+        return [{"id": p["id"]} for p in rows]
+
     # -------------------------------------------------------------- tables
     def table(self, name: str) -> _TableQuery:
         if name == "rag_child_chunks":
@@ -430,10 +612,14 @@ class GpuIndexClient:
                     if i is not None:
                         rows.append(self.store.child_row(i))
                 return rows
-            return _TableQuery(fetch)
+
+            def by_hash(hashes):
+                return [{"content_hash": h} for h in dict.fromkeys(hashes) if self.store.has_hash(h)]
+            return _TableQuery(fetch, by_hash=by_hash, insert=self.insert_children, org_id=self.org_id)
         if name == "rag_parent_chunks":
             return _TableQuery(lambda ids: [dict(self.store.parents[p]) for p in ids
-                                            if p in self.store.parents])
+                                            if p in self.store.parents], insert=self.insert_parents,
+                               org_id=self.org_id)
         # tenant discovery of the tool layer (tools/crm_knowledge.py:89-101 in the reference)
         if name == "rag_documents":
             return _TableQuery(lambda _ids: [{"org_id": self.org_id}] if self.org_id else [])

@@ -154,6 +154,12 @@ class ShardedIndex:
             dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)
             self.floor = bool(int(ok.item()))
 
+    def append_rows(self, *_a, **_kw):
+        """Not supported: an append to a document-sharded index needs a collective df / length
+        all-reduce and a rule for which rank takes the rows (Incremental ingest)."""
+        raise N.NativeError("append_rows is not supported on a ShardedIndex: rebuild the shards "
+                            "(appends to a document-sharded index are out of scope)")
+
     def _floor_exchange(self):
         if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline"):
             return None

@@ -75,6 +75,11 @@ class GpuIndex:
         self._ws_lex: Optional[torch.Tensor] = None
         self._ws_graph: Optional[torch.Tensor] = None
         self._lex_done = None   # event: the last bm25_search's kernels have left the lexical workspace
+        self._shortlist_auto = False   # set_dense(shortlist="auto"): an append may re-decide the flavour
+        self._backing: Dict[str, torch.Tensor] = {}   # name -> buffer with spare capacity (reserve_rows / append_rows)
+        self._lex_global = False    # idf / avgdl are a sharded corpus' (set_lexical_rows with a group)
+        self._spare: Dict[str, torch.Tensor] = {}     # CSR payload name -> destination of the next append
+        self._csr_cap: Dict[str, torch.Tensor] = {}   # CSR payload name -> the capacity buffer behind its view
 
     # ------------------------------------------------------------ builders
     def _t(self, a, dtype):
@@ -121,7 +126,7 @@ class GpuIndex:
             raise N.NativeError(f"row length {self.dim} is not a multiple of 4")
         self.dnorm, self.inv_norm = N.doc_norms(self.docs)
         self.docs16, self.doc_rel_err = (None, 0.0)
-        auto = shortlist == "auto"
+        auto = self._shortlist_auto = shortlist == "auto"
         if self.dim not in self.SCAN_DIMS and shortlist != "exact":
             if not auto:
                 raise N.NativeError(f"shortlist={shortlist!r} needs a row length in {self.SCAN_DIMS}, got "
@@ -225,6 +230,7 @@ class GpuIndex:
         idf = np.log(1.0 + (float(n_glob) - dfh + 0.5) / (dfh + 0.5))
         avgdl = float(sum_dl.item()) / max(n_glob, 1)
         self.df_local, self.df_global = df, df_glob
+        self._lex_global = group is not None or n_glob != n
         return self.set_lexical(rowptr, post_doc, post_tf, doclen, idf, avgdl if avgdl > 0 else 1.0, k1, b,
                                 dense_share)
 
@@ -278,6 +284,351 @@ class GpuIndex:
         self.tokens_packed = bool(pack)
         self.tokens = N.maxsim_pack(tok) if pack else tok
         return self
+
+    # ------------------------------------------------------------ incremental ingest
+    # Append in place (DESIGN.md "Incremental ingest"): after append_rows every device array is
+    # what a fresh build over all the rows would hold, so the query kernels and their throughput
+    # are the fresh build's.  The reference's ingest only ever inserts (rag2/ingest.py:361-470).
+    GROWTH = 1.5    # a buffer that is too small is replaced by one of GROWTH x its size (at least the need)
+
+    def _row_arrays(self) -> Dict[str, torch.Tensor]:
+        """The per-document arrays (leading dimension = rows; docs16: rows padded to tiles of 32)."""
+        arrs = dict(docs=self.docs, docs16=self.docs16, dnorm=self.dnorm, inv_norm=self.inv_norm,
+                    doc_coll=self.doc_coll, tokens=self.tokens,
+                    doclen=self.lex["doclen"] if self.lex is not None else None)
+        return {k: v for k, v in arrs.items() if v is not None}
+
+    def _set_row_array(self, name: str, view: torch.Tensor) -> None:
+        if name == "doclen":
+            self.lex["doclen"] = view
+        else:
+            setattr(self, name, view)
+
+    def _buffer(self, name: str, view: torch.Tensor, rows: int, capacity: Optional[int] = None) -> torch.Tensor:
+        """A buffer with room for ``rows`` leading rows of array ``name`` that already holds the rows
+        of ``view``: the view's own backing buffer when that has the room (the rows behind the
+        view are free to write: no kernel is given more than the logical size), else a new one of
+        max(rows, capacity or GROWTH x the old size) rows, the old rows copied on the device."""
+        back = self._backing.get(name)
+        if back is not None and back.shape[0] >= rows and back.shape[1:] == view.shape[1:] and \
+                back.data_ptr() == view.data_ptr():
+            return back
+        cap = max(rows, capacity or int(self.GROWTH * view.shape[0]))
+        buf = torch.empty((cap,) + tuple(view.shape[1:]), dtype=view.dtype, device=self.device)
+        buf[:view.shape[0]].copy_(view)
+        return buf
+
+    def _sync_streams(self) -> None:
+        """An append is not on the query path: queued BM25 / graph work on the side stream and
+        dense work on the main one may still read the arrays about to be swapped or extended."""
+        torch.cuda.current_stream(self.device).synchronize()
+        if getattr(self, "_side", None) is not None:
+            self._side.synchronize()
+        if self._lex_done is not None:
+            self._lex_done.synchronize()
+
+    def capacity_rows(self) -> int:
+        """Rows the per-document buffers hold without a reallocation (= n_docs until
+        reserve_rows / the first append)."""
+        caps = [self._backing[k].shape[0] if k in self._backing and self._backing[k].data_ptr() == v.data_ptr()
+                else v.shape[0] for k, v in self._row_arrays().items() if k != "docs16"]
+        return min(caps) if caps else 0
+
+    def reserve_rows(self, capacity: int, postings: Optional[int] = None) -> "GpuIndex":
+        """Room for ``capacity`` documents in every per-document array (rows, float16 image, norms,
+        collections, lengths, token store), so that appends up to there copy nothing old;
+        ``postings``: room for that many postings in the destination of the next lexical append.
+        The logical sizes, and what the kernels are given, do not change."""
+        capacity = int(capacity)
+        if capacity > self.n_docs:
+            self._sync_streams()
+            for name, view in self._row_arrays().items():
+                rows = (capacity + 31) // 32 * 32 if name == "docs16" else capacity
+                buf = self._buffer(name, view, rows, capacity=rows)
+                self._backing[name] = buf
+                self._set_row_array(name, buf[:view.shape[0]])
+        if postings and self.lex is not None:
+            sp = self._spare
+            for name in ("post_doc", "post_tf"):
+                if name not in sp or sp[name].shape[0] < postings:
+                    sp[name] = torch.empty(int(postings), dtype=torch.int32, device=self.device)
+        return self
+
+    @staticmethod
+    def _host_or_device(a, name: str, integer: bool = False):
+        """``a`` where it lives, as a tensor or a numpy array (host data: no device work)."""
+        t = a if isinstance(a, torch.Tensor) else np.asarray(a)
+        is_int = not t.dtype.is_floating_point and t.dtype != torch.bool if isinstance(t, torch.Tensor) \
+            else np.issubdtype(t.dtype, np.integer)
+        if integer and not is_int:
+            raise N.NativeError(f"append_rows: {name} must be an integer array, got {t.dtype}")
+        return t
+
+    def _validate_append(self, docs, lex, collections, tokens, mentions, n_rows) -> dict:
+        """Everything about an append that can be refused before any device work: which parts are
+        required (exactly the channels the index has), shapes, dtypes, id ranges.  -> the parts as
+        tensors where the caller left them + the batch size."""
+        E = N.NativeError
+        has_dense = self.docs is not None
+        if has_dense:
+            if docs is None:
+                raise E("append_rows: this index has a dense channel: docs [m, dim] is required")
+            docs = self._host_or_device(docs, "docs")
+            if docs.ndim != 2 or docs.shape[1] != self.dim:
+                raise E(f"append_rows: docs must be [m, {self.dim}], got {tuple(docs.shape)}")
+            m = int(docs.shape[0])
+            if n_rows is not None and int(n_rows) != m:
+                raise E("append_rows: n_rows differs from the number of dense rows")
+        else:
+            if docs is not None:
+                raise E("append_rows: this index has no dense channel (set_dense): docs must be None")
+            if n_rows is None:
+                raise E("append_rows: an index without a dense channel needs n_rows")
+            m = int(n_rows)
+        if m < 0 or self.n_docs + m > (1 << 31) - 1:
+            raise E("append_rows: row count out of range")
+        out = dict(m=m, docs=docs, lex=None, collections=None, tokens=None, mentions=None)
+        if (self.lex is not None) != (lex is not None):
+            raise E("append_rows: this index has a lexical channel: lex=(doc, term, tf, n_vocab) is required"
+                    if lex is None else "append_rows: this index has no lexical channel: lex must be None")
+        if lex is not None:
+            if self._lex_global:
+                raise E("append_rows: not supported on a document shard (idf / avgdl are the whole corpus': "
+                        "the append needs a collective df / length all-reduce)")
+            if len(lex) != 4:
+                raise E("append_rows: lex is (doc, term, tf or None, n_vocab)")
+            d, t, f, n_vocab = lex
+            d, t = self._host_or_device(d, "lex doc", True), self._host_or_device(t, "lex term", True)
+            f = None if f is None else self._host_or_device(f, "lex tf", True)
+            n_vocab = int(n_vocab)
+            if d.ndim != 1 or t.shape != d.shape or (f is not None and f.shape != d.shape):
+                raise E("append_rows: lex doc / term / tf are 1-d arrays of one length")
+            v_old = int(self.lex["rowptr"].shape[0]) - 1
+            if n_vocab < v_old or n_vocab > (1 << 31) - 2:
+                raise E(f"append_rows: n_vocab {n_vocab} is smaller than the index's vocabulary {v_old} "
+                        "(term ids never move: new terms get new ids at the end)")
+            if d.shape[0]:
+                if int(d.min()) < 0 or int(d.max()) >= m:
+                    raise E(f"append_rows: lex doc ids are local to the batch, 0 .. {m - 1}")
+                if int(t.max()) >= n_vocab:
+                    raise E(f"append_rows: term id {int(t.max())} >= n_vocab {n_vocab}")
+            out["lex"] = (d, t, f, n_vocab)
+        if (self.doc_coll is not None) != (collections is not None):
+            raise E("append_rows: this index has collection ids: collections [m] is required"
+                    if collections is None else "append_rows: this index has no collection ids (set_collections)")
+        if collections is not None:
+            c = self._host_or_device(collections, "collections", True)
+            if tuple(c.shape) != (m,):
+                raise E("append_rows: collections: one id per appended row")
+            out["collections"] = c
+        if (self.tokens is not None) != (tokens is not None):
+            raise E("append_rows: this index has a token store: tokens [m, d_tokens, tok_dim] is required"
+                    if tokens is None else "append_rows: this index has no token store (set_tokens)")
+        if tokens is not None:
+            tk = self._host_or_device(tokens, "tokens")
+            if tk.ndim != 3 or tk.shape[0] != m or tuple(tk.shape[1:]) != tuple(self.tokens.shape[1:]):
+                raise E(f"append_rows: tokens must be [{m}, {self.tokens.shape[1]}, {self.tokens.shape[2]}]")
+            out["tokens"] = tk
+        if (self.graph is not None) != (mentions is not None):
+            raise E("append_rows: this index has a graph channel: mentions=(entity, chunk, conf) is required "
+                    "(empty arrays when the new chunks mention nothing)"
+                    if mentions is None else "append_rows: this index has no graph channel (set_graph)")
+        if mentions is not None:
+            if len(mentions) != 3:
+                raise E("append_rows: mentions is (entity, chunk, conf or None)")
+            e, c, w = mentions
+            e, c = self._host_or_device(e, "mention entity", True), self._host_or_device(c, "mention chunk", True)
+            w = None if w is None else self._host_or_device(w, "mention conf")
+            if e.ndim != 1 or c.shape != e.shape or (w is not None and w.shape != e.shape):
+                raise E("append_rows: mention entity / chunk / conf are 1-d arrays of one length")
+            n_ent = int(self.graph["men_rowptr"].shape[0]) - 1
+            if e.shape[0]:
+                if int(e.min()) < 0 or int(e.max()) >= n_ent:
+                    raise E(f"append_rows: mention entity ids must be existing entities, 0 .. {n_ent - 1} "
+                            "(new entities need set_graph)")
+                if int(c.min()) < 0 or int(c.max()) >= m:
+                    raise E(f"append_rows: mention chunk ids are local to the batch, 0 .. {m - 1}")
+            out["mentions"] = (e, c, w)
+        return out
+
+    def _dense_flavour_after(self, new: torch.Tensor, n_new: int):
+        """What set_dense would decide for the rows so far + ``new``, without touching the index:
+        -> (shortlist, float16 image of the tail tiles or None, doc_rel_err, first row of the tail)."""
+        n_old, cur = self.n_docs, self.shortlist
+        t0 = n_old // 32 * 32     # the last partially filled tile of 32 rows is re-quantised
+        if cur not in ("f16", "f16-inline"):
+            return cur, None, self.doc_rel_err, t0
+        want = cur
+        if self._shortlist_auto:
+            total = torch.cuda.get_device_properties(self.device).total_memory
+            fits = cur == "f16" and 2 * n_new * self.dim <= self.AUTO_COPY_FRACTION * total
+            want = "f32" if n_new >= self.F16_MAX_ROWS else ("f16" if fits else "f16-inline")
+        tail16, err = None, 0.0
+        if want == "f16":         # (cur is "f16": growth never shrinks the copy)
+            tail16, e = N.dense_quantize_f16(torch.cat([self.docs[t0:n_old], new]), keep_copy=True)
+            err = max(self.doc_rel_err, e)
+        elif want == "f16-inline":
+            _, err = N.dense_quantize_f16(new, keep_copy=False)
+            # (the copy's error is measured on the normalised rows: the in-flight rounding's is not)
+            old = self.doc_rel_err if cur == "f16-inline" else N.dense_quantize_f16(self.docs, keep_copy=False)[1]
+            err = max(err, old)
+        if want != "f32" and (not np.isfinite(err) or err > self.F16_MAX_REL_ERR):
+            if not self._shortlist_auto:
+                raise N.NativeError("append_rows: the new rows do not fit float16 (values >= 65504 or mostly "
+                                    "below 6e-5 in magnitude): build the index with shortlist='f32'")
+            want = "f32"
+        if want == "f32":
+            tail16, err = None, 0.0
+        return want, tail16, err, t0
+
+    def append_rows(self, docs, lex=None, collections=None, tokens=None, mentions=None,
+                    n_rows: Optional[int] = None) -> range:
+        """Append m chunks to the live index -> the range of their LOCAL doc ids (add doc_base for
+        the global ones).  Afterwards every device array is, to the bit, what a fresh build over
+        all the rows would hold, and the next search sees the rows.
+          docs        float32 [m, dim] (row without an embedding: zeros);
+          lex         (doc, term, tf or None, n_vocab): the tokenised rows as set_lexical_rows
+                      takes them, doc ids LOCAL TO THE BATCH (0 .. m-1); term ids of the index's
+                      vocabulary, new terms numbered from the old vocabulary size on
+                      (n_vocab >= the old one); a negative term is a token outside the
+                      vocabulary (counts toward its chunk's length only);
+          collections int32 [m];   tokens float16 [m, d_tokens, tok_dim];
+          mentions    (entity, chunk, conf or None): entity ids of EXISTING entities, chunk ids
+                      local to the batch, in any order (stored by entity, then chunk, stably: the
+                      order index_build.build_graph gives the same rows).
+        Each part is required exactly when the index has that channel.  Everything is validated
+        before the first change and the new arrays are swapped in last: a failure leaves the index
+        answering over the old rows.  Synchronises the main and the side stream (not a query-path
+        call).  Not supported on a document shard of a sharded index."""
+        P = self._validate_append(docs, lex, collections, tokens, mentions, n_rows)
+        m, n_old = P["m"], self.n_docs
+        if m == 0:
+            return range(n_old, n_old)
+        n_new = n_old + m
+        new = {}          # name -> (buffer, logical rows): swapped in at the end
+        state = {}
+        # ---- dense rows: norms of the new rows, float16 image of the tail tiles
+        if self.docs is not None:
+            rows = self._t(P["docs"], torch.float32)
+            want, tail16, err, t0 = self._dense_flavour_after(rows, n_new)
+            dn, inv = N.doc_norms(rows)
+            self._sync_streams()
+            for name, view, tail in (("docs", self.docs, rows), ("dnorm", self.dnorm, dn), ("inv_norm", self.inv_norm, inv)):
+                buf = self._buffer(name, view, n_new)
+                buf[n_old:n_new].copy_(tail)
+                new[name] = (buf, n_new)
+            state.update(shortlist=want, doc_rel_err=err)
+        else:
+            self._sync_streams()
+            want, tail16 = None, None
+        if P["collections"] is not None:
+            buf = self._buffer("doc_coll", self.doc_coll, n_new)
+            buf[n_old:n_new].copy_(self._t(P["collections"], torch.int32))
+            new["doc_coll"] = (buf, n_new)
+        if P["tokens"] is not None:
+            tok = self._t(P["tokens"], torch.float16)
+            buf = self._buffer("tokens", self.tokens, n_new)
+            buf[n_old:n_new].copy_(N.maxsim_pack(tok) if self.tokens_packed else tok)   # (the layout is doc-local)
+            new["tokens"] = (buf, n_new)
+        dest = {}         # CSR payload name -> the capacity buffer it was appended into
+        lex_new = self._append_lexical(P["lex"], n_old, n_new, new, dest) if P["lex"] is not None else None
+        graph_new = self._append_mentions(P["mentions"], n_old, dest) if P["mentions"] is not None else None
+        if tail16 is not None:    # last: the one write that lands inside the old logical extent
+            rows16 = (n_new + 31) // 32 * 32    # (the old last tile's NaN padding becomes rows)
+            buf = self._buffer("docs16", self.docs16, rows16)
+            buf[t0:rows16].copy_(tail16)
+            new["docs16"] = (buf, rows16)
+        # ---- swap
+        # the buffers the CSRs were read from become the destinations of the next append
+        old = dict(self.lex or {}, **(self.graph or {}))
+        cap = self._csr_cap
+        self._spare = {k: cap[k] if k in cap and cap[k].data_ptr() == old[k].data_ptr() else old[k] for k in dest}
+        self._csr_cap = dest
+        if lex_new is not None:
+            self.lex = lex_new
+            self.df_local = self.df_global = lex_new.pop("df")
+        if graph_new is not None:
+            self.graph = graph_new
+        for name, (buf, n) in new.items():
+            self._backing[name] = buf
+            self._set_row_array(name, buf[:n])
+        if self.docs is not None:
+            self.shortlist, self.doc_rel_err = state["shortlist"], state["doc_rel_err"]
+            if self.shortlist not in ("f16",):
+                self.docs16 = None
+                self._backing.pop("docs16", None)
+        self.n_docs = n_new
+        # sized or cached for the old row count: the dense workspace (the threshold sample grows
+        # with n), the candidate lists of a pending dense_shortlist
+        self._ws = None
+        self._shortlist_of = None
+        torch.cuda.current_stream(self.device).synchronize()
+        return range(n_old, n_new)
+
+    def _csr_dest(self, name: str, like: torch.Tensor, nnz_new: int) -> torch.Tensor:
+        """Destination of a CSR append (out of place): the buffer the previous append read from
+        when it has the room, else a new one of max(need, GROWTH x the old size) elements."""
+        sp = self._spare.get(name)
+        if sp is not None and sp.shape[0] >= nnz_new and sp.dtype == like.dtype and sp.data_ptr() != like.data_ptr():
+            return sp
+        return torch.empty(max(nnz_new, int(self.GROWTH * like.shape[0])), dtype=like.dtype, device=self.device)
+
+    def _append_lexical(self, lex, n_old: int, n_new: int, new: dict, dest: dict) -> dict:
+        """The lexical side after the append, as a new ``self.lex`` dict (the old one is untouched)."""
+        d, t, f, n_vocab = lex
+        L = self.lex
+        # the delta CSR over the new rows, doc ids already in the index's numbering: no sort of old postings
+        rp_b, pd_b, ptf_b, dl_full, df_b = N.lexical_build(
+            self._t(d, torch.int32) + n_old, self._t(t, torch.int32),
+            None if f is None else self._t(f, torch.int32), n_new, n_vocab)
+        nnz = L["post_doc"].shape[0] + pd_b.shape[0]
+        rowptr, post_doc, post_tf, _ = N.csr_append(
+            L["rowptr"], L["post_doc"], L["post_tf"], rp_b, pd_b, ptf_b,
+            self._csr_dest("post_doc", L["post_doc"], nnz), self._csr_dest("post_tf", L["post_tf"], nnz))
+        dest.update(post_doc=post_doc, post_tf=post_tf)
+        post_doc, post_tf = post_doc[:nnz], post_tf[:nnz]
+        doclen_buf = self._buffer("doclen", L["doclen"], n_new)
+        doclen_buf[n_old:n_new].copy_(dl_full[n_old:n_new])
+        doclen = doclen_buf[:n_new]
+        # idf / avgdl as set_lexical_rows computes them: float64 numpy on the host from the device's df
+        df = rowptr[1:] - rowptr[:-1]
+        dfh = df.cpu().numpy().astype(np.float64)
+        idf = np.log(1.0 + (float(n_new) - dfh + 0.5) / (dfh + 0.5))
+        avgdl = float(doclen.sum(dtype=torch.float64).item()) / max(n_new, 1)
+        out = dict(rowptr=rowptr, post_doc=post_doc, post_tf=post_tf, doclen=doclen,
+                   idf=self._t(idf, torch.float64), avgdl=avgdl if avgdl > 0 else 1.0, k1=L["k1"], b=L["b"],
+                   dense_share=L["dense_share"])
+        out["bounds"] = N.bm25_bounds(rowptr, post_doc, post_tf, doclen, out["idf"], out["avgdl"], out["k1"], out["b"])
+        out["dense"] = N.bm25_dense_terms(rowptr, post_doc, post_tf, out["bounds"][2], n_new, out["dense_share"]) \
+            if out["dense_share"] > 0 else None
+        out["df"] = df
+        # (doclen is swapped in with the dict: only its backing buffer is noted among the row arrays)
+        new["doclen"] = (doclen_buf, n_new)
+        return out
+
+    def _append_mentions(self, mentions, n_old: int, dest: dict) -> dict:
+        """The graph side after the append (entity CSR unchanged; the chunk-major copy of the
+        mentions is rebuilt on next use, as after set_graph)."""
+        e, c, w = mentions
+        G = self.graph
+        n_ent = G["men_rowptr"].shape[0] - 1
+        e = self._t(e, torch.int64)
+        c = self._t(c, torch.int64)
+        w = torch.ones(e.shape[0], dtype=torch.float32, device=self.device) if w is None else self._t(w, torch.float32)
+        # the batch's mentions in the build's order: by entity, then chunk, stably
+        order = torch.sort(c, stable=True).indices
+        order = order[torch.sort(e[order], stable=True).indices]
+        rp_b = torch.zeros(n_ent + 1, dtype=torch.int64, device=self.device)
+        rp_b[1:] = torch.cumsum(torch.bincount(e, minlength=n_ent), 0)
+        mc_b = (c[order] + (self.doc_base + n_old)).to(torch.int32).contiguous()
+        mw_b = w[order].contiguous()
+        nnz = G["men_chunk"].shape[0] + mc_b.shape[0]
+        rowptr, mc, mw, _ = N.csr_append(G["men_rowptr"], G["men_chunk"], G["men_conf"], rp_b, mc_b, mw_b,
+                                         self._csr_dest("men_chunk", G["men_chunk"], nnz),
+                                         self._csr_dest("men_conf", G["men_conf"], nnz))
+        dest.update(men_chunk=mc, men_conf=mw)
+        return dict(ent_rowptr=G["ent_rowptr"], ent_col=G["ent_col"], men_rowptr=rowptr,
+                    men_chunk=mc[:nnz], men_conf=mw[:nnz])
 
     # ------------------------------------------------------------ channels
     def _workspace(self, nbytes: int) -> torch.Tensor:

@@ -228,7 +228,9 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
                            "section_heading": p.get("section_heading")} for p in parent_rows},
         collections=[r.get("collection") for r in child_rows]
         if any("collection" in r for r in child_rows) else None,
-        vocab=vocab, entity_names=[e.get("name", "") for e in entity_rows], doc_base=doc_base)
+        vocab=vocab, entity_names=[e.get("name", "") for e in entity_rows], doc_base=doc_base,
+        content_hashes=[r.get("content_hash") for r in child_rows]
+        if any(r.get("content_hash") is not None for r in child_rows) else None)
     hi = HostIndex(docs=docs, rowptr=rowptr, post_doc=pd, post_tf=ptf, doclen=dl, idf=idf,
                    avgdl=avgdl, store=store)
     if entity_rows:
@@ -243,23 +245,57 @@ _ARRAYS = ("docs", "rowptr", "post_doc", "post_tf", "doclen", "idf", "ent_rowptr
 _DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf")
 _DERIVED_SCALARS = ("doc_rel_err", "f16_layout", "lexical_tag", "dense_stride")
 _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modalities", "collections",
-                   "entity_names")
+                   "entity_names", "content_hashes")
+_NO_PAGE = np.iinfo(np.int32).min   # store_pages.npy: the SQL column is nullable (page INT)
+
+
+def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
+    """After ``GpuIndex.append_rows`` (the ingest seam, rag2/ingest.py:361-470) the device holds
+    rows the HostIndex has never seen: pull the source arrays back, in place, so that ``hi`` --
+    and a ``save`` of it -- equals a build from all the rows.  The store is appended to by the
+    client (``CorpusStore.append``) and is not touched here."""
+    g = gpu_index
+    if g.docs is not None:
+        hi.docs = g.docs.cpu().numpy()
+    if g.lex is not None:
+        L = g.lex
+        hi.rowptr, hi.post_doc, hi.post_tf = (L[k].cpu().numpy() for k in ("rowptr", "post_doc", "post_tf"))
+        hi.doclen, hi.idf, hi.avgdl = L["doclen"].cpu().numpy(), L["idf"].cpu().numpy(), float(L["avgdl"])
+    if g.graph is not None:
+        G = g.graph
+        hi.men_rowptr, hi.men_chunk, hi.men_conf = (G[k].cpu().numpy() for k in ("men_rowptr", "men_chunk", "men_conf"))
+    if hi.tokens is not None and len(hi.tokens) != g.n_docs:
+        if g.tokens_packed:
+            raise ValueError("the index keeps its token store in the packed layout only: the appended rows' "
+                             "token matrices cannot be pulled back -- append them to HostIndex.tokens before save()")
+        hi.tokens = g.tokens.cpu().numpy()
+    hi.derived = None   # (computed for the old rows; save(hi, path, gpu_index) exports the current ones)
+    return hi
+
 
 
 def save(hi: HostIndex, path: str, gpu_index=None) -> None:
     """``gpu_index``: the GpuIndex built from ``hi`` -- what its set-up computed on the device
     (export_derived) is saved too, so that a later ``load(path).to_gpu()`` does not recompute it."""
     os.makedirs(path, exist_ok=True)
+    if gpu_index is not None and gpu_index.n_docs != len(hi.docs):
+        refresh_from_gpu(hi, gpu_index)     # rows were appended on the device: never save the stale arrays
+    if hi.store is not None and len(hi.store.child_ids) != len(hi.docs):
+        raise ValueError(f"the row store holds {len(hi.store.child_ids)} chunks, the index {len(hi.docs)}: "
+                         "they were not appended to together (GpuIndexClient.insert_children does both)")
     for name in _ARRAYS:
         arr = getattr(hi, name)
         if arr is not None:
             np.save(os.path.join(path, name + ".npy"), arr, allow_pickle=False)
     meta: Dict[str, Any] = {"avgdl": hi.avgdl, "format": 2}
     derived = gpu_index.export_derived() if gpu_index is not None else hi.derived
+    for name in _DERIVED_ARRAYS:   # a directory saved before may hold derived arrays this index does not have
+        fp = os.path.join(path, "derived_" + name + ".npy")
+        if derived and derived.get(name) is not None:
+            np.save(fp, np.asarray(derived[name]), allow_pickle=False)
+        elif os.path.exists(fp):
+            os.remove(fp)
     if derived:
-        for name in _DERIVED_ARRAYS:
-            if derived.get(name) is not None:
-                np.save(os.path.join(path, "derived_" + name + ".npy"), np.asarray(derived[name]), allow_pickle=False)
         meta["derived"] = {k: derived[k] for k in _DERIVED_SCALARS if derived.get(k) is not None}
     if hi.store is not None:
         s = hi.store
@@ -272,7 +308,8 @@ def save(hi: HostIndex, path: str, gpu_index=None) -> None:
             np.save(os.path.join(path, f"store_{name}_blob.npy"), np.asarray(col.blob), allow_pickle=False)
             np.save(os.path.join(path, f"store_{name}_off.npy"), np.asarray(col.offsets), allow_pickle=False)
             columns.append(name)
-        np.save(os.path.join(path, "store_pages.npy"), np.asarray(s.pages, dtype=np.int32), allow_pickle=False)
+        np.save(os.path.join(path, "store_pages.npy"),
+                np.asarray([_NO_PAGE if pg is None else pg for pg in s.pages], dtype=np.int32), allow_pickle=False)
         voc = list(s.vocab.items())
         vcol = StringColumn.from_strings([k for k, _ in voc])
         np.save(os.path.join(path, "store_vocab_blob.npy"), np.asarray(vcol.blob), allow_pickle=False)
@@ -308,7 +345,9 @@ def load(path: str, mmap: bool = True) -> HostIndex:
             vocab = dict(zip(vcol, (int(v) for v in arr("store_vocab_ids"))))
             store = CorpusStore(child_ids=cols["child_ids"], parent_ids=cols["parent_ids"],
                                 document_ids=cols["document_ids"], texts=cols["texts"],
-                                pages=arr("store_pages").tolist(), modalities=cols["modalities"], parents=ms["parents"],
+                                pages=[None if pg == _NO_PAGE else pg for pg in arr("store_pages").tolist()],
+                                modalities=cols["modalities"], parents=ms["parents"],
                                 collections=cols.get("collections"), vocab=vocab,
-                                entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"])
+                                entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"],
+                                content_hashes=cols.get("content_hashes"))
     return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, **arrays)

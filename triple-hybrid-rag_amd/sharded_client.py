@@ -89,6 +89,16 @@ class _ShardEndpoint(GpuIndexClient):
         self._seq = 0
         self._closed = False
 
+    def insert_children(self, rows, embedding_key: str = "embedding_1024"):
+        """Not supported: which rank takes the rows, and the collective df / length all-reduce an
+        append to a document-sharded index needs, are not built (Incremental ingest)."""
+        raise N.NativeError("insert is not supported through a sharded index client: rebuild the shards "
+                            "(appends to a document-sharded index are out of scope)")
+
+    def insert_parents(self, rows):
+        raise N.NativeError("insert is not supported through a sharded index client: rebuild the shards "
+                            "(appends to a document-sharded index are out of scope)")
+
     # ---------------------------------------------------------------- messages
     def _broadcast(self, msg: Optional[torch.Tensor]) -> torch.Tensor:
         if msg is None:
