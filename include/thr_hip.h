@@ -50,6 +50,7 @@ enum {
                                * beyond k ~ 200 queries increasingly take the exhaustive path
                                * (still exact, much slower) */
 #define THR_BM25_MAX_TERMS 32
+#define THR_BM25_MAX_QUERIES (1 << 20) /* queries of one thr_bm25_topk call (the caller splits a larger batch) */
 #define THR_GRAPH_MAX_SEEDS 16
 #define THR_RRF_MAX_PER_CHANNEL 128
 #define THR_TOPK_MAX 128      /* bm25 / graph k upper bound */
@@ -303,6 +304,14 @@ int thr_bm25_bounds(const int64_t *rowptr, const int32_t *post_doc, const int32_
  * atomic max and are merged at the end -- a stop-word query is the job of many workgroups, not
  * of one.  ``workspace`` >= thr_bm25_workspace_bytes(n_queries, max_terms, k): item list, slice
  * edges, per-slice lists.
+ * Batch size: the item list has 3 * n_queries + 32768 slots -- two per query and 16384 for the sweeps
+ * and the workgroup walk, one per query and 16384 for the waves' slices -- and the slice sizes of a batch
+ * are doubled until its slices fit.  Every query can be a single item of its walk (plus one sweep), so
+ * every batch is planned in a bounded number of passes.  The workspace is 48 + 4 * max_terms bytes per
+ * query and 368 + 8 * max_terms + 16 * k bytes per slot (item, sweep entry, slice edges, the waves'
+ * records, per-slice list and count), each array rounded up to 256 bytes.  More than
+ * THR_BM25_MAX_QUERIES queries in one call return THR_ERR_UNSUPPORTED before anything is launched (item
+ * counts are 32 bits), and thr_bm25_workspace_bytes returns 0 for them, as for any size it does not take.
  * Wave walk (round 4, same ABI): with the bounds and impacts given, k <= 64 and the OR form, every
  * query of <= 8 terms is cut into slices of ~640-1536 postings instead and ONE WAVE walks a slice
  * (bm25_walk_wave_kernel: no workgroup barrier, sixteen waves -- sixteen independent latency chains --

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """BM25 kernel alone at the bench shape (1M docs, 2048 queries of 4 terms): the bench's query mix
 (stop words excluded) and the df-proportional mix (stop words included), with and without the
-WAND-style bounds; results checked equal.  python3 scripts/bench_bm25.py [docs] [queries]"""
+WAND-style bounds; results checked equal.  Per mix also what the planner chose for the call with
+bounds: the number of work items and the postings a stage-A / wave slice was aimed at (the control
+words at the start of the lexical workspace).  Any batch up to THR_BM25_MAX_QUERIES, also above
+the waves' 16384 tuned item slots.  python3 scripts/bench_bm25.py [docs] [queries]"""
 import json
 import os
 import sys
@@ -57,11 +60,13 @@ def main():
         post = sum(int(csr.df_local[t]) for row in qt for t in row if t >= 0)
         ms_all = timed(lambda: idx.bm25_search(qd, 50, prune=False))
         ms = timed(lambda: idx.bm25_search(qd, 50, prune=True))
+        ctl = idx._ws_lex[:64].view(torch.int32).cpu()   # (bm_layout: off_ctl is 0; the device is idle after timed())
         out[name] = {"queries": len(qt), "postings_per_query": round(post / len(qt), 1),
                      "ms_every_posting_scored": round(ms_all, 3), "ms_with_bounds": round(ms, 3),
                      # (bytes of EVERY posting over time: an HBM rate only for the unpruned call)
                      "every_posting_scored_GBps": round((post * 12 + len(qt) * 64) / ms_all / 1e6, 1),
                      "pruned_equivalent_GBps_not_a_traffic_figure": round((post * 12 + len(qt) * 64) / ms / 1e6, 1),
+                     "work_items": int(ctl[0]), "stage_a_slice_postings": int(ctl[7]),
                      "bit_equal_to_oracle": f"{ok}/{len(sub)}"}
     print(json.dumps(out))
 

@@ -49,6 +49,44 @@ def test_host_side_argument_checks_do_not_need_a_gpu():
                             None, None) == -1
 
 
+def test_bm25_batch_limit_and_workspace_growth_are_host_arithmetic():
+    """One thr_bm25_topk call takes at most THR_BM25_MAX_QUERIES queries: a larger batch is
+    refused on the host, before any pointer is looked at and before anything is launched (the
+    library without the limit answered these null pointers with THR_ERR_INVALID).  Below it the
+    item list has one wave slot per query on top of the tuned 16384 -- what lets the plan
+    kernel's fit loop end for every batch -- and the workspace grows as the header documents."""
+    import pytest
+    N = T._native
+    lib = N.load()
+    limit = N.THR_BM25_MAX_QUERIES
+    header = open(os.path.join(ROOT, "include", "thr_hip.h")).read()
+    assert re.search(r"#define\s+THR_BM25_MAX_QUERIES\s+\(1 << 20\)", header) and limit == 1 << 20
+
+    def call(nq):
+        return lib.thr_bm25_topk(None, None, None, None, None, None, None, None, None, None, None, 0, 1.0, 1.2,
+                                 0.75, 10, 5, 0, None, nq, 4, 10, 0, None, None, None, None, None, None, 0, None)
+    assert call(limit + 1) == -2 and call(2 ** 31 - 1) == -2       # THR_ERR_UNSUPPORTED
+    assert call(limit) == -1 and call(20000) == -1                  # (null pointers: THR_ERR_INVALID)
+    assert lib.thr_error_string(-2) == b"unsupported shape"
+    assert lib.thr_bm25_workspace_bytes(limit + 1, 4, 10) == 0
+    assert lib.thr_bm25_workspace_bytes(limit, 32, 128) > 0
+    with pytest.raises(N.NativeError, match=str(limit)):
+        N.bm25_check_batch(limit + 1)
+    N.bm25_check_batch(limit)
+    # monotonic in n_queries across the waves' tuned 16384 slots, and linear with the documented
+    # slope: 48 + 4 mt bytes per query, three item slots of 368 + 8 mt + 16 k bytes per query
+    # (each of the 20 arrays is rounded up to 256 bytes)
+    for mt, k in ((4, 10), (8, 50), (32, 128)):
+        sizes = [lib.thr_bm25_workspace_bytes(nq, mt, k) for nq in (1, 2048, 16383, 16384, 16385, 20000, 65537, limit)]
+        assert all(a < b for a, b in zip(sizes, sizes[1:]))
+        per_query = 48 + 4 * mt + 3 * (368 + 8 * mt + 16 * k)
+        for lo, hi in ((2048, 16384), (16384, 16385), (16384, 40000), (40000, limit)):
+            grow = lib.thr_bm25_workspace_bytes(hi, mt, k) - lib.thr_bm25_workspace_bytes(lo, mt, k)
+            assert abs(grow - (hi - lo) * per_query) <= 20 * 256, (mt, k, lo, hi, grow)
+        # ... of which the waves' slot per query is this change's
+        assert lib.thr_bm25_workspace_bytes(2048, mt, k) >= (3 * 2048 + 32768) * (368 + 8 * mt + 16 * k)
+
+
 def test_host_side_planning_functions():
     """Sizes and the query-tile choice are pure host arithmetic (no launch)."""
     N = T._native

@@ -21,6 +21,7 @@ THR_FLAG_OVERFLOW = 2
 THR_FLAG_EXACT = 4
 THR_DENSE_MAX_K = 256
 THR_BM25_MAX_TERMS = 32
+THR_BM25_MAX_QUERIES = 1 << 20
 THR_GRAPH_MAX_SEEDS = 16
 THR_RRF_MAX_PER_CHANNEL = 128
 THR_TOPK_MAX = 128
@@ -595,6 +596,13 @@ def bm25_workspace_bytes(n_queries: int, max_terms: int, k: int) -> int:
     return int(load().thr_bm25_workspace_bytes(n_queries, max_terms, k))
 
 
+def bm25_check_batch(n_queries: int) -> None:
+    """One thr_bm25_topk call takes at most THR_BM25_MAX_QUERIES queries (its item counts are 32 bits)."""
+    if n_queries > THR_BM25_MAX_QUERIES:
+        raise NativeError(f"bm25: {n_queries} queries in one call, the limit is {THR_BM25_MAX_QUERIES} "
+                          "(THR_BM25_MAX_QUERIES): split the batch")
+
+
 def bm25_topk(rowptr, post_doc, post_tf, doclen, idf, avgdl: float, query_terms, k: int,
               id_base: int = 0, k1: float = 1.2, b: float = 0.75, bounds=None,
               conjunctive: bool = False, doc_coll=None, query_coll=None,
@@ -612,6 +620,7 @@ def bm25_topk(rowptr, post_doc, post_tf, doclen, idf, avgdl: float, query_terms,
     if post_doc.shape != post_tf.shape or idf.shape[0] + 1 != rowptr.shape[0]:
         raise NativeError("bm25: CSR arrays are inconsistent")
     nq, mt = query_terms.shape
+    bm25_check_batch(nq)
     if mt > THR_BM25_MAX_TERMS or k > THR_TOPK_MAX:
         raise NativeError("bm25: too many terms per query or k too large")
     ptu = pbu = pim = None

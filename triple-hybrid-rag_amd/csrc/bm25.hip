@@ -187,6 +187,11 @@ constexpr int BM_TARGET_MIN = 8192;    // ... and at least (one pass), when it d
                                        // call spreads its 75 K postings over nine workgroups
 constexpr int PLAN_THREADS = 256;       // bm25_plan_kernel: one query per thread in as many workgroups as that takes (<= 64);
 constexpr int PLAN_MAX_BLOCKS = 64;     // the workgroup that finishes last cuts the slices and writes the item list
+// bm25_plan_kernel's fit loop doubles a slice size whose items do not fit, up to BM_TARGET_OPEN -- a size no query
+// reaches (at most 32 lists of < 2^31 postings, < 2^31 docs): every query is then its fewest items, which the
+// item list always holds (bm_layout) -- and at most BM_FIT_PASSES times (both sizes are there after 58 doublings)
+constexpr int BM_FIT_PASSES = 64;
+constexpr long long BM_TARGET_OPEN = 1ll << 40;
 
 __device__ __forceinline__ int bm_slices(long long tot, long long target);
 // stage-A slices of a query with dense terms: none when its other terms have no posting
@@ -381,10 +386,14 @@ __global__ __launch_bounds__(PLAN_THREADS) void bm25_plan_kernel(
         target_a = target_a < WW_TARGET_MIN ? WW_TARGET_MIN : target_a > WW_TARGET_MAX ? WW_TARGET_MAX : target_a;
     }
     // ``cap`` items for the sweeps and the workgroup walk's items (the slice size that budget gives them
-    // was tuned with it), ``cap_wave`` more for the waves' ~1 K-posting slices
+    // was tuned with it), ``cap_wave`` more for the waves' ~1 K-posting slices.  A slice size that does not
+    // fit is doubled, up to BM_TARGET_OPEN and at most BM_FIT_PASSES times: the last pass counts every query
+    // at BM_TARGET_OPEN -- one item of the waves, or one of the workgroup walk, or a stage A and one sweep --,
+    // and cap >= 2 nq, cap_wave >= nq hold that (bm_layout).  The loop ends whatever the batch.
     __shared__ int red_w[PLAN_THREADS];
     int total = 0, mine = 0;
-    for (;;) {
+    for (int pass = 0;; ++pass) {
+        if (pass == BM_FIT_PASSES) target = target_a = BM_TARGET_OPEN;
         mine = 0;
         int mine_w = 0;
         for (int q = q0; q < q1; ++q) {
@@ -413,12 +422,13 @@ __global__ __launch_bounds__(PLAN_THREADS) void bm25_plan_kernel(
         const bool grow_w = red_w[0] > cap_wave;
         __syncthreads();
         mine += mine_w;
-        if (fits) break;   // (every query is one or two items once the targets reach its totals: terminates)
+        if (fits || pass == BM_FIT_PASSES) break;
         if (grow_w) {
-            target_a *= 2;
+            target_a = target_a < BM_TARGET_OPEN / 2 ? target_a * 2 : BM_TARGET_OPEN;
             continue;
         }
-        target *= 2;
+        target = target < BM_TARGET_OPEN / 2 ? target * 2 : BM_TARGET_OPEN;
+        if (!wave_mode) target_a = target;   // (stage A on the workgroup walk: its slices are in ``cap`` and grow with the others)
     }
     // exclusive prefix of the per-thread item counts
     red[threadIdx.x] = mine;
@@ -1437,7 +1447,7 @@ constexpr int WW_WAVES = 4;        // waves per workgroup (independent: they nev
 constexpr int WW_STAGE = 1024;     // doc ids a wave stages per pass
 constexpr int WW_CAP = 128;        // top-k slots of a wave (k <= 64: a batch of 64 always fits after a cut)
 constexpr int WW_BLOOM = 256;      // words of Bloom bits per wave, shared out among the lists with postings
-constexpr int BM_WAVE_ITEMS = 16384;   // item slots for the waves' slices, on top of the list's capacity
+constexpr int BM_WAVE_ITEMS = 16384;   // item slots for the waves' slices beyond one per query, on top of the list's capacity
 
 struct WwLds {
     int32_t st_doc[WW_STAGE];
@@ -2382,19 +2392,21 @@ __global__ __launch_bounds__(BMM_THREADS) void bm25_merge_kernel(
 struct BmLayout {
     size_t off_ctl, off_theta, off_tot, off_dub, off_sweep, off_nt, off_S, off_SA, off_pmask, off_item0, off_long, off_qterms, off_items,
         off_ipos, off_wrec, off_wterm, off_ss, off_sid, off_scnt, off_stamps, total;
-    int cap, cap_base;
+    int cap, cap_base, cap_wave;   // item slots: all / sweeps + workgroup walk / waves
 };
 static BmLayout bm_layout(int nq, int mt, int k) {
     BmLayout L;
     static int extra = 0;
     if (!extra) {
         const char* ev = getenv("THR_BM25_ITEMS");   // item slots beyond two per query (A/B knob)
-        extra = ev && atoi(ev) >= 1024 ? atoi(ev) : BM_EXTRA_ITEMS;
+        extra = ev && atoi(ev) >= 1024 && atoi(ev) <= (1 << 24) ? atoi(ev) : BM_EXTRA_ITEMS;   // (L.cap stays far below 2^31)
     }
     // (a query with dense terms is at least two items: stage A, stage B; the wave walk cuts stage A
-    // into ~1 K-posting slices: 16 K more items for them)
+    // into ~1 K-posting slices: 16 K more items for them, and one per query -- the fewest the waves
+    // can be given, so that bm25_plan_kernel's fit loop always has a slice size that fits)
     L.cap_base = 2 * nq + extra;
-    L.cap = L.cap_base + BM_WAVE_ITEMS;
+    L.cap_wave = nq + BM_WAVE_ITEMS;
+    L.cap = L.cap_base + L.cap_wave;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         size_t o = off;
@@ -2493,7 +2505,7 @@ extern "C" int thr_bm25_dense_rows(const int64_t* rowptr, const int32_t* post_do
 }
 
 extern "C" size_t thr_bm25_workspace_bytes(int n_queries, int max_terms, int k) {
-    if (n_queries <= 0 || max_terms <= 0 || k <= 0) return 0;
+    if (n_queries <= 0 || n_queries > THR_BM25_MAX_QUERIES || max_terms <= 0 || k <= 0) return 0;
     return bm_layout(n_queries, max_terms, k).total;
 }
 
@@ -2508,6 +2520,9 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
                              double* out_scores, int64_t* out_ids, int32_t* out_counts,
                              void* workspace, size_t workspace_bytes, thr_stream_t stream) {
     clear_status();
+    // (the item counts and indices of a batch are 32 bits: 3 n_queries + 32 K slots, 256 slices per query
+    // at most; the caller splits a larger batch)
+    THR_RETURN_IF(n_queries > THR_BM25_MAX_QUERIES, THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(!rowptr || !post_doc || !post_tf || !doclen || !idf || !query_terms ||
                       !out_scores || !out_ids || !out_counts || !workspace,
                   THR_ERR_INVALID);
@@ -2571,7 +2586,7 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     int plan_blocks = (n_queries + PLAN_THREADS - 1) / PLAN_THREADS;
     plan_blocks = plan_blocks > PLAN_MAX_BLOCKS ? PLAN_MAX_BLOCKS : plan_blocks;
     hipLaunchKernelGGL(bm25_plan_kernel, dim3(plan_blocks), dim3(PLAN_THREADS), 0, st, rowptr, n_vocab, query_terms,
-                       n_queries, max_terms, L.cap_base, BM_WAVE_ITEMS, conjunctive, grid, BM_TARGET0, wave ? bm_num_cus() * 4 * WW_WAVES : 0, wave ? 1 : 0, walk_div, dslot, term_ub, n_docs, ctl,
+                       n_queries, max_terms, L.cap_base, L.cap_wave, conjunctive, grid, BM_TARGET0, wave ? bm_num_cus() * 4 * WW_WAVES : 0, wave ? 1 : 0, walk_div, dslot, term_ub, n_docs, ctl,
                        q_tot, q_dub, q_nt, q_S, q_SA, q_pmask, q_item0, q_long, q_terms, items);
     const int64_t edge_threads = (int64_t)L.cap * max_terms;
     hipLaunchKernelGGL(bm25_edges_kernel, dim3((unsigned)((edge_threads + 255) / 256)), dim3(256), 0, st,

@@ -800,9 +800,11 @@ class GpuIndex:
 
     def bm25_search(self, query_terms: torch.Tensor, k: int, collections=None,
                     conjunctive: bool = False, prune: bool = True, dense_rows: bool = True):
-        """collections: int32 [nq] collection id per query (-1 = unfiltered) or None."""
+        """collections: int32 [nq] collection id per query (-1 = unfiltered) or None.
+        One call takes at most N.THR_BM25_MAX_QUERIES (2^20) queries; a larger batch is refused."""
         L = self.lex
         qt = self._t(query_terms, torch.int32)
+        N.bm25_check_batch(qt.shape[0])
         dc, qc = self._qcoll(collections, qt.shape[0])
         need = N.bm25_workspace_bytes(qt.shape[0], qt.shape[1], k)
         # ONE lexical workspace per index, used from whichever stream the caller is on (the main
