@@ -1,8 +1,9 @@
 """Builds libthr_hip.so (the C-ABI of include/thr_hip.h) in-tree with hipcc for gfx950.
 
-Every ``csrc/*.hip`` is compiled to its own object (in parallel, only when the source, a
-shared header or the flags changed) and the objects are linked into one shared library --
-no device symbol crosses a file, so no relocatable device code is needed."""
+Every ``csrc/*.hip`` -- one per kernel family -- is compiled to its own object (in parallel, only
+when the source, a shared header or the flags changed) and the objects of the sources that exist
+are linked into one shared library: no device symbol crosses a file, so no relocatable device code
+is needed, and an object left in build/ by a source since removed or renamed is never linked."""
 from __future__ import annotations
 
 import glob
@@ -49,20 +50,32 @@ def _obj_stale(src: str) -> bool:
     return any(os.path.getmtime(d) > t for d in [src] + _headers())
 
 
+def _jobs(n: int) -> int:
+    """Compilers to run at once: one per source, at most 16, at most MAX_JOBS when that is set."""
+    cap = min(16, os.cpu_count() or 1)
+    if os.environ.get("MAX_JOBS", "").isdigit():
+        cap = min(cap, int(os.environ["MAX_JOBS"]))
+    return max(1, min(n, cap))
+
+
 def build_variant(name: str, defines, only=("bm25",)) -> str:
-    """An A/B build: the sources in ``only`` recompiled with extra -D flags, linked with the
-    regular objects into build/libthr_<name>.so (load it with THR_LIB_PATH)."""
+    """An A/B build: the kernel families in ``only`` (every source whose name is one of them or
+    starts with one and an underscore: the units of a family share its headers, which the flags
+    may change) recompiled with extra -D flags, linked with the regular objects into
+    build/libthr_<name>.so (load it with THR_LIB_PATH)."""
     build_native()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    objs = []
+    objs, todo = [], []
     for src in sources():
         base = os.path.basename(src)[:-4]
-        if base in only:
+        if any(base == f or base.startswith(f + "_") for f in only):
             o = os.path.join(OBJ_DIR, f"{base}.{name}.o")
-            subprocess.check_call([hipcc] + HIPCC_FLAGS + [f"-D{d}" for d in defines] + ["-c", src, "-o", o])
+            todo.append([hipcc] + HIPCC_FLAGS + [f"-D{d}" for d in defines] + ["-c", src, "-o", o])
             objs.append(o)
         else:
             objs.append(_obj(src))
+    with ThreadPoolExecutor(max_workers=_jobs(len(todo))) as ex:
+        list(ex.map(subprocess.check_call, todo))
     out = os.path.join(OBJ_DIR, f"libthr_{name}.so")
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
     return out
@@ -120,7 +133,7 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
                     pass
         open(_obj(src) + "." + _stamp(), "w").close()
 
-    with ThreadPoolExecutor(max_workers=min(len(todo) or 1, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=_jobs(len(todo))) as ex:
         list(ex.map(compile_one, todo))
     tmp_lib = f"{LIB_PATH}.tmp{os.getpid()}"
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [_obj(s) for s in sources()] + \

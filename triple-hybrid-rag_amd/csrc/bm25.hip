@@ -579,9 +579,11 @@ constexpr int BM_NSTAMP = 20;   // 0-13 phases (cycles), 14-19 counters
         }                                                                 \
     } while (0)
 #define BM_COUNT(i, v) do { if (threadIdx.x == 0) stamp_acc[i] += (unsigned long long)(v); } while (0)
+#define BM_STAMPS_ONLY(...) __VA_ARGS__
 #else
 #define BM_STAMP(i)
 #define BM_COUNT(i, v)
+#define BM_STAMPS_ONLY(...)
 #endif
 
 // DPM: 0 = ordinary queries only, 1 = stage-A slices only, 2 = both kinds in one launch (decided per item)
@@ -2390,11 +2392,29 @@ __global__ __launch_bounds__(BMM_THREADS) void bm25_merge_kernel(
 
 // ---- workspace of thr_bm25_topk ----
 struct BmLayout {
-    size_t off_ctl, off_theta, off_tot, off_dub, off_sweep, off_nt, off_S, off_SA, off_pmask, off_item0, off_long, off_qterms, off_items,
-        off_ipos, off_wrec, off_wterm, off_ss, off_sid, off_scnt, off_stamps, total;
+    int32_t* ctl;                  // [0] items, [1] [2] [4] next item of a kernel, [3] queries with dense terms, [5] sweeps, [6] plan workgroups done, [7] stage-A slice size, [8] queries of the workgroup walk  } zeroed
+    unsigned long long* theta;     // shared thresholds (keys)   } per call
+    int64_t* q_tot;
+    double* q_dub;
+    int32_t *q_nt, *q_S, *q_SA, *q_pmask, *q_item0, *q_long, *q_terms;
+    int2* items;
+    int32_t *sweep_items, *ipos;
+    WwItem* wrec;
+    WwTerm* wterm;
+    double* slice_s;
+    int64_t* slice_id;
+    int32_t* slice_cnt;
+    BM_STAMPS_ONLY(unsigned long long* stamps;)
+    size_t total;
     int cap, cap_base, cap_wave;   // item slots: all / sweeps + workgroup walk / waves
 };
-static BmLayout bm_layout(int nq, int mt, int k) {
+#ifdef BM_STAMPS
+}  // namespace thr
+#include "bm25_stamps.hpp"
+namespace thr {
+#endif
+// The workspace carved from `ws`; from null, its size alone.
+static BmLayout bm_layout(void* ws, int nq, int mt, int k) {
     BmLayout L;
     static int extra = 0;
     if (!extra) {
@@ -2407,48 +2427,30 @@ static BmLayout bm_layout(int nq, int mt, int k) {
     L.cap_base = 2 * nq + extra;
     L.cap_wave = nq + BM_WAVE_ITEMS;
     L.cap = L.cap_base + L.cap_wave;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    L.off_ctl = take(sizeof(int32_t) * 16);                 // [0] items, [1] [2] [4] next item of a kernel, [3] queries with dense terms, [5] sweeps, [6] plan workgroups done, [7] stage-A slice size, [8] queries of the workgroup walk  } zeroed
-    L.off_theta = take(sizeof(unsigned long long) * nq);   // shared thresholds (keys)   } per call
-    L.off_tot = take(sizeof(int64_t) * nq);
-    L.off_dub = take(sizeof(double) * nq);
-    L.off_nt = take(sizeof(int32_t) * nq);
-    L.off_S = take(sizeof(int32_t) * nq);
-    L.off_SA = take(sizeof(int32_t) * nq);
-    L.off_pmask = take(sizeof(int32_t) * nq);
-    L.off_item0 = take(sizeof(int32_t) * nq);
-    L.off_long = take(sizeof(int32_t) * nq);
-    L.off_qterms = take(sizeof(int32_t) * (size_t)nq * mt);
-    L.off_items = take(sizeof(int2) * (size_t)L.cap);
-    L.off_sweep = take(sizeof(int32_t) * (size_t)L.cap);
-    L.off_ipos = take(sizeof(int32_t) * 2 * (size_t)L.cap * mt);
-    L.off_wrec = take(sizeof(WwItem) * (size_t)L.cap);
-    L.off_wterm = take(sizeof(WwTerm) * (size_t)L.cap * 8);
-    L.off_ss = take(sizeof(double) * (size_t)L.cap * k);
-    L.off_sid = take(sizeof(int64_t) * (size_t)L.cap * k);
-    L.off_scnt = take(sizeof(int32_t) * (size_t)L.cap);
-#ifdef BM_STAMPS
-    L.off_stamps = take(sizeof(unsigned long long) * (3 * 4096 * (BM_NSTAMP + 1) + 8 * (size_t)L.cap));
-#endif
-    L.total = off;
+    const size_t cap = (size_t)L.cap;
+    Arena A{(char*)ws};
+    L.ctl = A.take<int32_t>(16);
+    L.theta = A.take<unsigned long long>(nq);
+    L.q_tot = A.take<int64_t>(nq);
+    L.q_dub = A.take<double>(nq);
+    L.q_nt = A.take<int32_t>(nq);
+    L.q_S = A.take<int32_t>(nq);
+    L.q_SA = A.take<int32_t>(nq);
+    L.q_pmask = A.take<int32_t>(nq);
+    L.q_item0 = A.take<int32_t>(nq);
+    L.q_long = A.take<int32_t>(nq);
+    L.q_terms = A.take<int32_t>((size_t)nq * mt);
+    L.items = A.take<int2>(cap);
+    L.sweep_items = A.take<int32_t>(cap);
+    L.ipos = A.take<int32_t>(2 * cap * mt);
+    L.wrec = A.take<WwItem>(cap);
+    L.wterm = A.take<WwTerm>(cap * 8);
+    L.slice_s = A.take<double>(cap * k);
+    L.slice_id = A.take<int64_t>(cap * k);
+    L.slice_cnt = A.take<int32_t>(cap);
+    BM_STAMPS_ONLY(L.stamps = A.take<unsigned long long>(bm_stamps_words(L.cap)));
+    L.total = A.total;
     return L;
-}
-
-static int bm_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
 }
 
 }  // namespace thr
@@ -2506,7 +2508,7 @@ extern "C" int thr_bm25_dense_rows(const int64_t* rowptr, const int32_t* post_do
 
 extern "C" size_t thr_bm25_workspace_bytes(int n_queries, int max_terms, int k) {
     if (n_queries <= 0 || n_queries > THR_BM25_MAX_QUERIES || max_terms <= 0 || k <= 0) return 0;
-    return bm_layout(n_queries, max_terms, k).total;
+    return bm_layout(nullptr, n_queries, max_terms, k).total;
 }
 
 extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, const int32_t* post_tf,
@@ -2534,34 +2536,12 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     THR_RETURN_IF(dense_slot && (!dense_imp || !dense_tf || !post_imp || !term_ub ||
                                  dense_stride < n_docs + BW_PAD || (dense_stride & 3)),
                   THR_ERR_INVALID);
-    const BmLayout L = bm_layout(n_queries, max_terms, k);
+    const BmLayout L = bm_layout(workspace, n_queries, max_terms, k);
     THR_RETURN_IF(workspace_bytes < L.total, THR_ERR_WORKSPACE);
-    char* ws = (char*)workspace;
     hipStream_t st = (hipStream_t)stream;
-    int32_t* ctl = (int32_t*)(ws + L.off_ctl);
-    unsigned long long* theta = (unsigned long long*)(ws + L.off_theta);
-    int64_t* q_tot = (int64_t*)(ws + L.off_tot);
-    double* q_dub = (double*)(ws + L.off_dub);
-    int32_t* sweep_items = (int32_t*)(ws + L.off_sweep);
-    int32_t* q_nt = (int32_t*)(ws + L.off_nt);
-    int32_t* q_S = (int32_t*)(ws + L.off_S);
-    int32_t* q_SA = (int32_t*)(ws + L.off_SA);
-    int32_t* q_pmask = (int32_t*)(ws + L.off_pmask);
-    int32_t* q_item0 = (int32_t*)(ws + L.off_item0);
-    int32_t* q_long = (int32_t*)(ws + L.off_long);
-    int32_t* q_terms = (int32_t*)(ws + L.off_qterms);
-    int2* items = (int2*)(ws + L.off_items);
-    int32_t* ipos = (int32_t*)(ws + L.off_ipos);
-    WwItem* wrec = (WwItem*)(ws + L.off_wrec);
-    WwTerm* wterm = (WwTerm*)(ws + L.off_wterm);
-    double* slice_s = (double*)(ws + L.off_ss);
-    int64_t* slice_id = (int64_t*)(ws + L.off_sid);
-    int32_t* slice_cnt = (int32_t*)(ws + L.off_scnt);
-    hipError_t e = hipMemsetAsync(ws + L.off_ctl, 0, L.off_tot - L.off_ctl, st);   // ctl + theta
+    hipError_t e = hipMemsetAsync(L.ctl, 0, (char*)L.q_tot - (char*)L.ctl, st);   // ctl + theta
     if (e != hipSuccess) return (int)e;
-#ifdef BM_STAMPS
-    (void)hipMemsetAsync(ws + L.off_stamps, 0, sizeof(unsigned long long) * (3 * 4096 * (BM_NSTAMP + 1) + 8 * (size_t)L.cap), st);
-#endif
+    BM_STAMPS_ONLY(bm_stamps_begin(L, st));
     static int small = -1, use_dense = 1, walk_div = 64, fuse_div = 8, use_wave = 1;
     if (small < 0) {
         const char* ei = getenv("THR_BM25_DENSE");    // 0: every term through its postings (A/B knob)
@@ -2577,7 +2557,7 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     }
     const bool big = small == 0, huge = small == 2;
     // persistent grid: as many workgroups as the chip holds at once (never more than items can exist)
-    int grid = bm_num_cus() * (huge ? 1 : big ? 2 : 4);
+    int grid = num_cus() * (huge ? 1 : big ? 2 : 4);
     if (grid > L.cap) grid = L.cap;
     const int32_t* dslot = use_dense ? dense_slot : nullptr;
     // OR queries of <= 8 terms by waves (bm25_walk_wave_kernel) when the impacts are there and k fits a
@@ -2586,36 +2566,31 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     int plan_blocks = (n_queries + PLAN_THREADS - 1) / PLAN_THREADS;
     plan_blocks = plan_blocks > PLAN_MAX_BLOCKS ? PLAN_MAX_BLOCKS : plan_blocks;
     hipLaunchKernelGGL(bm25_plan_kernel, dim3(plan_blocks), dim3(PLAN_THREADS), 0, st, rowptr, n_vocab, query_terms,
-                       n_queries, max_terms, L.cap_base, L.cap_wave, conjunctive, grid, BM_TARGET0, wave ? bm_num_cus() * 4 * WW_WAVES : 0, wave ? 1 : 0, walk_div, dslot, term_ub, n_docs, ctl,
-                       q_tot, q_dub, q_nt, q_S, q_SA, q_pmask, q_item0, q_long, q_terms, items);
+                       n_queries, max_terms, L.cap_base, L.cap_wave, conjunctive, grid, BM_TARGET0, wave ? num_cus() * 4 * WW_WAVES : 0, wave ? 1 : 0, walk_div, dslot, term_ub, n_docs, L.ctl,
+                       L.q_tot, L.q_dub, L.q_nt, L.q_S, L.q_SA, L.q_pmask, L.q_item0, L.q_long, L.q_terms, L.items);
     const int64_t edge_threads = (int64_t)L.cap * max_terms;
     hipLaunchKernelGGL(bm25_edges_kernel, dim3((unsigned)((edge_threads + 255) / 256)), dim3(256), 0, st,
-                       rowptr, post_doc, ctl, q_nt, q_S, q_SA, q_long, q_terms, items, max_terms, q_pmask, n_docs, ipos,
-                       idf, term_ub, dslot, dense_stride, query_coll, wave ? wrec : (WwItem*)nullptr,
-                       wave ? wterm : (WwTerm*)nullptr);
+                       rowptr, post_doc, L.ctl, L.q_nt, L.q_S, L.q_SA, L.q_long, L.q_terms, L.items, max_terms, L.q_pmask, n_docs, L.ipos,
+                       idf, term_ub, dslot, dense_stride, query_coll, wave ? L.wrec : (WwItem*)nullptr,
+                       wave ? L.wterm : (WwTerm*)nullptr);
     int rc = launch_status();
     if (rc) return rc;
-#ifdef BM_STAMPS
-    unsigned long long* d_stamps = (unsigned long long*)(ws + L.off_stamps);
-    if (grid > 4096) grid = 4096;
-#define BM_STAMP_ARG(DP) , d_stamps + (DP == 1 ? 2 : 0) * (size_t)4096 * (BM_NSTAMP + 1), d_stamps + (size_t)3 * 4096 * (BM_NSTAMP + 1) + 4 * (size_t)L.cap
-#else
-#define BM_STAMP_ARG(DP)
-#endif
+    BM_STAMPS_ONLY(if (grid > 4096) grid = 4096);   // (a stamp area holds 4096 workgroups)
     // Block shape: 512 threads / 8192 staged ids per pass / 75 KiB of LDS, two workgroups per CU --
     // a four-term query of the bench (6.7 K postings) is one pass.  THR_BM25_SHAPE=small selects
     // 256 threads / 4096 ids / 39 KiB, four per CU: the fixed cost of an item (set-up, staging, the
     // final sort) overlaps four ways, which wins when every list is short (2048 queries over lists
     // of <= 200 postings: 0.075 ms against 0.124 ms) and loses otherwise.
-#define THR_BM25_LAUNCH(T, S, W, C, DP)                                                            \
-    hipLaunchKernelGGL((bm25_topk_kernel<T, S, W, C, DP>), dim3(grid), dim3(T), 0, st, rowptr, post_doc, \
-                       post_tf, doclen, idf, term_ub, term_ub ? block_ub : nullptr,                 \
-                       term_ub ? post_imp : nullptr, dslot, dense_tf, dense_stride,    \
-                       avgdl, k1, b, (k1 + 1.0) / 255.0, 255.0 / (k1 + 1.0),                        \
-                       id_base, max_terms, k, conjunctive, doc_coll, query_coll, n_queries,         \
-                       wave ? -1 : dslot ? fuse_div : 0, ctl, q_nt, q_S,                            \
-                       q_SA, q_pmask, q_terms, items, ipos, theta, slice_s, slice_id, slice_cnt,    \
-                       out_scores, out_ids, out_counts BM_STAMP_ARG(DP))
+#define THR_BM25_LAUNCH(T, S, W, C, DP)                                                                     \
+    hipLaunchKernelGGL((bm25_topk_kernel<T, S, W, C, DP>), dim3(grid), dim3(T), 0, st, rowptr, post_doc,    \
+                       post_tf, doclen, idf, term_ub, term_ub ? block_ub : nullptr,                         \
+                       term_ub ? post_imp : nullptr, dslot, dense_tf, dense_stride,                         \
+                       avgdl, k1, b, (k1 + 1.0) / 255.0, 255.0 / (k1 + 1.0),                                \
+                       id_base, max_terms, k, conjunctive, doc_coll, query_coll, n_queries,                 \
+                       wave ? -1 : dslot ? fuse_div : 0, L.ctl, L.q_nt, L.q_S,                              \
+                       L.q_SA, L.q_pmask, L.q_terms, L.items, L.ipos, L.theta, L.slice_s, L.slice_id, L.slice_cnt, \
+                       out_scores, out_ids, out_counts                                                      \
+                       BM_STAMPS_ONLY(, bm_stamps_area(L, DP == 1 ? 2 : 0), bm_stamps_walk_log(L)))
 #define THR_BM25_LAUNCH_SHAPE(DP)                                                                     \
     do {                                                                                              \
         if (huge) THR_BM25_LAUNCH(1024, 16384, 8192, 2048, DP);   /* one 16-wave workgroup per CU */  \
@@ -2627,39 +2602,15 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     // (nothing, usually).  Else: queries with dense terms are stage A of the workgroup walk (fused with
     // the ordinary items, or on its own: the kernels themselves pick who works), the rest ordinary items.
     if (wave) {
-        int wgrid_w = bm_num_cus() * 4;   // sixteen waves per CU; a small batch has no use for thousands of waves
+        int wgrid_w = num_cus() * 4;   // sixteen waves per CU; a small batch has no use for thousands of waves
         if ((long long)n_queries * 32 + 32 < wgrid_w) wgrid_w = n_queries * 32 + 32;
         hipLaunchKernelGGL(bm25_walk_wave_kernel, dim3(wgrid_w), dim3(WW_WAVES * 64), 0, st, rowptr, post_doc,
                            post_tf, doclen, idf, term_ub, post_imp, dslot, dense_tf, dense_stride, avgdl, k1, b,
                            (k1 + 1.0) / 255.0, 255.0 / (k1 + 1.0),
-                           id_base, max_terms, k, doc_coll, query_coll, ctl, q_nt, q_S, q_SA, q_pmask, q_terms,
-                           items, ipos, wrec, wterm, theta, slice_s, slice_id, slice_cnt, out_scores, out_ids, out_counts
-#ifdef BM_STAMPS
-                           , (unsigned long long*)(ws + L.off_stamps)
-#endif
-                           );
-#ifdef BM_STAMPS
-        {
-            (void)hipStreamSynchronize(st);
-            const int nw = wgrid_w * WW_WAVES;
-            std::vector<unsigned long long> h((size_t)nw * 16);
-            (void)hipMemcpy(h.data(), ws + L.off_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            double tot[16] = {0};
-            double mx = 0;
-            for (int w = 0; w < nw; ++w) {
-                double all = 0;
-                for (int i = 0; i < 16; ++i) tot[i] += (double)h[(size_t)w * 16 + i];
-                for (int i = 0; i < 9; ++i) all += (double)h[(size_t)w * 16 + i];
-                mx = all > mx ? all : mx;
-            }
-            static const char* nm[9] = {"set-up", "stage+d_hi", "bloom", "classify", "score listed", "work list+advance", "finish", "skipped items", "idle tail"};
-            double all = 0;
-            for (int i = 0; i < 9; ++i) all += tot[i];
-            fprintf(stderr, "[bm25 wave walk] %d waves, %.0f cycles per wave (max %.0f):", nw, all / nw, mx);
-            for (int i = 0; i < 9; ++i) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * tot[i] / all);
-            fprintf(stderr, " | items %.0f passes %.0f cuts %.0f batches %.0f postings %.0f listed %.0f\n", tot[10], tot[11], tot[12], tot[13], tot[14], tot[15]);
-        }
-#endif
+                           id_base, max_terms, k, doc_coll, query_coll, L.ctl, L.q_nt, L.q_S, L.q_SA, L.q_pmask, L.q_terms,
+                           L.items, L.ipos, L.wrec, L.wterm, L.theta, L.slice_s, L.slice_id, L.slice_cnt, out_scores, out_ids, out_counts
+                           BM_STAMPS_ONLY(, L.stamps));
+        BM_STAMPS_ONLY(bm_stamps_report_waves(L, st, wgrid_w * WW_WAVES));
     } else if (dslot) {
         THR_BM25_LAUNCH_SHAPE(2);
         THR_BM25_LAUNCH_SHAPE(1);
@@ -2667,77 +2618,21 @@ extern "C" int thr_bm25_topk(const int64_t* rowptr, const int32_t* post_doc, con
     if (dslot) {
         // stage B: doc-window sweeps, skipped where stage A's threshold rules them out
         if ((rc = launch_status())) return rc;
-        hipLaunchKernelGGL(bm25_sweep_filter_kernel, dim3(1), dim3(FILTER_THREADS), 0, st, ctl, n_queries, q_S,
-                           q_SA, q_item0, q_dub, theta, slice_cnt, sweep_items);
-        int wgrid = bm_num_cus() * 2;
+        hipLaunchKernelGGL(bm25_sweep_filter_kernel, dim3(1), dim3(FILTER_THREADS), 0, st, L.ctl, n_queries, L.q_S,
+                           L.q_SA, L.q_item0, L.q_dub, L.theta, L.slice_cnt, L.sweep_items);
+        int wgrid = num_cus() * 2;
         if (wgrid > L.cap) wgrid = L.cap;
-#ifdef BM_STAMPS
-#define BW_STAMP_ARG , (unsigned long long*)(ws + L.off_stamps) + (size_t)4096 * (BM_NSTAMP + 1)
-#else
-#define BW_STAMP_ARG
-#endif
         hipLaunchKernelGGL((bm25_window_kernel<512, 8192, 1024>), dim3(wgrid), dim3(512), 0, st, rowptr, post_doc,
                            doclen, idf, dslot, dense_imp, dense_tf, dense_stride, avgdl, k1, b, n_docs, id_base,
-                           max_terms, k, doc_coll, query_coll, ctl, q_nt, q_S, q_SA, q_pmask, q_terms, items,
-                           sweep_items, ipos, theta, slice_s, slice_id, slice_cnt, out_scores, out_ids,
-                           out_counts BW_STAMP_ARG);
+                           max_terms, k, doc_coll, query_coll, L.ctl, L.q_nt, L.q_S, L.q_SA, L.q_pmask, L.q_terms, L.items,
+                           L.sweep_items, L.ipos, L.theta, L.slice_s, L.slice_id, L.slice_cnt, out_scores, out_ids,
+                           out_counts BM_STAMPS_ONLY(, bm_stamps_area(L, 1)));
         if ((rc = launch_status())) return rc;
     }
     THR_BM25_LAUNCH_SHAPE(0);
-#ifdef BM_STAMPS
-    {
-        static const char* names[BM_NSTAMP] = {"item set-up", "init", "quotas", "staging", "edges/prefix", "phase 2 (+ chunk reset)",
-                                               "bloom build", "singles listed", "singles scored", "work list / boot select", "compact/advance", "finish",
-                                               "mask / acc fill", "slot scan / middle search", "#acc passes", "#mask passes",
-                                               "#postings masked", "#survivors", "#phase2 rounds", ""};
-        (void)hipStreamSynchronize(st);
-        for (int pass = 0; pass < (dslot ? 3 : 1); ++pass) {
-            const int g_n = pass == 1 ? bm_num_cus() * 2 : grid;
-            std::vector<unsigned long long> h((size_t)g_n * (BM_NSTAMP + 1));
-            (void)hipMemcpy(h.data(), d_stamps + (size_t)pass * 4096 * (BM_NSTAMP + 1), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            double tot[BM_NSTAMP + 1] = {0};
-            for (int g = 0; g < g_n; ++g)
-                for (int i = 0; i <= BM_NSTAMP; ++i) tot[i] += (double)h[(size_t)g * (BM_NSTAMP + 1) + i];
-            double all = 0;
-            for (int i = 0; i < 14; ++i) all += tot[i];
-            fprintf(stderr, "[bm25 stamps%s] %d queries, %d workgroups, %.0f items, %.0f cycles per workgroup:", pass == 1 ? " window kernel (stage B)" : pass == 2 ? " stage A" : "", n_queries, g_n,
-                    tot[BM_NSTAMP], all / g_n);
-            for (int i = 0; i < 14; ++i)
-                if (names[i][0]) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * tot[i] / all);
-            for (int i = 14; i < 20; ++i) fprintf(stderr, " %s %.0f", names[i][0] ? names[i] : "#wmax|#singles", tot[i]);
-            fprintf(stderr, "\n");
-        }
-        if (dslot) {   // the sweep items one by one: when each started and ended (cycles since the first), its passes and survivors
-            int h_ctl[8];
-            (void)hipMemcpy(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost);
-            const int ns = h_ctl[5];
-            std::vector<unsigned long long> lg((size_t)4 * (ns > 0 ? ns : 1));
-            (void)hipMemcpy(lg.data(), d_stamps + (size_t)3 * 4096 * (BM_NSTAMP + 1), lg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int i = 0; i < ns; ++i) {
-                if (lg[4 * i + 1] < t0) t0 = lg[4 * i + 1];
-                if (lg[4 * i + 2] > t1) t1 = lg[4 * i + 2];
-            }
-            fprintf(stderr, "[bm25 sweep items] %d items, %llu cycles from the first start to the last end\n", ns, ns ? t1 - t0 : 0ull);
-            if (getenv("THR_BM25_ITEM_LOG")) {
-                const int ni = h_ctl[0];
-                std::vector<unsigned long long> wl((size_t)4 * (ni > 0 ? ni : 1));
-                (void)hipMemcpy(wl.data(), d_stamps + (size_t)3 * 4096 * (BM_NSTAMP + 1) + 4 * (size_t)L.cap, wl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-                for (int i = 0; i < ni; ++i)
-                    if (wl[4 * i + 2])
-                        fprintf(stderr, "[walk] %d q %llu slice %llu dp %llu nt %llu postings %llu cycles %llu passes %llu\n", i, wl[4 * i] >> 32,
-                                (wl[4 * i] >> 16) & 0xFFFF, (wl[4 * i] >> 8) & 0xFF, wl[4 * i] & 0xFF, wl[4 * i + 1], wl[4 * i + 2], wl[4 * i + 3]);
-            }
-            if (getenv("THR_BM25_ITEM_LOG"))
-                for (int i = 0; i < ns; ++i)
-                    fprintf(stderr, "[item] %d q %llu slice %llu np %llu walked %llu start %llu cycles %llu passes %llu survivors %llu\n", i,
-                            lg[4 * i] >> 32, (lg[4 * i] >> 16) & 0xFFFF, (lg[4 * i] >> 8) & 0xFF, lg[4 * i] & 0xFF, lg[4 * i + 1] - t0,
-                            lg[4 * i + 2] - lg[4 * i + 1], lg[4 * i + 3] >> 32, lg[4 * i + 3] & 0xFFFFFFFFull);
-        }
-    }
-#endif
+    BM_STAMPS_ONLY(bm_stamps_report(L, st, n_queries, grid, dslot != nullptr));
     if ((rc = launch_status())) return rc;
-    hipLaunchKernelGGL(bm25_merge_kernel, dim3(n_queries), dim3(BMM_THREADS), 0, st, q_S, q_item0,
-                       slice_s, slice_id, slice_cnt, k, out_scores, out_ids, out_counts);
+    hipLaunchKernelGGL(bm25_merge_kernel, dim3(n_queries), dim3(BMM_THREADS), 0, st, L.q_S, L.q_item0,
+                       L.slice_s, L.slice_id, L.slice_cnt, k, out_scores, out_ids, out_counts);
     return launch_status();
 }

@@ -99,28 +99,23 @@ static int key_bits(int64_t n_vocab) {
 }
 static LbLayout lb_layout(int64_t n_pairs, int64_t n_vocab) {
     LbLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+    Arena A;
     const size_t n = (size_t)n_pairs;
-    L.off_keys = take(sizeof(uint64_t) * n);
-    L.off_vals = take(sizeof(int32_t) * n);
-    L.off_skeys = take(sizeof(uint64_t) * n);
-    L.off_svals = take(sizeof(int32_t) * n);
-    L.off_ukeys = take(sizeof(uint64_t) * n);
-    L.off_sums = take(sizeof(int32_t) * n);
-    L.off_count = take(sizeof(int64_t) * 2);
+    L.off_keys = A.take(sizeof(uint64_t) * n);
+    L.off_vals = A.take(sizeof(int32_t) * n);
+    L.off_skeys = A.take(sizeof(uint64_t) * n);
+    L.off_svals = A.take(sizeof(int32_t) * n);
+    L.off_ukeys = A.take(sizeof(uint64_t) * n);
+    L.off_sums = A.take(sizeof(int32_t) * n);
+    L.off_count = A.take(sizeof(int64_t) * 2);
     size_t t_sort = 0, t_red = 0;
     (void)rocprim::radix_sort_pairs((void*)nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                     (const int32_t*)nullptr, (int32_t*)nullptr, n, 0u, (unsigned)key_bits(n_vocab));
     (void)rocprim::reduce_by_key((void*)nullptr, t_red, (const uint64_t*)nullptr, (const int32_t*)nullptr, n,
                                  (uint64_t*)nullptr, (int32_t*)nullptr, (int64_t*)nullptr);
     L.tmp_bytes = t_sort > t_red ? t_sort : t_red;
-    L.off_tmp = take(L.tmp_bytes);
-    L.total = off;
+    L.off_tmp = A.take(L.tmp_bytes);
+    L.total = A.total;
     return L;
 }
 

@@ -7,7 +7,7 @@
 // HNSW index inside PostgreSQL; this is the exact scan that index approximates.
 //
 // Pipeline per batch of queries (all kernels on one stream, no host sync):
-//   K0 pack_queries_f16         (default scan) queries -> fragment-major f16 register image
+//   K0 pack_queries_f16         [dense_scan_f16q.hip] (default scan) queries -> fragment-major f16 register image
 //   K1 scan<MODE_ALL>           score a strided SAMPLE of row groups for every query tile
 //   K2 kth_select               tau[q] ~ the ks-th largest sample score: about `aim` rows of
 //                               the corpus will pass it
@@ -15,7 +15,9 @@
 //                               emit (score, row) >= tau[q].  Default: dense_scan_f16qs (f16
 //                               MFMA over the normalised f16 copy, queries in registers);
 //                               dense_scan_f16 / dense_scan_mfma2 (dense_scan_mfma at dim 1024)
-//                               are the other flavours
+//                               are the other flavours [dense_scan_f16q.hip, dense_scan_f16.hip,
+//                               dense_scan_mfma.hip: a unit per flavour, called through the
+//                               launch functions of dense_common.hpp]
 //   K4a select_band             per query: the band of candidates that can still reach the
 //                               top-k -> a shortlist of rows
 //   K4b rescore_rank            shortlist re-scored in float64 with sequential accumulation
@@ -25,49 +27,8 @@
 // Algorithmic HBM bytes of K3 = n_docs * dim * 4 per tile pass.
 #include <stdlib.h>
 
-#include "thr_common.hpp"
+#include "dense_common.hpp"
 
-namespace thr {
-
-constexpr int CHUNK = 256;                 // floats per wave-wide float4 load (1 KiB)
-constexpr int MODE_ALL = 0, MODE_FILTER = 1;
-constexpr int CAND_CAP = 16384;            // candidates kept per query between K3 and K4
-constexpr int SAMPLE_MAX = 1 << 20;        // upper bound of the sample (rows) for the tau estimate
-constexpr int WBUF = 256;                  // per-wave LDS staging slots for passing rows
-constexpr int ROW_BITS = 27;               // tile-list entries pack (query-in-tile << 27 | row)
-constexpr uint32_t ROW_MASK = (1u << ROW_BITS) - 1;
-constexpr int ROW_BITS_F16 = 25;           // f16 shortlist scans: up to 96 queries per tile -> 7 bits
-
-struct Cand {
-    float score;
-    uint32_t doc;
-};
-
-}  // namespace thr
-// ---------------------------------------------------------------------------
-// Block -> (row slice, query tile) for the MFMA scans.
-// Every query tile streams the same rows, so the launch is laid out for the 8 private L2s:
-// workgroups are dealt round-robin over the XCDs (b and b+8 share one), and a 1-D grid of
-// 8 * m * n_qtiles blocks is decoded so that the blocks resident together on one XCD are the
-// n_qtiles query tiles of the SAME row slice.  They walk identical addresses in step: the
-// first one to ask for a line pulls it from HBM, the others hit it in that XCD's L2.
-// Placement is a speed matter only: any dispatch order gives the same result.
-// ---------------------------------------------------------------------------
-struct ScanSlot {
-    int qtile, slice, nslices;
-};
-__device__ __forceinline__ ScanSlot scan_slot(int n_qtiles) {
-    ScanSlot s;
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3;
-    s.qtile = j % n_qtiles;
-    s.slice = xcd + 8 * (j / n_qtiles);
-    s.nslices = gridDim.x / n_qtiles;
-    return s;
-}
-
-#include "dense_scan_mfma.hpp"
-#include "dense_scan_f16.hpp"
-#include "dense_scan_f16q.hpp"
 namespace thr {
 
 // K3b: split a tile's mixed candidate list into the per-query lists K4 reads.  Each block
@@ -1223,19 +1184,12 @@ struct DensePlan {
 };
 
 constexpr int KIND_F32 = 0, KIND_F16 = 1;
-// in-flight-rounding f16 scan (dense_scan_f16): query sub-tiles of 32 per pass -- 2 (64 queries,
-// 96 KiB of LDS at dim 768) when the tile fits next to the transpose tiles, else 1
-static size_t f16_lds_bytes(int dim, int nq) {
-    return sizeof(_Float16) * 32 * nq * (size_t)dim +
-           (sizeof(Cand) * WBUF + sizeof(float4) * MF2_STAGE_F4) * H_WAVES;
-}
-static int f16_pick_nq(int dim) { return f16_lds_bytes(dim, 2) <= 160 * 1024 ? 2 : 1; }
 
 // The scan over the float16 copy (queries in registers, rows through LDS): dense_scan_f16qs
 // (staggered 8-wave block) where 8 x 32 queries' B operands fit the registers of two waves per
 // SIMD, else dense_scan_f16q (4-wave blocks); THR_DENSE_F16=q forces the latter (it has the
 // stamped diagnostic build).  Read once.
-static bool qreg_staggered(int dim) {
+bool qreg_staggered(int dim) {
     static int forced_q = -1;
     if (forced_q < 0) {
         const char* e = getenv("THR_DENSE_F16");
@@ -1243,11 +1197,11 @@ static bool qreg_staggered(int dim) {
     }
     return !forced_q && dim <= 768;
 }
-static int qreg_waves(int dim) { return qreg_staggered(dim) ? 8 : 4; }   // qreg_qw queries per wave
+int qreg_waves(int dim) { return qreg_staggered(dim) ? 8 : 4; }   // qreg_qw queries per wave
 // MFMA shape of the staggered scan and therefore of the copy / query images: 16 (16x16x32, the
 // default: 2.50 ms against 2.67 ms per 2048 x 1M x 768 launch) or 32 (32x32x16,
 // THR_DENSE_MFMA=32).  Read once: the copy's layout depends on it.
-static int qreg_shape(int dim) {
+int qreg_shape(int dim) {
     static int v = 0;
     if (!v) {
         const char* e = getenv("THR_DENSE_MFMA");
@@ -1258,7 +1212,7 @@ static int qreg_shape(int dim) {
 }
 // queries per wave: 32, or 48 at dim 1024 with the 16x16x32 shape (dense_scan_f16q<1024, .., 48>:
 // three 16-query blocks per wave, 192 queries per CU; THR_DENSE_QW=32 keeps the 32-query kernel for A/B)
-static int qreg_qw(int dim) {
+int qreg_qw(int dim) {
     static int forced32 = -1;
     if (forced32 < 0) {
         const char* e = getenv("THR_DENSE_QW");
@@ -1270,7 +1224,7 @@ constexpr int QREG_MAX_SEG = 1024;
 // The register-resident scans address a lane's candidate segment with a 32-bit byte offset from
 // the start of the candidate area ((q * CAND_CAP + segment start) * sizeof(Cand)): a batch may
 // hold as many (padded) queries as keep every offset below 2^32.
-static int qreg_max_queries(int dim) {
+int qreg_max_queries(int dim) {
     const int qt = qreg_qw(dim) * qreg_waves(dim);
     const int64_t m = (int64_t)UINT32_MAX / ((int64_t)CAND_CAP * (int64_t)sizeof(Cand));
     return (int)(m / qt * qt);
@@ -1318,25 +1272,20 @@ static DensePlan make_plan(int64_t n_docs, int n_queries, int kprime, int kind =
     p.sample_groups = p.sampled ? sg : 0;
     p.sample_docs = p.sample_groups * p.unit;
     p.groups = groups;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    p.off_tau = take(sizeof(float) * p.qpad);
-    p.off_qerr = take(sizeof(float) * p.qpad);
+    Arena A;
+    p.off_tau = A.take(sizeof(float) * p.qpad);
+    p.off_qerr = A.take(sizeof(float) * p.qpad);
     p.tile_cap = p.qreg ? 1 : p.qtile * (CAND_CAP / 2);   // (no tile lists in the qreg scan)
     // (off_cnt and off_tcnt are zeroed by one memset; the qreg scan keeps one count per segment)
-    p.off_cnt = take(sizeof(int) * p.qpad * (p.qreg ? QREG_MAX_SEG : 1));
-    p.off_tcnt = take(sizeof(int) * p.ntiles);
-    p.off_cand = take(sizeof(Cand) * (size_t)p.qpad * CAND_CAP);
-    p.off_tlist = take(sizeof(Cand) * (size_t)p.ntiles * p.tile_cap);
-    p.off_sample = take(sizeof(float) * (size_t)p.qpad * (size_t)p.sample_docs);
-    p.off_qfrag = take(p.qreg ? sizeof(_Float16) * (size_t)p.qpad * (size_t)dim : 0);
-    p.off_selrows = take(sizeof(int32_t) * (size_t)p.qpad * SEL_BIG_BAND);   // K4a -> K4b shortlists
-    p.off_selmeta = take(sizeof(int32_t) * 4 * (size_t)p.qpad);
-    p.total = off;
+    p.off_cnt = A.take(sizeof(int) * p.qpad * (p.qreg ? QREG_MAX_SEG : 1));
+    p.off_tcnt = A.take(sizeof(int) * p.ntiles);
+    p.off_cand = A.take(sizeof(Cand) * (size_t)p.qpad * CAND_CAP);
+    p.off_tlist = A.take(sizeof(Cand) * (size_t)p.ntiles * p.tile_cap);
+    p.off_sample = A.take(sizeof(float) * (size_t)p.qpad * (size_t)p.sample_docs);
+    p.off_qfrag = A.take(p.qreg ? sizeof(_Float16) * (size_t)p.qpad * (size_t)dim : 0);
+    p.off_selrows = A.take(sizeof(int32_t) * (size_t)p.qpad * SEL_BIG_BAND);   // K4a -> K4b shortlists
+    p.off_selmeta = A.take(sizeof(int32_t) * 4 * (size_t)p.qpad);
+    p.total = A.total;
     return p;
 }
 
@@ -1365,23 +1314,11 @@ __global__ __launch_bounds__(256) void dense_floor_kernel(const float* __restric
     }
 }
 
-static int g_num_cus = 0;
-static int num_cus() {
-    if (!g_num_cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            g_num_cus = prop.multiProcessorCount;
-        if (g_num_cus <= 0) g_num_cus = 256;
-    }
-    return g_num_cus;
-}
-
 // Grid of an MFMA scan (see scan_slot): 1-D, 8 * m * n_qtiles blocks, one block per CU.  m is
 // chosen for the fullest last round of blocks, the smallest such m first (fewer, longer row
 // slices; at 32 query tiles m = 1 and the whole launch is a single round).
-static dim3 scan_grid(int ntiles, int64_t n_row_tiles, int waves, bool* shared_rows,
-                      int blocks_per_cu = 1, int m_cap = 64) {
+dim3 scan_grid(int ntiles, int64_t n_row_tiles, int waves, bool* shared_rows, int blocks_per_cu,
+               int m_cap) {
     const int cus = num_cus() * blocks_per_cu;   // block slots
     int64_t m_max = n_row_tiles / (8 * (int64_t)waves);  // every wave gets at least one row tile
     if (m_max < 1) m_max = 1;
@@ -1403,177 +1340,7 @@ static dim3 scan_grid(int ntiles, int64_t n_row_tiles, int waves, bool* shared_r
 
 // row loads: non-temporal when no other query tile will ask for the same lines, plain when the
 // query tiles of a slice share them through L2
-static bool scan_nt(bool shared_rows) { return !shared_rows; }
-
-template <int MODE>
-static int launch_scan_mfma(int dim, const float* docs, const float* inv_norm, int64_t n_docs,
-                            const float* queries, int n_queries, int ntiles, int64_t n_row_tiles,
-                            int64_t tile_stride, const float* tau, int* tile_cnt, Cand* tile_list,
-                            int tile_cap, float* sample, int64_t sample_ld, hipStream_t st,
-                            const int32_t* doc_coll = nullptr, const int32_t* query_coll = nullptr) {
-    const size_t lds1 = sizeof(float) * MF_QT * (size_t)dim + sizeof(Cand) * MF_WAVES * WBUF;
-    auto lds2_for = [&](int nw) {
-        return sizeof(float) * MF_QT * (size_t)dim + (sizeof(Cand) * WBUF + sizeof(float4) * MF2_STAGE_F4) * nw;
-    };
-    // v2 adds a 4 KiB transpose tile per wave on top of the query tile: 8 waves fit up to dim
-    // 768.  At dim 1024 only 4 waves (one per SIMD) would fit, and that measured slower than
-    // the fragment-load variant with 8 waves (4.30 vs 4.93 TB/s), which therefore runs there.
-    int nw = 0;
-    if (dim % 128 == 0 && dim >= 256)
-        nw = lds2_for(8) <= 160 * 1024 ? 8 : 0;
-    const bool v2 = nw != 0;
-    const size_t lds = v2 ? lds2_for(nw) : lds1;
-    const int waves = v2 ? nw : MF_WAVES;
-    bool shared_rows = false;
-    const dim3 grid = scan_grid(ntiles, n_row_tiles, waves, &shared_rows);
-    const bool nt = scan_nt(shared_rows);
-#define THR_MF_LAUNCH(KERN, THREADS)                                                              \
-    {                                                                                             \
-        auto kern = KERN;                                                                         \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(THREADS), lds, st, docs, inv_norm, n_docs, queries,   \
-                           n_queries, n_row_tiles, tile_stride, tau, tile_cnt, tile_list,         \
-                           tile_cap, sample, sample_ld, doc_coll, query_coll);                    \
-    }
-#define THR_MF_CASE(D8)                                                                           \
-    case D8:                                                                                      \
-        if (!v2) THR_MF_LAUNCH((dense_scan_mfma<D8, MODE>), MF_THREADS)                           \
-        else if (nt) THR_MF_LAUNCH((dense_scan_mfma2<D8, MODE, true, 8>), 512)                    \
-        else THR_MF_LAUNCH((dense_scan_mfma2<D8, MODE, false, 8>), 512)                           \
-        break;
-    switch (dim / 8) {
-        THR_MF_CASE(32)
-        THR_MF_CASE(64)
-        THR_MF_CASE(96)
-        THR_MF_CASE(128)
-        default:
-            return THR_ERR_UNSUPPORTED;
-    }
-#undef THR_MF_CASE
-#undef THR_MF_LAUNCH
-    return launch_status();
-}
-
-// the in-flight-rounding f16 scan: streams the float32 rows and rounds them in registers
-template <int MODE>
-static int launch_scan_f16(int dim, int nq, const float* rows32, const float* inv_norm,
-                           int64_t n_docs, const float* queries, int n_queries, int ntiles,
-                           int64_t n_row_tiles, int64_t tile_stride, const float* tau, int* tile_cnt,
-                           Cand* tile_list, int tile_cap, float* sample, int64_t sample_ld,
-                           hipStream_t st, const int32_t* doc_coll = nullptr,
-                           const int32_t* query_coll = nullptr) {
-    const size_t lds = f16_lds_bytes(dim, nq);
-    THR_RETURN_IF(lds > 160 * 1024, THR_ERR_UNSUPPORTED);
-    bool shared_rows = false;
-    const dim3 grid = scan_grid(ntiles, n_row_tiles, H_WAVES, &shared_rows);
-    const bool nt = scan_nt(shared_rows);
-#define THR_H_LAUNCH(KERN)                                                                        \
-    {                                                                                             \
-        auto kern = KERN;                                                                         \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(H_THREADS), lds, st, rows32, inv_norm, n_docs,        \
-                           queries, n_queries, n_row_tiles, tile_stride, tau, tile_cnt, tile_list, \
-                           tile_cap, sample, sample_ld, doc_coll, query_coll);                    \
-    }
-#define THR_H_INLINE(DIM, NQV)                                                                    \
-    {                                                                                             \
-        if (nt) THR_H_LAUNCH((dense_scan_f16<DIM, MODE, true, NQV>))                              \
-        else THR_H_LAUNCH((dense_scan_f16<DIM, MODE, false, NQV>))                                \
-    }
-    switch (dim * 10 + nq) {
-        case 5122: THR_H_INLINE(512, 2) break;
-        case 7682: THR_H_INLINE(768, 2) break;
-        case 10241: THR_H_INLINE(1024, 1) break;
-        default: return THR_ERR_UNSUPPORTED;
-    }
-#undef THR_H_INLINE
-#undef THR_H_LAUNCH
-    return launch_status();
-}
-
-template <int MODE, bool PROF = false>
-static int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int n_qtiles,
-                            int64_t n_row_tiles, int64_t tile_stride, const float* tau, int* seg_cnt,
-                            Cand* cand, float* sample, int64_t sample_ld, hipStream_t st,
-                            int* nseg_out = nullptr, const int32_t* doc_coll = nullptr,
-                            const int32_t* query_coll = nullptr, int n_queries = 1 << 30,
-                            unsigned long long* stamps = nullptr, int* n_blocks = nullptr) {
-    bool shared_rows = false;
-    const bool stag = qreg_staggered(dim);
-    // a lane's candidate segment is (row slice, row half): at most 256 slices (512 segments, two
-    // per thread of select_rescore) -- enough for one block per CU when the batch is a single
-    // workgroup tile of queries
-    const dim3 grid = scan_grid(n_qtiles, n_row_tiles, 1, &shared_rows, (!stag && dim <= 768) ? 2 : 1, 32);
-    const int shape = qreg_shape(dim);
-    const int nseg = (shape == 16 ? 4 : 2) * (int)(grid.x / n_qtiles);
-    if (nseg_out) *nseg_out = nseg;
-    if (n_blocks) *n_blocks = (int)grid.x;
-    if (PROF && !stamps) return THR_OK;   // size query
-#define THR_QS_LAUNCH(DIM, SHAPE)                                                                 \
-    {                                                                                             \
-        auto kern = dense_scan_f16qs<DIM, MODE, SHAPE>;                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                           QStag<DIM>::LDS_BYTES);                                \
-        if (e != hipSuccess) return (int)e;                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(QS_NW * 64), QStag<DIM>::LDS_BYTES, st,               \
-                           (const f32x4*)rows16, (const f32x4*)qfrag, n_qtiles, n_row_tiles,      \
-                           tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg, sample, sample_ld,   \
-                           doc_coll, query_coll, n_queries);                                      \
-    }
-    if (stag) {
-        if (dim == 512 && shape == 32) THR_QS_LAUNCH(512, 32)
-        else if (dim == 512) THR_QS_LAUNCH(512, 16)
-        else if (shape == 32) THR_QS_LAUNCH(768, 32)
-        else THR_QS_LAUNCH(768, 16)
-        return launch_status();
-    }
-#undef THR_QS_LAUNCH
-#define THR_Q_LAUNCH(DIM, SHAPE)                                                                  \
-    {                                                                                             \
-        auto kern = dense_scan_f16q<DIM, MODE, PROF, SHAPE>;                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                   \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                           QScan<DIM>::LDS_BYTES);                                \
-        if (e != hipSuccess) return (int)e;                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(Q_NW * 64), QScan<DIM>::LDS_BYTES, st,                \
-                           (const f32x4*)rows16, (const f32x4*)qfrag, n_qtiles, n_row_tiles,      \
-                           tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg, sample, sample_ld,   \
-                           doc_coll, query_coll, n_queries, stamps);                              \
-    }
-    switch (dim) {
-        case 512: if (shape == 16) THR_Q_LAUNCH(512, 16) else THR_Q_LAUNCH(512, 32) break;
-        case 768: if (shape == 16) THR_Q_LAUNCH(768, 16) else THR_Q_LAUNCH(768, 32) break;
-        case 1024:
-            if (shape == 16 && qreg_qw(dim) == 48) THR_Q_LAUNCH(1024, 48)
-            else if (shape == 16) THR_Q_LAUNCH(1024, 16)
-            else THR_Q_LAUNCH(1024, 32)
-            break;
-        default: return THR_ERR_UNSUPPORTED;
-    }
-#undef THR_Q_LAUNCH
-    return launch_status();
-}
-
-static int launch_pack_queries(int dim, const float* queries, int n_queries, int qpad,
-                               _Float16* qfrag, float* qerr, hipStream_t st) {
-    const dim3 grid((unsigned)(qpad / 32));
-    const bool s16 = qreg_shape(dim) == 16;
-#define THR_PACK(DIM, SHAPE) \
-    hipLaunchKernelGGL((pack_queries_f16<DIM, SHAPE>), grid, dim3(256), 0, st, queries, n_queries, (f32x4*)qfrag, qerr)
-    switch (dim) {
-        case 512: if (s16) THR_PACK(512, 16); else THR_PACK(512, 32); break;
-        case 768: if (s16) THR_PACK(768, 16); else THR_PACK(768, 32); break;
-        case 1024: if (s16) THR_PACK(1024, 16); else THR_PACK(1024, 32); break;
-        default: return THR_ERR_UNSUPPORTED;
-    }
-#undef THR_PACK
-    return launch_status();
-}
+bool scan_nt(bool shared_rows) { return !shared_rows; }
 
 // fp32 error bound of the MFMA scan, relative to ||q||*||d||, in units of 2^-24: a dim-long fma chain
 static double scan_eps(int dim) {
@@ -1759,19 +1526,8 @@ extern "C" int thr_dense_quantize_f16(const float* docs, int64_t n_docs, int dim
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(max_rel_err, 0, sizeof(float), st);
     if (e != hipSuccess) return (int)e;
-    if (docs16) {
-        // normalised rows, NaN for rows without an embedding and for the padding of the last tile
-        THR_RETURN_IF(dim % 16 != 0, THR_ERR_UNSUPPORTED);
-        const int64_t n_pad = (n_docs + 31) / 32 * 32;
-        hipLaunchKernelGGL(quantize_f16_norm, dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, st,
-                           docs, n_docs, dim, qreg_shape(dim), reinterpret_cast<_Float16*>(docs16),
-                           reinterpret_cast<unsigned int*>(max_rel_err));
-        return launch_status();
-    }
-    // measure only: the in-flight-rounding scan rounds the rows as they are
-    hipLaunchKernelGGL(measure_f16_error, dim3((unsigned)((n_docs + 3) / 4)), dim3(256), 0, st, docs,
-                       n_docs, dim, reinterpret_cast<unsigned int*>(max_rel_err));
-    return launch_status();
+    return launch_quantize_f16(docs, n_docs, dim, reinterpret_cast<_Float16*>(docs16),
+                               reinterpret_cast<unsigned int*>(max_rel_err), st);
 }
 
 extern "C" int thr_dense_topk_f16(const float* docs, const uint16_t* docs16, double doc_rel_err,

@@ -16,22 +16,12 @@
 // 64 dims and ONE v_mfma_f32_32x32x16_f16 per 16-byte fragment pair; 64 queries per pass (96 KiB
 // of LDS as f16) at dim <= 768, 32 at dim 1024.
 #pragma once
+#include "dense_common.hpp"
 
 namespace thr {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-constexpr int H_WAVES = 8;
 constexpr int H_THREADS = H_WAVES * WAVE;
 
-// round 8 floats to nearest-even float16 (same rounding as quantize_f16, whose error bound covers
-// both flavours)
-__device__ __forceinline__ f32x4 pack_f16x8(f32x4 lo, f32x4 hi) {
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    const half4 a = __builtin_convertvector(lo, half4), b = __builtin_convertvector(hi, half4);
-    half8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(f32x4, v);
-}
 
 // NQ = query sub-tiles of 32 (1 or 2).  A stage (64 dims of 32 rows) is 8 KiB of float32: each
 // lane loads float4 #c and #(8+c) of its row's 16 (two fully coalesced 128-byte row segments

@@ -42,6 +42,7 @@
 // atomics also drained the DMA queue).  select_band reads the segments in place
 // (cand_cnt[q * nseg + s] entries each).
 #pragma once
+#include "dense_common.hpp"
 
 namespace thr {
 

@@ -19,33 +19,13 @@
 // so that the 32 lanes of a ds_read_b128 (one query row each, stride 3 KiB) hit
 // distinct bank groups.
 #pragma once
-#include <type_traits>
+#include "dense_common.hpp"
 
 namespace thr {
 
-// compile-time loop: the body sees its index as a constant expression, so register arrays
-// indexed with it stay in registers (a "#pragma unroll" the compiler declines would demote
-// them to scratch)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int MF_THREADS = 512;
 constexpr int MF_WAVES = MF_THREADS / WAVE;
-constexpr int MF_ROWS = 32;   // rows per wave tile
-constexpr int MF_QT = 32;     // queries per tile pass
 constexpr int MF_NPF = 8;     // float4 row chunks kept in flight per lane (8 KiB per wave)
-
-// swizzled float4 index of 16-byte chunk `cidx` of query row q (row length D8*2 chunks)
-__device__ __forceinline__ int mf_qslot(int q, int cidx, int chunks_per_row) {
-    return q * chunks_per_row + ((cidx & ~15) | ((cidx ^ q) & 15));
-}
 
 template <int D8, int MODE>  // D8 = dim / 8
 __global__ __launch_bounds__(MF_THREADS) void dense_scan_mfma(
@@ -204,14 +184,7 @@ __global__ __launch_bounds__(MF_THREADS) void dense_scan_mfma(
 // full MFMA quad (256 cycles) before it is used.  Stages run in groups of 4 (= ring depth)
 // so every register-array index is a constant.
 // ---------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: plain SSA loads/stores
 constexpr int MF2_AHEAD = 4;               // ring depth: stages (4 KiB each) in flight per wave
-constexpr int MF2_STAGE_F4 = MF_ROWS * 8;  // float4 slots per stage tile (32 rows x 8 chunks)
-
-// float4 slot of (row, chunk) inside a stage tile: chunk ^ ((row >> 1) & 7)
-__device__ __forceinline__ int mf2_slot(int row, int chunk) {
-    return row * 8 + (chunk ^ ((row >> 1) & 7));
-}
 
 template <int D8, int MODE, bool nt_loads, int NW>  // NW = waves per workgroup
 __global__ __launch_bounds__(NW * WAVE) void dense_scan_mfma2(

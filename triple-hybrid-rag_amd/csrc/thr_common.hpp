@@ -23,6 +23,45 @@ inline int launch_status() {
     return e == hipSuccess ? THR_OK : (int)e;
 }
 
+// CUs of the current device (256 when it cannot be asked)
+inline int num_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+            cus = prop.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
+// A workspace handed out in 256-byte-aligned pieces, in call order.  Without a base it only sizes
+// (the *_workspace_bytes entry points): the typed take() then returns null.
+struct Arena {
+    char* base = nullptr;
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t o = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+    template <typename T>
+    T* take(size_t n) {
+        const size_t o = take(sizeof(T) * n);
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+};
+
+// Launch of a kernel with dynamic LDS above the 64 KiB default: the attribute, the launch, the status.
+template <typename... P, typename... A>
+inline int launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return launch_status();
+}
+
 // ---- order-preserving float <-> uint keys (larger float => larger key) ----
 __device__ __forceinline__ uint32_t fkey(float f) {
     uint32_t u = __float_as_uint(f);
