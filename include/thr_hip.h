@@ -266,6 +266,30 @@ int thr_csr_append(const int64_t *rowptr_a, int64_t rows_a, int64_t nnz_a, const
                    int64_t *rowptr_out, void *out0, void *out1 /* or NULL */,
                    int64_t out_capacity, thr_stream_t stream);
 
+/* f2  delete: order-preserving removal of entries from a CSR, with renumbering.  The reference's
+ * store deletes rows: every RAG 2.0 table hangs on its parent with ON DELETE CASCADE
+ * (database/migrations/20260114_rag2_schema.sql:65-66, 106-108, 187, 217-218), its end-to-end tests
+ * clear a tenant with table("rag_child_chunks").delete().eq(...) (tests/test_rag2_e2e.py:276-293)
+ * and the RAG 1.0 ingestor has delete_by_source (src/voice_agent/ingestion/kb_ingest.py:492-510).
+ *   ``ids`` [nnz] is the payload that decides liveness (post_doc; men_chunk with id_base = the
+ *   shard's doc_base), ``pay`` [nnz] an opaque 4-byte companion (post_tf int32, men_conf float32)
+ *   or NULL (then pay_out is NULL too); ``remap`` [n_ids]: new id of old id i, -1 = deleted,
+ *   ascending over the survivors.  Entry p is kept iff 0 <= ids[p] - id_base < n_ids and
+ *   remap[ids[p] - id_base] >= 0, and is written as remap[...] + id_base.  Kept entries keep their
+ *   relative order; rowptr_out [rows + 1]: rowptr_out[t] = kept entries before position rowptr[t]
+ *   (rows do not change: a row that empties keeps its id).  *nnz_out (device memory) = the number
+ *   of kept entries; of ids_out / pay_out (buffers of their own, room for out_capacity elements)
+ *   the first min(*nnz_out, out_capacity) are written, nothing behind them.
+ * Stream-ordered, three launches, no workgroup waits for another, no host round trip inside;
+ * ``workspace`` >= thr_csr_compact_workspace_bytes().  The kernels check every source index
+ * against nnz, every remap index against n_ids and every destination against out_capacity. */
+size_t thr_csr_compact_workspace_bytes(int64_t rows, int64_t nnz);
+int thr_csr_compact(const int64_t *rowptr, int64_t rows, int64_t nnz, const int32_t *ids,
+                    const void *pay /* or NULL */, const int32_t *remap, int64_t n_ids,
+                    int64_t id_base, int64_t *rowptr_out, int32_t *ids_out,
+                    void *pay_out /* or NULL */, int64_t out_capacity, int64_t *nnz_out,
+                    void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
 /* a3  lexical channel: Okapi BM25 (k1, b) top-k over a CSR inverted index,
  * OR semantics, float64 accumulation in query-term order.
  * Stands where SQL rag2_lexical_search (ts_rank_cd ... ORDER BY rank DESC

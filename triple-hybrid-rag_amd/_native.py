@@ -68,6 +68,8 @@ _SIGNATURES = {
     "thr_lexical_build_workspace_bytes": (_sz, [_i64, _i64]),
     "thr_lexical_build": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_csr_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "thr_csr_compact_workspace_bytes": (_sz, [_i64, _i64]),
+    "thr_csr_compact": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "thr_bm25_block_count": (_sz, [_i64]),
     "thr_bm25_bounds": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "thr_bm25_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -311,6 +313,23 @@ def dense_quantize_f16(docs: torch.Tensor, keep_copy: bool = True):
     return d16, float(err.item())
 
 
+def dense_quantize_f16_into(docs: torch.Tensor, d16: Optional[torch.Tensor], err: torch.Tensor) -> None:
+    """thr_dense_quantize_f16 into buffers the caller holds: ``d16`` float16 with room for the
+    image of the rows (None: measure only), ``err`` a float32 [1] device slot for the max relative
+    row error.  Allocates nothing and reads nothing back (GpuIndex.delete_rows, phase 2)."""
+    p = _dev(docs, torch.float32, "docs", 2)
+    n, d = docs.shape
+    pe = _dev(err, torch.float32, "err", 1)
+    ph = None
+    if d16 is not None:
+        ph = _dev(d16, torch.float16, "d16", 2)
+        if d16.shape[1] != d or d16.numel() * 2 < int(load().thr_dense_f16_copy_bytes(n, d)):
+            raise NativeError("dense_quantize_f16_into: the float16 destination is too small")
+    if err.numel() != 1:
+        raise NativeError("dense_quantize_f16_into: err is one float32")
+    _check(load().thr_dense_quantize_f16(p, n, d, ph, pe, _stream()), "thr_dense_quantize_f16")
+
+
 def dense_f16_layout(dim: int) -> str:
     """Tag of the fragment-major layout thr_dense_quantize_f16 writes in this process: the
     register image of the MFMA shape the copy scan runs with (16x16x32, or 32x32x16 under the
@@ -533,6 +552,50 @@ def csr_append(rowptr_a, a0, a1, rowptr_b, b0, b1, out0=None, out1=None):
                                  _dev(out1, b1.dtype, "out1", 1) if nnz and b1 is not None else None,
                                  cap, _stream()), "thr_csr_append")
     return rowptr_out, out0, (out1 if b1 is not None else None), nnz
+
+
+def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out=None):
+    """Order-preserving removal of entries from a CSR, with renumbering (thr_csr_compact): entry p
+    is kept iff ``remap[ids[p] - id_base] >= 0`` (ids outside [id_base, id_base + len(remap)) are
+    dropped) and is written as ``remap[...] + id_base``.  ``rowptr`` int64 [rows + 1], ``ids`` int32
+    [nnz], ``pay`` a 4-byte tensor [nnz] or None, ``remap`` int32 [n_ids] (-1 = deleted, ascending over
+    the survivors).  ``ids_out`` / ``pay_out``: capacity-reserved 1-d destinations of the payloads'
+    dtypes with room for all nnz entries (the kept count is not known before the call; allocated
+    when None) -- only the kept entries are written.  One host read-back at the end (the kept
+    count).  -> (rowptr_out, ids_out, pay_out or None, nnz_kept)."""
+    # (shapes and dtypes first: they are refused on any device, before a pointer is taken)
+    rows, nnz = rowptr.shape[0] - 1, ids.shape[0]
+    if rows < 1:
+        raise NativeError("csr_compact: rowptr has no rows")
+    if id_base < 0:
+        raise NativeError("csr_compact: id_base is negative")
+    if pay is not None and (pay.dtype.itemsize != 4 or pay.dim() != 1 or pay.shape[0] != nnz):
+        raise NativeError("csr_compact: the payload is a 1-d array of 4-byte elements, one per id")
+    if pay is None and pay_out is not None:
+        raise NativeError("csr_compact: pay_out without a payload")
+    for out, like, name in ((ids_out, ids, "ids_out"), (pay_out, pay, "pay_out")):
+        if out is not None and (out.dtype != like.dtype or out.dim() != 1 or out.shape[0] < nnz):
+            raise NativeError(f"csr_compact: {name} is too small (room for every entry is needed) or of another dtype")
+    prp = _dev(rowptr, torch.int64, "rowptr", 1)
+    pid = _dev(ids, torch.int32, "ids", 1)
+    prm = _dev(remap, torch.int32, "remap", 1)
+    dev = ids.device
+    if ids_out is None:
+        ids_out = torch.empty(nnz, dtype=torch.int32, device=dev)
+    if pay_out is None and pay is not None:
+        pay_out = torch.empty(nnz, dtype=pay.dtype, device=dev)
+    rowptr_out = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+    kept = torch.zeros(1, dtype=torch.int64, device=dev)
+    need = int(load().thr_csr_compact_workspace_bytes(rows, nnz))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    cap = ids_out.shape[0] if pay is None else min(ids_out.shape[0], pay_out.shape[0])
+    _check(load().thr_csr_compact(prp, rows, nnz, pid if nnz else None,
+                                  _dev(pay, pay.dtype, "pay", 1) if nnz and pay is not None else None,
+                                  prm if remap.shape[0] else None, remap.shape[0], int(id_base),
+                                  rowptr_out.data_ptr(), _dev(ids_out, torch.int32, "ids_out", 1) if nnz else None,
+                                  _dev(pay_out, pay.dtype, "pay_out", 1) if nnz and pay is not None else None,
+                                  cap, kept.data_ptr(), ws.data_ptr(), need, _stream()), "thr_csr_compact")
+    return rowptr_out, ids_out, (pay_out if pay is not None else None), int(kept.item())
 
 
 # --------------------------------------------------------------------- a3

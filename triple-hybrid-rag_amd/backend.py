@@ -22,12 +22,25 @@ The ingest seam (src/voice_agent/rag2/ingest.py:361-470) is served too:
     client.table("rag_parent_chunks").insert(row | [rows]).execute().data
 
 An insert appends to the store AND to the live index (``GpuIndex.append_rows``): the next
-``retrieve()`` sees the chunk.  The reference's ingest never deletes; neither does this.
+``retrieve()`` sees the chunk.
+
+Deletes are served as the SQL store serves them (ON DELETE CASCADE from documents to parents to
+children, database/migrations/20260114_rag2_schema.sql:65-66, 106-108; the reference's own tests
+clear a tenant this way, tests/test_rag2_e2e.py:276-293):
+
+    client.table("rag_child_chunks").delete().eq("id" | "document_id" | "parent_id", v).execute().data
+    client.table("rag_child_chunks").delete().in_("id" | "document_id", vs).execute().data
+    client.table("rag_parent_chunks").delete().eq("id" | "document_id", v).execute().data   (+ their children)
+    client.table("rag_documents").delete().eq("id", d).execute().data      (+ its children and their parents)
+
+A delete removes the chunks from the live index (``GpuIndex.delete_rows``: the next ``retrieve()``
+no longer sees them) and from the store; an update is a delete followed by an insert.
 """
 from __future__ import annotations
 
 import collections.abc
 import re
+import weakref
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -117,6 +130,32 @@ class CorpusStore:
         self._hashes.update(h for h in hashes if h is not None)
         return range(n0, n0 + len(rows))
 
+    def delete(self, rows: Sequence[int]) -> List[Dict[str, Any]]:
+        """Remove the child-chunk rows with these row indices (any order, repeats allowed) -> the
+        deleted rows as ``child_row`` gives them, in row order.  Every column is compacted (the
+        survivors keep their order: row i becomes row i - #deleted below i, as
+        ``GpuIndex.delete_rows`` renumbers the index), the id lookup is rebuilt and the rows'
+        content hashes are forgotten, so the same content can be ingested again.  Parents, the
+        vocabulary and the entity names are not touched (term and entity ids never move)."""
+        n = len(self.child_ids)
+        gone = sorted({int(r) for r in rows})
+        if gone and (gone[0] < 0 or gone[-1] >= n):
+            raise ValueError(f"row index out of range 0 .. {n - 1}")
+        if not gone:
+            return []
+        out = [self.child_row(i) for i in gone]
+        dead = set(gone)
+        # (a loaded store keeps its columns as read-only blobs: they become lists here, as in append)
+        names = ["child_ids", "parent_ids", "document_ids", "texts", "pages", "modalities"]
+        names += [c for c in ("collections", "content_hashes") if getattr(self, c) is not None]
+        lost = {self.content_hashes[i] for i in gone} if self.content_hashes is not None else set()
+        for name in names:
+            col = getattr(self, name)
+            setattr(self, name, [col[i] for i in range(n) if i not in dead])
+        self._row_of = {cid: i for i, cid in enumerate(self.child_ids)}
+        self._hashes -= {h for h in lost if h is not None}
+        return out
+
     def row_index(self, child_id: str) -> Optional[int]:
         return self._row_of.get(child_id)
 
@@ -165,7 +204,7 @@ class LazyRows(collections.abc.Sequence):
     read an unfilled list storage behind the fetch (``json.dumps(rows.materialize())`` for C-level
     consumers that insist on a real list)."""
 
-    __slots__ = ("_fetch", "_rows", "_error")
+    __slots__ = ("_fetch", "_rows", "_error", "__weakref__")
 
     def __init__(self, fetch):
         self._fetch = fetch
@@ -214,10 +253,12 @@ class LazyRows(collections.abc.Sequence):
 
 
 class _TableQuery:
-    def __init__(self, fetch, by_hash=None, insert=None, org_id=None):
+    def __init__(self, fetch, by_hash=None, insert=None, org_id=None, delete=None):
         self._fetch = fetch
         self._by_hash = by_hash       # content_hash lookup (rag_child_chunks only)
         self._insert = insert         # row writer (the two chunk tables)
+        self._delete = delete         # row remover: [(column, values), ...] -> the deleted rows
+        self._filters: Optional[List[Any]] = None   # delete(): the filters so far (AND)
         self._org_id = org_id
         self._ids: Optional[List[Any]] = None
         self._hashes: Optional[List[Any]] = None
@@ -231,6 +272,18 @@ class _TableQuery:
     def eq(self, *a, **_kw):
         if len(a) == 2 and a[0] == "org_id" and self._org_id is not None and a[1] not in (None, self._org_id):
             self._foreign = True
+        if self._filters is not None and len(a) == 2 and a[0] != "org_id":
+            self._filters.append((a[0], [a[1]]))
+        return self
+
+    def delete(self):
+        """``table(t).delete().eq(col, v)`` / ``.in_(col, vs)`` ... ``.execute().data`` = the deleted
+        rows of the table addressed; several filters combine with AND.  A delete without a filter
+        other than ``org_id`` is refused at execute() (PostgREST refuses it too, and it would
+        empty the index)."""
+        if self._delete is None:
+            raise ValueError("this table is read-only in the GPU index")
+        self._filters = []
         return self
 
     def insert(self, rows):
@@ -244,6 +297,9 @@ class _TableQuery:
         return self
 
     def in_(self, column: str, values: Sequence[Any]):
+        if self._filters is not None:
+            self._filters.append((column, list(values)))
+            return self
         if column == "content_hash" and self._by_hash is not None:
             self._hashes = list(values)
             return self
@@ -253,6 +309,10 @@ class _TableQuery:
         return self
 
     def execute(self):
+        if self._filters is not None:
+            if not self._filters:
+                raise ValueError("DELETE requires a WHERE clause: a delete without a filter other than org_id is refused")
+            return _Reply([] if self._foreign else self._delete(self._filters))
         if self._rows is not None:
             return _Reply(self._insert(self._rows))
         if self._hashes is not None:
@@ -504,7 +564,14 @@ class GpuIndexClient:
                 scores, ids = self._download(S, I)
             return self._rows(ids, scores, len(ids), "rank", limit)
         self._pending_lex = LazyRows(fetch)
+        self._track(self._pending_lex)
         return self._pending_lex
+
+    def _track(self, lazy: LazyRows) -> None:
+        """Deferred replies hold LOCAL doc ids: a delete materialises the unresolved ones before
+        the ids shift (weak references: a reply nobody holds any more is not kept alive)."""
+        alive = [r for r in getattr(self, "_lazy", ()) if r() is not None and r()._fetch is not None]
+        self._lazy = alive + [weakref.ref(lazy)]      # (LazyRows compares by value: no hash, no WeakSet)
 
     # -------------------------------------------------------------- ingest
     def _check_org(self, rows: Sequence[Dict[str, Any]]) -> None:
@@ -602,6 +669,102 @@ class GpuIndexClient:
             del self._by_text
         return [{"id": p["id"]} for p in rows]
 
+    # -------------------------------------------------------------- delete
+    def _child_rows_where(self, filters, columns=("id", "document_id", "parent_id")) -> List[int]:
+        """Row indices of the child chunks that match every (column, values) filter."""
+        st = self.store
+        rows: Optional[set] = None
+        for column, values in filters:
+            if column not in columns:
+                raise ValueError(f"delete: rag_child_chunks rows are addressed by {' / '.join(columns)}, not {column!r}")
+            if column == "id":
+                hit = {i for i in (st.row_index(v) for v in values) if i is not None}
+            else:
+                want = set(values)
+                col = st.document_ids if column == "document_id" else st.parent_ids
+                hit = {i for i, v in enumerate(col) if v in want}
+            rows = hit if rows is None else rows & hit
+        return sorted(rows or ())
+
+    def _delete_rows(self, rows: List[int]) -> List[Dict[str, Any]]:
+        """Remove store rows ``rows`` (sorted, distinct) from the index, then from the store."""
+        if not rows:
+            return []
+        # a deferred reply issued before the delete holds local ids that are about to shift
+        self._pending_lex = None
+        for ref in getattr(self, "_lazy", ()):
+            lazy = ref()
+            if lazy is not None:
+                try:
+                    lazy.materialize()
+                except Exception:   # (its own caller sees that failure when it looks at the rows)
+                    pass
+        self._lazy = []
+        images = None
+        if self.image_index is not None:
+            dead = set(rows)
+            images = [j for j, r in enumerate(self.image_rows) if r in dead]
+            if images and len(images) >= len(self.image_rows):
+                raise N.NativeError("delete refused: every row of the image index would be deleted: build a new index")
+        self.index.delete_rows(np.asarray(rows, dtype=np.int64))       # index first: a refusal leaves both untouched
+        deleted = self.store.delete(rows)
+        if self.image_index is not None:
+            if images:
+                self.image_index.delete_rows(np.asarray(images, dtype=np.int64))
+            gone = np.asarray(rows, dtype=np.int64)
+            self.image_rows = [int(r - np.searchsorted(gone, r)) for r in self.image_rows if r not in dead]
+        if hasattr(self, "_by_text"):
+            del self._by_text
+        return deleted
+
+    def delete_children(self, ids: Sequence[Any]) -> List[Dict[str, Any]]:
+        """``table("rag_child_chunks").delete().in_("id", ids)``: the chunks leave the live index
+        (``GpuIndex.delete_rows``) and then the store -> the deleted rows.  Unknown ids delete
+        nothing and are not an error.  Unresolved deferred replies (``LazyRows``) are read back
+        first; the index is changed before the store, so a refused delete (every row of the
+        index) leaves both as they were."""
+        return self._delete_rows(self._child_rows_where([("id", list(ids))]))
+
+    def _delete_children_where(self, filters) -> List[Dict[str, Any]]:
+        return self._delete_rows(self._child_rows_where(filters))
+
+    def _delete_parents_where(self, filters) -> List[Dict[str, Any]]:
+        """Parent rows by ``id`` / ``document_id`` (a parent belongs to one document: the one its
+        children name) -> the deleted parent rows; their children go with them (schema :106)."""
+        st = self.store
+        pids: Optional[set] = None
+        for column, values in filters:
+            if column == "id":
+                hit = {v for v in values if v in st.parents}
+            elif column == "document_id":
+                want = set(values)
+                hit = {p for p, d in zip(st.parent_ids, st.document_ids) if d in want and p in st.parents}
+            else:
+                raise ValueError(f"delete: rag_parent_chunks rows are addressed by id / document_id, not {column!r}")
+            pids = hit if pids is None else pids & hit
+        pids = pids or set()
+        if not pids:
+            return []
+        self._delete_rows([i for i, p in enumerate(st.parent_ids) if p in pids])
+        return [st.parents.pop(p) for p in sorted(pids, key=list(st.parents).index)]
+
+    def _delete_documents_where(self, filters) -> List[Dict[str, Any]]:
+        """Documents by ``id`` -> [{"id": d}, ...] of those that had chunks; their children and
+        the parents those reference go with them (schema :65, :107)."""
+        st = self.store
+        docs: Optional[set] = None
+        for column, values in filters:
+            if column != "id":
+                raise ValueError(f"delete: rag_documents rows are addressed by id, not {column!r}")
+            docs = set(values) if docs is None else docs & set(values)
+        rows = [i for i, d in enumerate(st.document_ids) if d in (docs or ())]
+        found = list(dict.fromkeys(st.document_ids[i] for i in rows))
+        pids = {st.parent_ids[i] for i in rows}
+        self._delete_rows(rows)
+        for p in pids:
+            st.parents.pop(p, None)
+        return [{"id": d} for d in found]
+
     # -------------------------------------------------------------- tables
     def table(self, name: str) -> _TableQuery:
         if name == "rag_child_chunks":
@@ -615,14 +778,16 @@ class GpuIndexClient:
 
             def by_hash(hashes):
                 return [{"content_hash": h} for h in dict.fromkeys(hashes) if self.store.has_hash(h)]
-            return _TableQuery(fetch, by_hash=by_hash, insert=self.insert_children, org_id=self.org_id)
+            return _TableQuery(fetch, by_hash=by_hash, insert=self.insert_children, org_id=self.org_id,
+                               delete=self._delete_children_where)
         if name == "rag_parent_chunks":
             return _TableQuery(lambda ids: [dict(self.store.parents[p]) for p in ids
                                             if p in self.store.parents], insert=self.insert_parents,
-                               org_id=self.org_id)
+                               org_id=self.org_id, delete=self._delete_parents_where)
         # tenant discovery of the tool layer (tools/crm_knowledge.py:89-101 in the reference)
         if name == "rag_documents":
-            return _TableQuery(lambda _ids: [{"org_id": self.org_id}] if self.org_id else [])
+            return _TableQuery(lambda _ids: [{"org_id": self.org_id}] if self.org_id else [], org_id=self.org_id,
+                               delete=self._delete_documents_where)
         if name == "organizations":
             return _TableQuery(lambda _ids: [{"id": self.org_id}] if self.org_id else [])
         raise ValueError(f"table {name!r} is not served by the GPU index")

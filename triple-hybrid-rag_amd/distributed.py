@@ -160,6 +160,12 @@ class ShardedIndex:
         raise N.NativeError("append_rows is not supported on a ShardedIndex: rebuild the shards "
                             "(appends to a document-sharded index are out of scope)")
 
+    def delete_rows(self, *_a, **_kw):
+        """Not supported: a delete from a document-sharded index needs the same collective df /
+        length all-reduce as an append, and the shards' id ranges would move (Delete in place)."""
+        raise N.NativeError("delete_rows is not supported on a ShardedIndex: rebuild the shards "
+                            "(deletes from a document-sharded index are out of scope)")
+
     def _floor_exchange(self):
         if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline"):
             return None

@@ -22,6 +22,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, Optional
 
+import functools
 import logging
 import os
 import warnings
@@ -40,6 +41,17 @@ def floor_width(k: int, n_shards: int) -> int:
     to the true k-th score unless one shard holds most of the k best."""
     m = max(16, 2 * -(-k // max(1, n_shards)))
     return max(1, min(m, N.THR_DENSE_MAX_K, 4096 // max(1, n_shards)))   # (n_shards * m values fit the band kernel's LDS)
+
+
+def _refuse_when_unusable(fn):
+    """A delete that failed in its in-place phase leaves rows half moved (GpuIndex.delete_rows): the
+    index marks itself unusable, and no search, append or delete may run on it afterwards."""
+    @functools.wraps(fn)
+    def call(self, *a, **kw):
+        if getattr(self, "_unusable", None):
+            raise N.NativeError(self._unusable)
+        return fn(self, *a, **kw)
+    return call
 
 
 @dataclass
@@ -80,6 +92,8 @@ class GpuIndex:
         self._lex_global = False    # idf / avgdl are a sharded corpus' (set_lexical_rows with a group)
         self._spare: Dict[str, torch.Tensor] = {}     # CSR payload name -> destination of the next append
         self._csr_cap: Dict[str, torch.Tensor] = {}   # CSR payload name -> the capacity buffer behind its view
+        self._mutations = 0     # appends + deletes so far (index_build.save: the host arrays are stale)
+        self._unusable: Optional[str] = None   # set when a delete failed while rows were moving in place
 
     # ------------------------------------------------------------ builders
     def _t(self, a, dtype):
@@ -355,13 +369,13 @@ class GpuIndex:
         return self
 
     @staticmethod
-    def _host_or_device(a, name: str, integer: bool = False):
+    def _host_or_device(a, name: str, integer: bool = False, who: str = "append_rows"):
         """``a`` where it lives, as a tensor or a numpy array (host data: no device work)."""
         t = a if isinstance(a, torch.Tensor) else np.asarray(a)
         is_int = not t.dtype.is_floating_point and t.dtype != torch.bool if isinstance(t, torch.Tensor) \
             else np.issubdtype(t.dtype, np.integer)
         if integer and not is_int:
-            raise N.NativeError(f"append_rows: {name} must be an integer array, got {t.dtype}")
+            raise N.NativeError(f"{who}: {name} must be an integer array, got {t.dtype}")
         return t
 
     def _validate_append(self, docs, lex, collections, tokens, mentions, n_rows) -> dict:
@@ -481,6 +495,7 @@ class GpuIndex:
             tail16, err = None, 0.0
         return want, tail16, err, t0
 
+    @_refuse_when_unusable
     def append_rows(self, docs, lex=None, collections=None, tokens=None, mentions=None,
                     n_rows: Optional[int] = None) -> range:
         """Append m chunks to the live index -> the range of their LOCAL doc ids (add doc_base for
@@ -562,6 +577,7 @@ class GpuIndex:
         # with n), the candidate lists of a pending dense_shortlist
         self._ws = None
         self._shortlist_of = None
+        self._mutations += 1
         torch.cuda.current_stream(self.device).synchronize()
         return range(n_old, n_new)
 
@@ -590,6 +606,16 @@ class GpuIndex:
         doclen_buf = self._buffer("doclen", L["doclen"], n_new)
         doclen_buf[n_old:n_new].copy_(dl_full[n_old:n_new])
         doclen = doclen_buf[:n_new]
+        out = self._lexical_derived(rowptr, post_doc, post_tf, doclen, n_new)
+        # (doclen is swapped in with the dict: only its backing buffer is noted among the row arrays)
+        new["doclen"] = (doclen_buf, n_new)
+        return out
+
+    def _lexical_derived(self, rowptr, post_doc, post_tf, doclen, n_new: int) -> dict:
+        """What follows a changed CSR (an append's or a delete's), as a new ``self.lex`` dict + "df":
+        df from the row pointers, idf / avgdl as set_lexical_rows computes them, the pruning bounds
+        and the dense-term rows for the new row count."""
+        L = self.lex
         # idf / avgdl as set_lexical_rows computes them: float64 numpy on the host from the device's df
         df = rowptr[1:] - rowptr[:-1]
         dfh = df.cpu().numpy().astype(np.float64)
@@ -602,8 +628,6 @@ class GpuIndex:
         out["dense"] = N.bm25_dense_terms(rowptr, post_doc, post_tf, out["bounds"][2], n_new, out["dense_share"]) \
             if out["dense_share"] > 0 else None
         out["df"] = df
-        # (doclen is swapped in with the dict: only its backing buffer is noted among the row arrays)
-        new["doclen"] = (doclen_buf, n_new)
         return out
 
     def _append_mentions(self, mentions, n_old: int, dest: dict) -> dict:
@@ -629,6 +653,187 @@ class GpuIndex:
         dest.update(men_chunk=mc, men_conf=mw)
         return dict(ent_rowptr=G["ent_rowptr"], ent_col=G["ent_col"], men_rowptr=rowptr,
                     men_chunk=mc[:nnz], men_conf=mw[:nnz])
+
+    # ------------------------------------------------------------ delete
+    # Delete in place (DESIGN.md "Delete in place"): after delete_rows every device array is what a
+    # fresh build over the surviving rows, in their old order, would hold -- the delete pays, the query
+    # path does not change.  The store this index stands in for deletes by cascade
+    # (20260114_rag2_schema.sql:65-66, 106-108, 187, 217-218; tests/test_rag2_e2e.py:276-293).
+    STAGING_BYTES = 256 << 20    # the large per-row arrays are compacted through a buffer of at most this size
+
+    def _own_buffer(self, name: str, view: torch.Tensor) -> torch.Tensor:
+        """The capacity buffer behind ``view`` (reserve_rows / append_rows), or the view itself."""
+        back = self._backing.get(name)
+        if back is not None and back.data_ptr() == view.data_ptr() and back.shape[1:] == view.shape[1:] and \
+                back.shape[0] >= view.shape[0]:
+            return back
+        return view
+
+    def _compact_dest(self, name: str, like: torch.Tensor) -> torch.Tensor:
+        """Destination of a CSR compaction (out of place, room for every old entry: the kept count
+        is the kernel's result): the spare buffer of the last append or delete when it has the room."""
+        sp = self._spare.get(name)
+        if sp is not None and sp.shape[0] >= like.shape[0] and sp.dtype == like.dtype and sp.data_ptr() != like.data_ptr():
+            return sp
+        return torch.empty(like.shape[0], dtype=like.dtype, device=self.device)
+
+    @_refuse_when_unusable
+    def delete_rows(self, ids) -> torch.Tensor:
+        """Delete chunks from the live index -> the int32 [n_old] remap on the device: old LOCAL
+        doc id -> new local id, -1 = deleted.  ``ids``: local doc ids, host or device, any order,
+        repeats allowed.  The survivors keep their order and are renumbered 0 .. n' - 1; afterwards
+        every device array is, to the bit, what a fresh build over the surviving rows would hold
+        (same vocabulary size, entity set and shortlist flavour: a term or entity whose list empties
+        keeps its id, and "auto" is not re-decided on the smaller row count), and the next search
+        no longer sees the rows.  An update is a delete followed by an append.
+
+        Two phases.  Phase 1 does everything that can fail -- validation (integer ids inside
+        [0, n_docs), at least one survivor: deleting every row is refused, build a new index),
+        every allocation (the CSR destinations, the staging buffer, the bounds and dense-term
+        rows), thr_csr_compact over the postings and the mentions, the new idf / avgdl / bounds,
+        the small per-row arrays (norms, collections, lengths) gathered out of place -- and touches
+        nothing a query reads: a failure there leaves the index answering over the old rows.
+        Phase 2 only copies inside buffers that already exist: the float32 rows and the token
+        store are compacted IN PLACE from the first deleted row on, in ascending chunks through
+        the staging buffer (every source row lies at or behind its destination, so nothing is read
+        after it was overwritten), the float16 image is re-quantised from the tile of the first
+        deleted row on; then the new views and the row count are swapped in.  It allocates
+        no device memory (every buffer it writes, the error slots included, exists by then).  An exception out of phase 2 (a HIP error) leaves rows half moved: the index marks
+        itself unusable and every later search, append or delete raises.
+
+        Synchronises the main and the side stream first (not a query-path call): a query running
+        concurrently on another stream is excluded by that, exactly as for the float16 tail write
+        of append_rows.  The backing buffers keep their capacity for later appends.  Not supported
+        on a document shard of a sharded index."""
+        E = N.NativeError
+        n_old = self.n_docs
+        if getattr(self, "_lex_global", False):
+            raise E("delete_rows: not supported on a document shard (idf / avgdl are the whole corpus': "
+                    "the delete needs a collective df / length all-reduce)")
+        if (ids.numel() if isinstance(ids, torch.Tensor) else np.asarray(ids).size) == 0:
+            return torch.arange(n_old, dtype=torch.int32, device=self.device)   # (also a plain [])
+        t = self._host_or_device(ids, "ids", integer=True, who="delete_rows").reshape(-1)
+        first, hi = int(t.min()), int(t.max())
+        if first < 0 or hi >= n_old:
+            raise E(f"delete_rows: ids are local doc ids, 0 .. {n_old - 1}")
+        uniq = int(torch.unique(t).numel()) if isinstance(t, torch.Tensor) else int(np.unique(t).size)
+        if uniq >= n_old:
+            raise E("delete_rows: every row would be deleted: build a new index")
+        # ---- phase 1: nothing a query reads is written
+        self._sync_streams()
+        keep = torch.ones(n_old, dtype=torch.bool, device=self.device)
+        keep[self._t(t, torch.int64)] = False
+        src = keep.nonzero().reshape(-1)          # new id -> old id, ascending
+        n_new = int(src.shape[0])
+        rank = torch.cumsum(keep, 0, dtype=torch.int32) - 1
+        remap = torch.where(keep, rank, torch.full_like(rank, -1))
+        new = {}          # name -> (buffer, logical rows): swapped in at the end
+        for name, view in self._row_arrays().items():
+            if name in ("docs", "docs16", "tokens"):
+                continue
+            buf = torch.empty_like(self._own_buffer(name, view))     # (4 - 8 bytes a row; keeps the capacity)
+            torch.index_select(view, 0, src, out=buf[:n_new])
+            new[name] = (buf, n_new)
+        dest = {}         # CSR payload name -> the capacity buffer it was compacted into
+        lex_new = graph_new = None
+        if self.lex is not None:
+            L = self.lex
+            rowptr, pd, ptf, k = N.csr_compact(L["rowptr"], L["post_doc"], L["post_tf"], remap, 0,
+                                               self._compact_dest("post_doc", L["post_doc"]),
+                                               self._compact_dest("post_tf", L["post_tf"]))
+            dest.update(post_doc=pd, post_tf=ptf)
+            lex_new = self._lexical_derived(rowptr, pd[:k], ptf[:k], new["doclen"][0][:n_new], n_new)
+        if self.graph is not None:
+            G = self.graph
+            rowptr, mc, mw, k = N.csr_compact(G["men_rowptr"], G["men_chunk"], G["men_conf"], remap, self.doc_base,
+                                              self._compact_dest("men_chunk", G["men_chunk"]),
+                                              self._compact_dest("men_conf", G["men_conf"]))
+            dest.update(men_chunk=mc, men_conf=mw)
+            graph_new = dict(ent_rowptr=G["ent_rowptr"], ent_col=G["ent_col"], men_rowptr=rowptr,
+                             men_chunk=mc[:k], men_conf=mw[:k])
+        # the large arrays: rows below the first deleted one stay where they are
+        t0 = first // 32 * 32                     # the float16 tile of the first deleted row is re-quantised
+        f16 = self.docs is not None and self.shortlist in ("f16", "f16-inline")
+        moves = []        # (name, buffer, first row that moves, rows per chunk)
+        per_q = 32        # rows per chunk of the float16 re-measure / re-quantisation
+        for name, start in (("docs", t0), ("tokens", first)):
+            view = getattr(self, name)
+            if view is None:
+                continue
+            buf = self._own_buffer(name, view)
+            new[name] = (buf, n_new)              # the shorter view is swapped in whether or not a row moves
+            row_bytes = max(1, view[0].numel() * view.element_size())
+            per = max(32, self.STAGING_BYTES // row_bytes // 32 * 32)
+            if name == "docs":
+                per_q = min(per, (max(n_new - t0, t0) + 31) // 32 * 32)
+            if start < n_new:                     # (a delete of trailing rows only moves nothing)
+                moves.append((name, buf, start, min(per, (n_new - start + 31) // 32 * 32)))
+        stage = torch.empty(max([per * (buf[0].numel() * buf.element_size()) for _, buf, _, per in moves] or [0]),
+                            dtype=torch.uint8, device=self.device)
+        q16 = buf16 = errs = err_max = None
+        if f16:
+            per_tail = max([p for name, _, _, p in moves if name == "docs"] or [32])
+            below = range(0, t0, per_q) if self.shortlist == "f16" else range(0, min(t0, 1))
+            n_tail = len(range(t0, n_new, per_tail))
+            errs = torch.zeros(len(below) + n_tail, dtype=torch.float32, device=self.device)
+            err_max = torch.zeros(1, dtype=torch.float32, device=self.device)
+            if self.shortlist == "f16":
+                q16 = torch.empty((per_q, self.dim), dtype=torch.float16, device=self.device)
+                buf16 = self._own_buffer("docs16", self.docs16)
+            # the error of the rows that do not move, measured as the fresh build measures it (the
+            # float16 copy's on the normalised rows, into the temporary; the in-flight rounding's in one call)
+            for j, a in enumerate(below):
+                if self.shortlist == "f16":
+                    b = min(a + per_q, t0)
+                    N.dense_quantize_f16_into(self.docs[a:b], q16[:b - a], errs[n_tail + j:n_tail + j + 1])
+                else:
+                    N.dense_quantize_f16_into(self.docs[:t0], None, errs[n_tail:n_tail + 1])
+        torch.cuda.current_stream(self.device).synchronize()    # (an asynchronous failure of phase 1 surfaces here)
+        # ---- phase 2: in-place row moves inside existing buffers, then the swap; no device allocation
+        try:
+            for name, buf, start, per in moves:
+                view = getattr(self, name)
+                tmp_all = stage[:per * buf[0].numel() * buf.element_size()].view(buf.dtype).view((per,) + tuple(buf.shape[1:]))
+                for j, a in enumerate(range(start, n_new, per)):
+                    b = min(a + per, n_new)
+                    tmp = tmp_all[:b - a]
+                    torch.index_select(view, 0, src[a:b], out=tmp)
+                    buf[a:b].copy_(tmp)
+                    if name == "docs" and f16:
+                        if q16 is not None:
+                            r16 = (b - a + 31) // 32 * 32     # (the last tile's padding is what a full quantisation writes)
+                            N.dense_quantize_f16_into(tmp, q16[:r16], errs[j:j + 1])
+                            buf16[a:a + r16].copy_(q16[:r16])
+                        else:
+                            N.dense_quantize_f16_into(tmp, None, errs[j:j + 1])
+            if self.docs16 is not None:
+                new["docs16"] = (self._own_buffer("docs16", self.docs16), (n_new + 31) // 32 * 32)
+            # ---- swap
+            # the buffers the CSRs were read from become the destinations of the next append or delete
+            old = dict(self.lex or {}, **(self.graph or {}))
+            cap = self._csr_cap
+            self._spare = {k: cap[k] if k in cap and cap[k].data_ptr() == old[k].data_ptr() else old[k] for k in dest}
+            self._csr_cap = dest
+            if lex_new is not None:
+                self.df_local = self.df_global = lex_new.pop("df")
+                self.lex = lex_new
+            if graph_new is not None:
+                self.graph = graph_new          # (the chunk-major copy of the mentions is rebuilt on next use)
+            for name, (buf, n) in new.items():
+                self._backing[name] = buf
+                self._set_row_array(name, buf[:n])
+            if f16:
+                self.doc_rel_err = float(torch.amax(errs, 0, keepdim=True, out=err_max).item())
+            self.n_docs = n_new
+            self._ws = None
+            self._shortlist_of = None
+            self._mutations += 1
+            torch.cuda.current_stream(self.device).synchronize()
+        except BaseException as exc:
+            self._unusable = ("this index is unusable: a delete failed while rows were being moved in place "
+                              f"({type(exc).__name__}: {exc}); build a new index")
+            raise
+        return remap
 
     # ------------------------------------------------------------ channels
     def _workspace(self, nbytes: int) -> torch.Tensor:
@@ -658,6 +863,7 @@ class GpuIndex:
             return N.dense_f16_max_queries(self.dim, True)
         return 1 << 30
 
+    @_refuse_when_unusable
     def dense_search(self, queries: torch.Tensor, k: int, kprime: Optional[int] = None,
                      rescue: bool = True, sync: bool = True, collections=None, floor_exchange=None):
         """Exact cosine top-k -> (scores f64, ids i64, counts i32, n_rescued).  Queries the
@@ -744,6 +950,7 @@ class GpuIndex:
         dc, qc = self._qcoll(collections, queries.shape[0])
         return queries, kp, ws, dc, qc
 
+    @_refuse_when_unusable
     def dense_shortlist(self, queries: torch.Tensor, k: int, n_shards: int, kprime: Optional[int] = None,
                         collections=None) -> torch.Tensor:
         queries, kp, ws, dc, qc = self._f16_call(queries, k, kprime, collections)
@@ -754,6 +961,7 @@ class GpuIndex:
         self._shortlist_of = (queries.shape[0], kp, collections is not None, ws.data_ptr())
         return lb
 
+    @_refuse_when_unusable
     def dense_finish(self, queries: torch.Tensor, k: int, gfloor: Optional[torch.Tensor] = None,
                      kprime: Optional[int] = None, rescue: bool = True, collections=None,
                      lb_all: Optional[torch.Tensor] = None):
@@ -777,6 +985,7 @@ class GpuIndex:
                                        self._ws_rescue, doc_coll=dc, query_coll=qc)
         return S, I, cnt, flags0, n_rescued
 
+    @_refuse_when_unusable
     def scan_probe(self, queries: torch.Tensor) -> None:
         """Launch ONLY the streaming scan kernel of the last dense_search (same workspace, so the
         thresholds tau are the ones that search computed): the timing/roofline probe."""
@@ -798,6 +1007,7 @@ class GpuIndex:
             raise N.NativeError("collections: one id per query")
         return self.doc_coll, qc
 
+    @_refuse_when_unusable
     def bm25_search(self, query_terms: torch.Tensor, k: int, collections=None,
                     conjunctive: bool = False, prune: bool = True, dense_rows: bool = True):
         """collections: int32 [nq] collection id per query (-1 = unfiltered) or None.
@@ -829,6 +1039,7 @@ class GpuIndex:
                            doc_coll=dc, query_coll=qc, workspace=self._ws_lex,
                            dense=L["dense"] if prune and dense_rows else None)
 
+    @_refuse_when_unusable
     def graph_search(self, query_seeds: torch.Tensor, k: int, hops: int = 2):
         G = self.graph
         # three tiers on the device (small / full on-chip capacities, then a capacity-free walk
@@ -843,6 +1054,7 @@ class GpuIndex:
                                     workspace=self._ws_graph)
         return S, I, cnt
 
+    @_refuse_when_unusable
     def maxsim(self, qtok: torch.Tensor, cand_global_ids: torch.Tensor) -> torch.Tensor:
         """MaxSim of each query against its candidate docs (global ids; ids outside this
         shard or negative score -inf)."""
@@ -850,6 +1062,7 @@ class GpuIndex:
                             self.doc_base, packed=self.tokens_packed)
 
     # ------------------------------------------------------------ pipeline
+    @_refuse_when_unusable
     def side_channels(self, query_terms, lexical_top_k: int, query_seeds, graph_top_k: int, hops: int):
         """The lexical and graph channels of a batch on a second HIP stream, so that they run
         beside the dense channel instead of after it: they do not depend on it before the fusion,
@@ -893,6 +1106,7 @@ class GpuIndex:
             self._side = torch.cuda.Stream(device=self.device, priority=0 if eq else -1)
         return self._side
 
+    @_refuse_when_unusable
     def retrieve_batch(self, queries: torch.Tensor, query_terms: Optional[torch.Tensor] = None,
                        query_seeds: Optional[torch.Tensor] = None, top_k: int = 10,
                        semantic_top_k: int = 100, lexical_top_k: int = 50, graph_top_k: int = 50,
@@ -923,3 +1137,4 @@ class GpuIndex:
             # on ``rerank_score or 0`` (retrieval.py:449-455), on the device
             ids, sc, cnt = N.rerank_order(self.maxsim(qtok, ids), ids, cnt, top_k)
         return BatchResult(ids, sc, cnt, ch, nres)
+

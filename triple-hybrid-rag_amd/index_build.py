@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import json
 import os
+import weakref
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence
 
@@ -249,11 +250,24 @@ _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modaliti
 _NO_PAGE = np.iinfo(np.int32).min   # store_pages.npy: the SQL column is nullable (page INT)
 
 
+def _mutated_since_sync(hi: HostIndex, gpu_index) -> bool:
+    """True when ``gpu_index`` was appended to or deleted from since ``hi`` last held its rows: it
+    was built from ``hi`` (no mutation yet), or ``refresh_from_gpu`` pulled THIS index at THIS
+    mutation count.  (The row count alone does not tell: a delete followed by an append can leave
+    it as it was.)"""
+    count = getattr(gpu_index, "_mutations", 0)
+    if not count:
+        return False
+    ref, seen = getattr(hi, "_synced", (None, 0))
+    return ref is None or ref() is not gpu_index or seen != count
+
+
 def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
-    """After ``GpuIndex.append_rows`` (the ingest seam, rag2/ingest.py:361-470) the device holds
-    rows the HostIndex has never seen: pull the source arrays back, in place, so that ``hi`` --
-    and a ``save`` of it -- equals a build from all the rows.  The store is appended to by the
-    client (``CorpusStore.append``) and is not touched here."""
+    """After ``GpuIndex.append_rows`` (the ingest seam, rag2/ingest.py:361-470) or
+    ``GpuIndex.delete_rows`` the device holds other rows than the HostIndex: pull the source arrays
+    back, in place, so that ``hi`` -- and a ``save`` of it -- equals a build from the rows the index
+    holds now.  The store is appended to and deleted from by the client (``CorpusStore.append`` /
+    ``.delete``) and is not touched here."""
     g = gpu_index
     if g.docs is not None:
         hi.docs = g.docs.cpu().numpy()
@@ -264,11 +278,18 @@ def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
     if g.graph is not None:
         G = g.graph
         hi.men_rowptr, hi.men_chunk, hi.men_conf = (G[k].cpu().numpy() for k in ("men_rowptr", "men_chunk", "men_conf"))
-    if hi.tokens is not None and len(hi.tokens) != g.n_docs:
+    if hi.tokens is not None:
+        stale = len(hi.tokens) != g.n_docs
         if g.tokens_packed:
-            raise ValueError("the index keeps its token store in the packed layout only: the appended rows' "
-                             "token matrices cannot be pulled back -- append them to HostIndex.tokens before save()")
-        hi.tokens = g.tokens.cpu().numpy()
+            # the packed layout cannot be pulled back: the caller keeps HostIndex.tokens in step, and a
+            # token store of the right length is trusted (as before deletes existed)
+            if stale:
+                raise ValueError("the index keeps its token store in the packed layout only: the appended rows' "
+                                 "token matrices cannot be pulled back -- append them to HostIndex.tokens (and drop "
+                                 "the deleted rows' with the remap delete_rows returned) before save()")
+        elif stale or _mutated_since_sync(hi, g):
+            hi.tokens = g.tokens.cpu().numpy()
+    hi._synced = (weakref.ref(g), getattr(g, "_mutations", 0))
     hi.derived = None   # (computed for the old rows; save(hi, path, gpu_index) exports the current ones)
     return hi
 
@@ -278,11 +299,13 @@ def save(hi: HostIndex, path: str, gpu_index=None) -> None:
     """``gpu_index``: the GpuIndex built from ``hi`` -- what its set-up computed on the device
     (export_derived) is saved too, so that a later ``load(path).to_gpu()`` does not recompute it."""
     os.makedirs(path, exist_ok=True)
-    if gpu_index is not None and gpu_index.n_docs != len(hi.docs):
-        refresh_from_gpu(hi, gpu_index)     # rows were appended on the device: never save the stale arrays
+    if gpu_index is not None and (gpu_index.n_docs != len(hi.docs) or _mutated_since_sync(hi, gpu_index)):
+        # rows were appended or deleted on the device (a delete followed by an append can leave the
+        # row count as it was): never save the stale arrays
+        refresh_from_gpu(hi, gpu_index)
     if hi.store is not None and len(hi.store.child_ids) != len(hi.docs):
         raise ValueError(f"the row store holds {len(hi.store.child_ids)} chunks, the index {len(hi.docs)}: "
-                         "they were not appended to together (GpuIndexClient.insert_children does both)")
+                         "they were not appended to together (GpuIndexClient.insert_children / delete_children change both)")
     for name in _ARRAYS:
         arr = getattr(hi, name)
         if arr is not None:

@@ -99,6 +99,19 @@ class _ShardEndpoint(GpuIndexClient):
         raise N.NativeError("insert is not supported through a sharded index client: rebuild the shards "
                             "(appends to a document-sharded index are out of scope)")
 
+    def _refuse_delete(self, *_a, **_kw):
+        """Not supported: a delete from a document-sharded index needs the same collective df /
+        length all-reduce as an append, and the front's store holds the WHOLE corpus' rows while
+        its index holds one shard's (Delete in place).  Raised before anything is
+        touched, whichever way the delete arrives: ``table(t).delete()...execute()`` on the three
+        tables routes through the ``_delete_*_where`` methods, the direct call through
+        ``delete_children``."""
+        raise N.NativeError("delete is not supported through a sharded index client: rebuild the shards "
+                            "(deletes from a document-sharded index are out of scope)")
+
+    delete_children = _delete_rows = _refuse_delete
+    _delete_children_where = _delete_parents_where = _delete_documents_where = _refuse_delete
+
     # ---------------------------------------------------------------- messages
     def _broadcast(self, msg: Optional[torch.Tensor]) -> torch.Tensor:
         if msg is None:
