@@ -71,7 +71,7 @@ inline void bm_stamps_report(const BmLayout& L, hipStream_t st, int n_queries, i
     // the sweep items one by one: when each started and ended (cycles since the first), its passes and survivors
     int h_ctl[8];
     (void)hipMemcpy(h_ctl, L.ctl, sizeof(h_ctl), hipMemcpyDeviceToHost);
-    const int ns = h_ctl[5];
+    const int ns = h_ctl[CTL_SWEEPS];
     std::vector<unsigned long long> lg((size_t)4 * (ns > 0 ? ns : 1));
     (void)hipMemcpy(lg.data(), bm_stamps_sweep_log(L), lg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     unsigned long long t0 = ~0ull, t1 = 0;
@@ -81,7 +81,7 @@ inline void bm_stamps_report(const BmLayout& L, hipStream_t st, int n_queries, i
     }
     fprintf(stderr, "[bm25 sweep items] %d items, %llu cycles from the first start to the last end\n", ns, ns ? t1 - t0 : 0ull);
     if (!getenv("THR_BM25_ITEM_LOG")) return;
-    const int ni = h_ctl[0];
+    const int ni = h_ctl[CTL_ITEMS];
     std::vector<unsigned long long> wl((size_t)4 * (ni > 0 ? ni : 1));
     (void)hipMemcpy(wl.data(), bm_stamps_walk_log(L), wl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     for (int i = 0; i < ni; ++i)
