@@ -31,7 +31,7 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     out = {"queries": nq, "scan_ms_real_tau": round(timed(), 4)}
-    # tau is the first array of the workspace (make_plan: off_tau = 0), qpad floats
+    # tau is the first array of the workspace (make_plan: tau is the first take), qpad floats
     qpad = (nq + 127) // 128 * 128
     tau = idx._ws[: 4 * qpad].view(torch.float32)
     keep = tau.clone()

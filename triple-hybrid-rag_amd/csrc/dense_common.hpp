@@ -1,7 +1,8 @@
 // What the dense translation units share: the sizes and records of the pipeline, the device helpers
 // and tile sizes more than one scan flavour uses, and the host functions the units call each other
-// through -- the knob readers and the scan grid of dense.hip, the launch functions of the scans, each
-// defined beside its kernels.
+// through -- the knobs and the scan grid of dense.hip; the launch functions of the scans, of the
+// selection and of the rescoring, each defined beside its kernels, which take the records dense.hip
+// fills once per call (DensePlan, DenseIndex, DenseBatch, DensePhase).
 #pragma once
 #include <type_traits>
 
@@ -17,6 +18,8 @@ constexpr int WBUF = 256;                  // per-wave LDS staging slots for pas
 constexpr int ROW_BITS = 27;               // tile-list entries pack (query-in-tile << 27 | row)
 constexpr uint32_t ROW_MASK = (1u << ROW_BITS) - 1;
 constexpr int ROW_BITS_F16 = 25;           // f16 shortlist scans: up to 96 queries per tile -> 7 bits
+constexpr int SEL_BIG_BAND = 1024;         // rows a query's shortlist may hold (K4a -> K4b): the row stride of sel_rows
+constexpr int CS_BINS = 4096;              // histogram bins of the coarse selects = most values select_band ranks in their place
 
 struct Cand {
     float score;
@@ -96,7 +99,69 @@ inline size_t f16_lds_bytes(int dim, int nq) {
 }
 inline int f16_pick_nq(int dim) { return f16_lds_bytes(dim, 2) <= 160 * 1024 ? 2 : 1; }
 
-// dense.hip: the knobs (each read once, there), the grid of a scan
+// fp32 error bound of the MFMA scans, relative to ||q||*||d||, in units of 2^-24: a dim-long fma chain
+inline double scan_eps(int dim) {
+    const double u = 5.9604644775390625e-08;
+    return ((double)dim + 16.0) * u;
+}
+
+// ---- what the launch functions take: filled once per entry point (dense.hip) ----
+// The work plan of a batch and its workspace, carved by make_plan.
+constexpr int KIND_F32 = 0, KIND_F16 = 1;
+struct DensePlan {
+    int kind;      // KIND_F32: float32 MFMA scan; KIND_F16: an f16 MFMA scan
+    bool packed;   // KIND_F16 only: dense_scan_f16q[s] over the fragment-major copy (queries in registers,
+                   // rows through LDS; the candidate area is written in per-lane segments), else float32
+                   // rows rounded in flight
+    int nq, qtile, ntiles, qpad, row_bits, ksample, tile_cap;
+    bool sampled;
+    int64_t groups, sample_groups, sample_stride, sample_docs;
+    float* tau;
+    float* qerr;         // null for KIND_F32 (no quantisation term)
+    int* cnt;            // } zeroed per call
+    int* tcnt;           // } by one memset
+    Cand *cand, *tlist;
+    float* sample;
+    _Float16* qfrag;
+    int32_t *sel_rows, *sel_meta;   // K4a -> K4b shortlists
+    size_t total;
+};
+// The index as the caller holds it.
+struct DenseIndex {
+    const float *docs, *inv_norm;
+    int64_t n_docs;
+    int dim;
+    const double* dnorm = nullptr;
+    int64_t id_base = 0;
+    const int32_t* doc_coll = nullptr;
+    const _Float16* docs16 = nullptr;   // the normalised f16 copy (null: float32 rows)
+    double doc_rel_err = 0.0;
+};
+// The batch of one call (no outputs before the shards' exchange).
+struct DenseBatch {
+    const float* queries;
+    int n_queries, k, kprime;
+    const int32_t* query_coll;
+    hipStream_t st;
+    double* out_scores = nullptr;
+    int64_t* out_ids = nullptr;
+    int32_t* out_counts = nullptr;
+    uint32_t* out_flags = nullptr;
+};
+// What only document shards use.  PIPE_ALL = one call; PIPE_SHORTLIST = K1..K3 + the top_m lower
+// bounds (the candidate lists stay in the workspace); PIPE_FINISH = K4 on those lists with the
+// shards' common floor.
+enum { PIPE_ALL = 0, PIPE_SHORTLIST = 1, PIPE_FINISH = 2 };
+struct DensePhase {
+    int phase = PIPE_ALL;
+    float* top_lb = nullptr;         // SHORTLIST: this shard's lower bounds [nq, top_m]
+    int top_m = 0;
+    const float* gfloor = nullptr;   // FINISH: the common floor, or
+    const float* lb_all = nullptr;   //   the shards' gathered lower bounds [n_shards, nq, top_m]
+    int n_shards = 0;
+};
+
+// dense.hip: the knobs (read once, there), the grid of a scan
 bool qreg_staggered(int dim);
 int qreg_waves(int dim);
 int qreg_shape(int dim);
@@ -132,5 +197,11 @@ int launch_pack_queries(int dim, const float* queries, int n_queries, int qpad, 
 // docs16 == null: the rounding error alone (measure_f16_error)
 int launch_quantize_f16(const float* docs, int64_t n_docs, int dim, _Float16* docs16,
                         unsigned int* max_rel_err, hipStream_t st);
+// dense_select.hip: K2 (the sampled and the unsampled form), K3b, K4a (nseg: segments per query of
+// the candidate area as the register-resident scan left it, else 0); dense_rescore.hip: K4b, both sizes
+int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& B);
+int launch_bucket(const DensePlan& P, hipStream_t st);
+int launch_band(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, const DensePhase& S, int nseg);
+int launch_rescore(const DensePlan& P, const DenseIndex& X, const DenseBatch& B);
 
 }  // namespace thr

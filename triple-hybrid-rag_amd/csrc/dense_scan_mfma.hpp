@@ -2,8 +2,8 @@
 //
 // Why MFMA for an HBM-bound scan: with 32 queries per corpus pass the scan needs
 // 2*32*768 flop per 3 KiB row = 16 flop/B, i.e. ~98 TFLOP/s at the HBM rate.  The
-// VALU version of this kernel (dense_scan<> in dense.hip) issues one v_fmac per 128
-// flop and tops out at ~51 TFLOP/s (3.2 TB/s, profiles/r1_bench_valu_qt32_*): it is
+// VALU version of this kernel (dense_scan<>, since removed) issued one v_fmac per 128
+// flop and topped out at ~51 TFLOP/s (3.2 TB/s, profiles/r1_bench_valu_qt32_*): it is
 // VALU-issue-bound, not bandwidth-bound.  v_mfma_f32_32x32x2_f32 has the same nominal
 // rate (64 flop/clk/SIMD) but is ONE instruction per 4096 flop, and its result is an
 // exact k-ordered f32 fma chain (MI355X guide, "FP32-input MFMA"), so the numerics
