@@ -88,6 +88,37 @@ def test_append_rows_validation_runs_before_any_device_work():
     assert lexical.append_rows(rows[:0], lex=(d[:0], t[:0], None, 50)) == range(100, 100)
 
 
+def test_storage_knows_the_buffer_behind_an_array_until_the_array_is_replaced():
+    import torch
+    from triple_hybrid_rag_amd.index_mutate import _Storage
+    S = _Storage()
+    docs, docs16 = torch.arange(40.0).reshape(20, 2), torch.ones(32, 2, dtype=torch.float16)
+    assert S.behind("docs", docs) is docs and S.with_room("docs", docs, 20) is docs
+    assert S.padded("docs16", 33) == 64 and S.padded("docs", 33) == 33
+    # reserve: exactly the rows asked for (the float16 image: whole tiles), the old rows copied
+    buf, buf16 = S.with_room("docs", docs, 50, exact=True), S.with_room("docs16", docs16, 50, exact=True)
+    assert buf.shape == (50, 2) and buf16.shape == (64, 2) and torch.equal(buf[:20], docs)
+    view = buf[:20]
+    S.held["docs"] = (buf, view)
+    assert S.behind("docs", view) is buf and S.with_room("docs", view, 50) is buf
+    grown = S.with_room("docs", view, 51)                  # too small: GROWTH x the rows so far, at least the need
+    assert grown.shape[0] == 51 and torch.equal(grown[:20], docs)
+    S.held["docs"] = (buf, buf[:])
+    assert S.with_room("docs", S.held["docs"][1], 51).shape[0] == 75
+    # a builder replaced the array (set_dense again): the record is about a tensor the index no longer holds
+    again = docs.clone()
+    assert S.behind("docs", again) is again and S.with_room("docs", again, 25).shape[0] == 30
+    # CSR payloads: the buffer a mutation read from is the next one's destination
+    old = torch.arange(8, dtype=torch.int32)
+    dest = S.destination("post_doc", old, 10, grow=True)
+    assert dest.shape[0] == 12 and S.destination("post_doc", old, 8, grow=False).shape[0] == 8
+    S.rotate({"post_doc": (dest, dest[:10])}, {"post_doc": old, "doclen": docs})
+    assert S.spare == {"post_doc": old} and S.held["post_doc"][0] is dest
+    assert S.destination("post_doc", S.held["post_doc"][1], 8, grow=False) is old
+    assert S.destination("post_doc", S.held["post_doc"][1], 9, grow=False).shape[0] == 9      # no room
+    assert S.destination("post_doc", old[:4], 4, grow=False) is not old                        # never its own source
+
+
 def test_sharded_classes_refuse_appends():
     from triple_hybrid_rag_amd.distributed import ShardedIndex
     from triple_hybrid_rag_amd.sharded_client import ShardedIndexClient

@@ -355,7 +355,21 @@ def test_triple_hybrid_delete_append_delete_equals_fresh_build(T):
     gone1 = np.unique(np.concatenate([np.arange(2048, 2112), rng.choice(n0, 150, replace=False)]))
     alive = first.copy()
     alive[gone1] = False
+    # phase 2 of a delete (the in-place moves, then the swap) allocates no device memory: not one
+    # request reaches the caching allocator while either runs
+    allocated = []
+
+    def counted(fn):
+        def call(*args):
+            before = torch.cuda.memory_stats()["allocation.all.allocated"]
+            out = fn(*args)
+            allocated.append(torch.cuda.memory_stats()["allocation.all.allocated"] - before)
+            return out
+        return call
+    idx._move_rows, idx._commit = counted(idx._move_rows), counted(idx._commit)
     r1 = idx.delete_rows(gone1)
+    del idx._move_rows, idx._commit
+    assert allocated == [0, 0]
     assert idx.capacity_rows() == cap and idx.docs.data_ptr() == ptr    # the reservation survives, nothing reallocated
     # append the rest (local ids continue behind the survivors)
     sel, msel = doc >= n0, mc >= n0
