@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark: queries/sec for the fused top-10 of the RAG 2.0 retrieval hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config dense|dense_bm25|triple|triple_rerank|all]
-                    [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                    [--config dense|dense_bm25|triple|triple_rerank|all]
 
 A step = one pass of the hot path over one batch of ``--queries`` (default 2048) synthetic
 queries, inputs resident in HBM.  The headline line is always BASELINE.json configs[1]
-(1M-doc / 768-d dense-only cosine top-100 -> RRF -> fused top-10); at N = 1 the default run also
-times configs[2]-[4]'s pipelines on the same corpus (``configs`` in the JSON): dense + BM25,
-triple-hybrid, triple-hybrid + MaxSim rerank of the fused top-100.  For N > 1 the SAME corpus is
-sharded by document across the ranks (strong scaling, one process per GPU, RCCL all-gather of
-the per-shard top-k per channel, second all-gather for the rerank scores) and only ``--config``
-(default dense) is timed.
+(1M-doc / 768-d dense-only cosine top-100 -> RRF -> fused top-10).  A plain run does what that
+line needs and no more: it generates the inputs, warms up, times the K steps and prints the line.
+For N > 1 the SAME corpus is sharded by document across the ranks (strong scaling, one process
+per GPU, RCCL all-gather of the per-shard top-k per channel, second all-gather for the rerank
+scores) and ``--config`` (default dense) is timed.
 
-The JSON line also carries
+``--full`` adds everything else the benchmark measures and checks, each in runs of its own after
+the headline's: at N = 1 configs[2]-[4]'s pipelines on the same corpus (``configs`` in the JSON:
+dense + BM25, triple-hybrid, triple-hybrid + MaxSim rerank of the fused top-100) with a parity
+sample against the oracle, each channel kernel alone (``stages_alone``), the other shortlist
+flavours (``other_shortlists``) and ``--shard-proxy``; at N > 1 a rank's share of the step
+(``config.per_rank_ms``) and the pure document-sharded layout (``config.strong_doc_sharded``); and
   roofline      the dominant kernel -- the dense scan -- launched alone through
                 thr_dense_scan_probe_f16 and timed with HIP events on its stream: 2*N*D*Q flops
                 per launch / average launch time against the dense f16 MFMA peak; ``traffic`` =
@@ -21,14 +25,19 @@ The JSON line also carries
                 when the shape differs) and the HBM GB/s that traffic means at the measured time
   cpu_baseline  the CPU oracle's fast path (float32 BLAS shortlist + float64 rescoring,
                 oracle/thr_oracle.py) timed on this host's cores on a bounded sample (rank 0, N = 1)
+                and the fused top-10 of the timed path compared with it (``parity_check``)
   latency       the drop-in ``RAG2Retriever.retrieve()`` one query at a time (p50 / p95), and the
                 scan alone for batches of 1 / 32 / 256 queries as HBM GB/s (one pass over the
                 float16 copy: the regime where the HBM roofline applies)
+``--no-extras`` and ``--no-cpu-baseline`` leave parts of a ``--full`` run out.
 
 ``--dump-outputs DIR`` writes what the LAST timed step of every timed pipeline returned (the
 BatchResult of retrieve_batch: fused ids / scores / counts and every channel's list) as
 ``DIR/<pipeline>_<field>.npy``.  The inputs are seeded, so two builds of the library run with the
-same arguments can be compared array by array.
+same arguments can be compared array by array.  At N = 1 without ``--config`` the arrays are those
+of all four pipelines, with or without ``--full``: a plain run that dumps generates the lexical,
+graph and token inputs too and gives configs[2]-[4]'s pipelines their W + K steps after the
+headline's (their rates: ``configs``).
 """
 from __future__ import annotations
 
@@ -55,11 +64,15 @@ PMC_PROFILE = os.path.join(ROOT, "profiles", "r4_scan_f16qs_counters.json")
 DUMP_MAX_BYTES = 64_000_000
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's steps, also measure and check everything else: the other "
+                         "pipelines, shortlist flavours and layouts, each kernel alone, the roofline, the "
+                         "latency section, the CPU baseline and the parity with the oracle")
     ap.add_argument("--docs", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--queries", type=int, default=2048,
@@ -67,7 +80,8 @@ def parse():
                          "row slices per XCD, one full round of the 256 CUs for the default scan")
     ap.add_argument("--top-k", type=int, default=10)
     ap.add_argument("--config", choices=CONFIGS + ("all",), default=None,
-                    help="pipeline to time; default: all four at N = 1 (headline = dense), dense at N > 1")
+                    help="pipeline to time; default: dense (the headline), followed at N = 1 by the other "
+                         "three when --full or --dump-outputs is given; all = the four of them")
     ap.add_argument("--preset", choices=("configs1", "configs2", "configs3", "configs4"), default=None,
                     help="a BASELINE.json config at its stated size and layout: configs1 = 1M dense-only; "
                          "configs2 = 1M dense + BM25 + RRF(0.8/0.7); configs3 = 10M triple-hybrid cut into "
@@ -85,14 +99,16 @@ def parse():
                          "--doc-shards N forces the pure document-sharded layout")
     ap.add_argument("--min-shard-docs", type=int, default=500_000)
     ap.add_argument("--shard-proxy", type=int, default=0, metavar="G",
-                    help="N = 1 only: also hold the --docs corpus as G document shards in THIS process and "
+                    help="--full at N = 1 only: also hold the --docs corpus as G document shards in THIS process and "
                          "time one shard's share of a dense step (everything but the collectives) with and "
                          "without the shard floor exchange -> config.shard_floor_proxy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU oracle's leg (cpu_baseline, parity_check, parity_sample)")
     ap.add_argument("--cpu-queries", type=int, default=2048)
     ap.add_argument("--probe-reps", type=int, default=5)
     ap.add_argument("--no-extras", "--no-f16-extra", dest="no_extras", action="store_true",
-                    help="skip the other shortlist flavours, the other configs and the latency section")
+                    help="--full without the other shortlist flavours, the other configs and the latency "
+                         "section; --dump-outputs without the other configs")
     ap.add_argument("--lexical-mix", choices=("survey", "no-stopwords"), default="survey",
                     help="query terms of the lexical channel: survey = 4 term ids sampled in proportion to "
                          "df (SURVEY 8d: stop words included, ~0.5M postings per query at 1M docs); "
@@ -104,9 +120,11 @@ def parse():
                     help="after the timed steps, write what the last timed step of every timed pipeline "
                          "returned as DIR/<pipeline>_<field>.npy (float32 / float64; more than 64 MB in all: "
                          "the same seeded sample of the query rows of every array)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.shard_proxy and not args.full:
+        ap.error("--shard-proxy is one of the measurements of --full")
     if args.preset:
         args.config = {"configs1": "dense", "configs2": "dense_bm25", "configs3": "triple",
                        "configs4": "triple_rerank"}[args.preset]
@@ -115,6 +133,15 @@ def parse():
                 args.docs = 10_000_000
             args.doc_shards = args.doc_shards or args.gpus
     return args
+
+
+def which_config(args, world):
+    """The pipeline a run times, or "all": the four of CONFIGS, the headline (dense) first.  Without
+    ``--config`` that is dense alone, except at N = 1 in a ``--full`` run and in one that dumps its
+    outputs (whose arrays are those of all four pipelines, ``--full`` or not)."""
+    if args.config:
+        return args.config
+    return "all" if world == 1 and not args.no_extras and (args.full or args.dump_outputs) else "dense"
 
 
 def result_arrays(cfg, res):
@@ -192,7 +219,10 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world,
                                     device_id=torch.device("cuda", local_rank))
-    which = args.config or ("all" if world == 1 and not args.no_extras else "dense")
+    which = which_config(args, world)
+    # the sections of a --full run that --no-extras / --no-cpu-baseline leave out
+    extras_on = args.full and not args.no_extras
+    cpu_on = args.full and not args.no_cpu_baseline
     run_cfgs = list(CONFIGS) if which == "all" else [which]
     need_lex = any(c != "dense" for c in run_cfgs)
     need_graph = any(c.startswith("triple") for c in run_cfgs)
@@ -389,7 +419,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped.update(result_arrays(head_cfg, res))
     qps = args.steps * nq * n_replicas / elapsed   # every replica serves its own batch
-    roofline = probe_scan(primary)
+    roofline = probe_scan(primary) if args.full else None
     head_ids = res.ids.clone()
     def rank_breakdown(B, elapsed, roof):
         """Where this rank's share of a step goes: the scan alone, the exchange alone (the same
@@ -480,7 +510,7 @@ def main():
                         "in these figures -- they have never run on more than one GPU"}
 
     per_rank = strong = None
-    if world > 1:
+    if world > 1 and args.full:
         per_rank = rank_breakdown(B, elapsed, roofline)
         # The north star's layout -- the corpus cut into N document shards, ONE batch served by all
         # N GPUs, per-shard top-k merged through the all-gather -- is reported in every
@@ -514,6 +544,7 @@ def main():
                             "value": round(args.steps * nq / el2, 1), "unit": "queries/s",
                             "ms_per_step": round(1e3 * el2 / args.steps, 3), "rescued_queries": resc2,
                             "_ids": r2.ids}
+    if which == "all" and args.full:
         # per-stage launch times, each stage alone (HIP events)
         Ss, Is, _, _ = index.dense_search(qd, 100, sync=False)
         Sl, Il, _ = index.bm25_search(qtd, 50)
@@ -562,7 +593,7 @@ def main():
 
     # ---- the other shortlist flavours, measured in the same run for comparison ----
     extras = {}
-    if world == 1 and not args.no_extras and args.dim in (512, 768, 1024):
+    if world == 1 and extras_on and args.dim in (512, 768, 1024):
         for name in FLAVOURS:
             if name == primary:
                 continue
@@ -577,7 +608,7 @@ def main():
 
     # ---- single-query regime (N = 1): drop-in retrieve() latency; the scan at small batches ----
     latency = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras_on:
         latency = {"scan_small_batches": []}
         copy_bytes = n_local * args.dim * 2
         for b in (1, 32, 256):
@@ -645,7 +676,7 @@ def main():
     # ---- exactness of what was timed + CPU baseline (rank 0, N = 1) ----
     cpu = None
     check = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_on:
         from oracle import c_oracle as CO
         from oracle import thr_oracle as O
         torch.set_num_threads(os.cpu_count() or 1)
@@ -724,7 +755,7 @@ def main():
                  "triple_rerank": f"{args.docs}-doc triple-hybrid + late-interaction rerank (32x128x128, top-100)"}
         out = {
             "metric": "queries/sec (fused top-10)", "value": round(qps, 1), "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
             # same corpus at every N; with replicas the per-GPU work is fixed from doc_shards GPUs on
             "scaling": "weak" if n_replicas > 1 else "strong", "vs_baseline": None,
@@ -751,6 +782,7 @@ def main():
         }
         if cfg_out:
             out["configs"] = cfg_out
+        if chan:
             out["stages_alone"] = chan
         if extras:
             out["other_shortlists"] = extras

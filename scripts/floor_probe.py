@@ -2,7 +2,7 @@
 """A document-sharded dense step with every shard in this process, for a kernel trace:
     rocprofv3 --kernel-trace --stats -d D -o floor -- python3 scripts/floor_probe.py floor 8
     rocprofv3 --kernel-trace --stats -d D -o classic -- python3 scripts/floor_probe.py classic 8
-(bench.py --shard-proxy times the same two loops; here only one of them runs, so the per-kernel
+(bench.py --full --shard-proxy times the same two loops; here only one of them runs, so the per-kernel
 averages of the stats file belong to it.)"""
 import os
 import sys

@@ -1928,8 +1928,9 @@ def test_cli_config0_100_queries_match_the_oracle_pipeline(T):
 def test_bench_multi_rank_control_flow():
     """bench.py --gpus N end to end on one GPU (THR_BENCH_REHEARSAL: all ranks on cuda:0, gloo in
     place of RCCL): document sharding, replicas, exchange, merge and the single JSON line of rank 0,
-    which at N > 1 always carries the north star's layout (``config.strong_doc_sharded``: the corpus
-    cut into N document shards, one batch served by all N GPUs) next to whatever layout ran."""
+    which with --full at N > 1 always carries the north star's layout (``config.strong_doc_sharded``:
+    the corpus cut into N document shards, one batch served by all N GPUs) next to whatever layout
+    ran, and without it the headline alone."""
     import json
     import os
     import subprocess
@@ -1938,6 +1939,7 @@ def test_bench_multi_rank_control_flow():
     env = dict(os.environ, THR_BENCH_REHEARSAL="1")
     port = 29800 + os.getpid() % 1000
     for gpus, extra, label, pipeline in (
+            (2, None, "doc-shard x2", "dense"),    # a plain run: the headline's steps, no breakdown
             (2, [], "doc-shard x2", "dense"),
             (2, ["--doc-shards", "1"], "doc-shard x1 x 2 replicas", "dense"),
             (2, ["--config", "triple_rerank", "--token-docs", "20000"], "doc-shard x2", "triple_rerank"),
@@ -1947,7 +1949,7 @@ def test_bench_multi_rank_control_flow():
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
              "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--docs", "40000", "--queries", "192",
-             "--no-extras", "--no-cpu-baseline"] + extra,
+             ] + (["--full", "--no-extras", "--no-cpu-baseline"] + extra if extra is not None else []),
             env=env, cwd=root, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1957,10 +1959,15 @@ def test_bench_multi_rank_control_flow():
         assert rec["config"]["parallelism"].startswith(label) and rec["config"]["rescued_queries"] == 0
         replicas = "replicas" in label
         assert rec["scaling"] == ("weak" if replicas else "strong")
-        # where a rank's share of the step goes (scan / exchange / the rest)
-        assert set(rec["config"]["per_rank_ms"]) >= {"step_ms", "scan_ms", "exchange_ms", "fixed_ms"}
         assert rec["config"]["collective_backend"] == "gloo" and rec["config"]["world_size_seen"] == gpus
         assert rec["config"]["pipeline"] == pipeline
+        port += 1
+        if extra is None:
+            assert rec["full"] is False and rec["roofline"] is None
+            assert rec["config"]["per_rank_ms"] is None and rec["config"]["strong_doc_sharded"] is None
+            continue
+        # where a rank's share of the step goes (scan / exchange / the rest)
+        assert set(rec["config"]["per_rank_ms"]) >= {"step_ms", "scan_ms", "exchange_ms", "fixed_ms"}
         strong = rec["config"]["strong_doc_sharded"]
         assert strong["layout"] == f"doc-shard x{gpus}" and strong["scaling"] == "strong"
         assert strong["ms_per_step"] > 0 and strong["value"] > 0 and strong["same_run_as_the_headline"] == (not replicas)
@@ -1968,7 +1975,6 @@ def test_bench_multi_rank_control_flow():
         assert strong["per_rank_ms"]["shard_docs"] == 40000 // gpus
         if not replicas:
             assert strong["value"] == rec["value"] and strong["ms_per_step"] == rec["ms_per_step"]
-        port += 1
 
 
 def test_tool_layer_over_a_gpu_index_client(T, golden):
