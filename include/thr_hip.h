@@ -290,6 +290,51 @@ int thr_csr_compact(const int64_t *rowptr, int64_t rows, int64_t nnz, const int3
                     void *pay_out /* or NULL */, int64_t out_capacity, int64_t *nnz_out,
                     void *workspace, size_t workspace_bytes, thr_stream_t stream);
 
+/* f4  scoped queries: which rows a query may see.  Every reference RPC carries p_org_id
+ * (database/migrations/20260114_rag2_schema.sql:341-410), the RAG 2.0 ones p_collection, the RAG 1.0
+ * ones p_category / p_source_document (src/voice_agent/retrieval/hybrid_search.py:227-231), all applied
+ * in SQL BEFORE the LIMIT.  A scope is a conjunction of equalities over per-row int32 attribute
+ * columns; a batch names n_preds distinct ones.
+ *   h_cols [n_cols]: a HOST array of device pointers, each column int32 [n_docs];
+ *   preds int32 [n_preds, n_cols]: the value a row must hold per column, -1 = any value, a value
+ *      below -1 matches no row (a name the store has never seen);
+ *   rowptr int64 [n_preds + 1], rows int32 [cap]: per predicate its matching rows, ASCENDING.
+ *      rowptr is always complete (rowptr[n_preds] = all matches); of ``rows`` only the first
+ *      min(rowptr[n_preds], cap) entries are written, nothing behind them -- the caller compares
+ *      rowptr[n_preds] with cap before it uses the lists.  rows == NULL with cap == 0: counts only;
+ *   labels int32 [n_docs] + overlap int32 [1] (both or neither): the LOWEST predicate a row
+ *      matches, -2 for none; *overlap != 0 when some row matched two.  With disjoint predicates
+ *      ``labels`` is the doc_coll of thr_dense_topk* / thr_bm25_topk and a query's predicate index
+ *      its query_coll: the unchanged kernels then rank inside the scope.
+ * Rows without an embedding stay in the lists (the scorers skip them).  Three launches -- count per
+ * slice of consecutive rows, one scan, scatter -- no workgroup waits for another, no atomic, no
+ * host read-back, the same output every run; every destination index is checked against cap.
+ * ``workspace`` >= thr_scope_resolve_workspace_bytes(). */
+#define THR_SCOPE_MAX_COLS 8
+#define THR_SCOPE_MAX_PREDS 4096
+#define THR_SCOPE_MAX_QUERIES (1 << 20)
+size_t thr_scope_resolve_workspace_bytes(int64_t n_docs, int n_preds);
+int thr_scope_resolve(const int32_t *const *h_cols, int n_cols, int64_t n_docs, const int32_t *preds,
+                      int n_preds, int64_t *rowptr, int32_t *rows, int64_t cap, int32_t *labels,
+                      int32_t *overlap, void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
+/* Exact cosine top-k of every query over the ROW LIST of its scope (rowptr / rows of
+ * thr_scope_resolve, or any lists of local row indices; query_scope int32 [nq] in [0, n_scopes), any
+ * other value = no rows, n_scopes <= THR_SCOPE_MAX_PREDS): thr_dense_topk_exact's contract and bits --
+ * sequential float64 accumulation of the float32 products in dimension order, ||q|| the same way,
+ * dot / (qn * dn), rows with dnorm 0 absent, a zero query scores 0.0, (score desc, id asc), flags
+ * THR_FLAG_CERTIFIED | THR_FLAG_EXACT, padding (-inf, -1) -- at the cost of the scope's rows, not of
+ * n_docs.  Any dim that is a multiple of 4.  The queries of a scope share its rows: a work item is
+ * (8 queries of one scope, a slice of its row list); the queries are grouped by scope by a small
+ * kernel of this call (the caller passes them in any order).  Row indices outside [0, n_docs) and
+ * list positions at or behind rows_cap (the capacity ``rows`` was resolved with) are never read. */
+size_t thr_dense_topk_rows_workspace_bytes(int n_queries, int n_scopes, int k);
+int thr_dense_topk_rows(const float *docs, const double *dnorm, int64_t n_docs, int dim, int64_t id_base,
+                        const float *queries, int n_queries, int k, const int64_t *rowptr,
+                        const int32_t *rows, int64_t rows_cap, int n_scopes, const int32_t *query_scope,
+                        double *out_scores, int64_t *out_ids, int32_t *out_counts, uint32_t *out_flags,
+                        void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
 /* a3  lexical channel: Okapi BM25 (k1, b) top-k over a CSR inverted index,
  * OR semantics, float64 accumulation in query-term order.
  * Stands where SQL rag2_lexical_search (ts_rank_cd ... ORDER BY rank DESC

@@ -25,6 +25,9 @@ THR_BM25_MAX_QUERIES = 1 << 20
 THR_GRAPH_MAX_SEEDS = 16
 THR_RRF_MAX_PER_CHANNEL = 128
 THR_TOPK_MAX = 128
+THR_SCOPE_MAX_COLS = 8
+THR_SCOPE_MAX_PREDS = 4096
+THR_SCOPE_MAX_QUERIES = 1 << 20
 ABI_VERSION = 9
 
 _lib = None
@@ -70,6 +73,11 @@ _SIGNATURES = {
     "thr_csr_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "thr_csr_compact_workspace_bytes": (_sz, [_i64, _i64]),
     "thr_csr_compact": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "thr_scope_resolve_workspace_bytes": (_sz, [_i64, _i32]),
+    "thr_scope_resolve": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "thr_dense_topk_rows_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "thr_dense_topk_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_bm25_block_count": (_sz, [_i64]),
     "thr_bm25_bounds": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "thr_bm25_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -596,6 +604,80 @@ def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out
                                   _dev(pay_out, pay.dtype, "pay_out", 1) if nnz and pay is not None else None,
                                   cap, kept.data_ptr(), ws.data_ptr(), need, _stream()), "thr_csr_compact")
     return rowptr_out, ids_out, (pay_out if pay is not None else None), int(kept.item())
+
+
+# --------------------------------------------------------------------- f4
+def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = True, rows_out=None):
+    """thr_scope_resolve: ``cols`` a sequence of C int32 [n_docs] device columns, ``preds`` int32
+    [P, C] (-1 = any value, below -1 = no row).  -> (rowptr i64 [P + 1], rows i32 [cap], labels i32
+    [n_docs] or None, overlap i32 [1] or None).  ``cap`` (default n_docs; 0 = counts and labels only)
+    is the room for the lists: rowptr is complete either way and the caller compares rowptr[P] with
+    cap before it reads ``rows``.  ``rows_out``: an int32 buffer of at least cap entries to write the
+    lists into (returned as ``rows``; nothing behind cap is written).  No host read-back."""
+    cols = list(cols)
+    if not 1 <= len(cols) <= THR_SCOPE_MAX_COLS:
+        raise NativeError(f"scope_resolve: 1 .. {THR_SCOPE_MAX_COLS} attribute columns, got {len(cols)}")
+    n = cols[0].shape[0]
+    if any(c.dim() != 1 or c.shape[0] != n for c in cols):
+        raise NativeError("scope_resolve: every column is 1-d of the same length")
+    if preds.dim() != 2 or preds.shape[1] != len(cols):
+        raise NativeError(f"scope_resolve: preds must be [P, {len(cols)}]")
+    P = preds.shape[0]
+    if not 1 <= P <= THR_SCOPE_MAX_PREDS:
+        raise NativeError(f"scope_resolve: 1 .. {THR_SCOPE_MAX_PREDS} predicates per call, got {P}")
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+        raise NativeError("scope_resolve: cap is negative")
+    ptrs = (C.c_void_p * len(cols))(*[_dev(c, torch.int32, "column", 1) for c in cols])
+    pp = _dev(preds, torch.int32, "preds", 2)
+    dev = preds.device
+    rowptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    if rows_out is not None:
+        if rows_out.dim() != 1 or rows_out.shape[0] < cap:
+            raise NativeError("scope_resolve: rows_out holds fewer than cap entries")
+        _dev(rows_out, torch.int32, "rows_out", 1)
+    rows = torch.empty(cap, dtype=torch.int32, device=dev) if rows_out is None else rows_out
+    labels = torch.empty(n, dtype=torch.int32, device=dev) if want_labels else None
+    overlap = torch.empty(1, dtype=torch.int32, device=dev) if want_labels else None
+    need = int(load().thr_scope_resolve_workspace_bytes(n, P))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _check(load().thr_scope_resolve(ptrs, len(cols), n, pp, P, rowptr.data_ptr(), rows.data_ptr() if cap else None,
+                                    cap, labels.data_ptr() if want_labels else None,
+                                    overlap.data_ptr() if want_labels else None, ws.data_ptr(), need, _stream()),
+           "thr_scope_resolve")
+    return rowptr, rows, labels, overlap
+
+
+def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_base: int = 0):
+    """thr_dense_topk_rows: exact cosine top-k of every query over the row list of its scope
+    (rowptr i64 [P + 1] / rows i32 of scope_resolve, query_scope i32 [nq] in [0, P), anything else =
+    no rows).  -> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
+    pd = _dev(docs, torch.float32, "docs", 2)
+    n, d = docs.shape
+    pq = _dev(queries, torch.float32, "queries", 2)
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise NativeError(f"queries dim {queries.shape[1]} != docs dim {d}")
+    pn = _dev(dnorm, torch.float64, "dnorm", 1)
+    if dnorm.shape[0] != n:
+        raise NativeError("dnorm length != n_docs")
+    P = rowptr.shape[0] - 1
+    if not 1 <= P <= THR_SCOPE_MAX_PREDS:
+        raise NativeError(f"dense_topk_rows: 1 .. {THR_SCOPE_MAX_PREDS} scopes")
+    if query_scope.shape != (nq,):
+        raise NativeError("dense_topk_rows: query_scope has the wrong length")
+    if not 1 <= k <= THR_DENSE_MAX_K:
+        raise NativeError(f"dense_topk_rows: k must be 1 .. {THR_DENSE_MAX_K}")
+    prp = _dev(rowptr, torch.int64, "rowptr", 1)
+    prw = _dev(rows, torch.int32, "rows", 1)
+    pqs = _dev(query_scope, torch.int32, "query_scope", 1)
+    need = int(load().thr_dense_topk_rows_workspace_bytes(nq, P, k))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=docs.device)
+    S, I, cnt, flg = _alloc_out(nq, k, docs.device)
+    _check(load().thr_dense_topk_rows(pd, pn, n, d, int(id_base), pq, nq, k, prp, prw if rows.shape[0] else None,
+                                      rows.shape[0], P, pqs, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
+                                      flg.data_ptr(), ws.data_ptr(), need, _stream()), "thr_dense_topk_rows")
+    return S, I, cnt, flg
 
 
 # --------------------------------------------------------------------- a3

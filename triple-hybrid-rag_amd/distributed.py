@@ -134,6 +134,10 @@ def gather_rows(x: torch.Tensor, group=None) -> torch.Tensor:
     return out
 
 
+SCOPES_REFUSED = ("scopes= is not supported on a document-sharded index: scoped queries are resolved and routed "
+                  "per single-GPU GpuIndex (the shard-floor exchange takes collection ids only)")
+
+
 class ShardedIndex:
     """A GpuIndex holding this rank's document shard + the cross-rank merge."""
 
@@ -183,12 +187,14 @@ class ShardedIndex:
     def retrieve_batch(self, queries, query_terms=None, query_seeds=None, top_k: int = 10,
                        semantic_top_k: int = 100, lexical_top_k: int = 50, graph_top_k: int = 50,
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
-                       qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100) -> BatchResult:
+                       qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100, scopes=None) -> BatchResult:
         """Per channel: this shard's exact top-k -> all-gather -> merge; fusion on every rank (the
         merged lists are identical everywhere); rerank: every rank scores the fused
         candidates it OWNS with thr_maxsim (-inf for the others), a second all-gather of the
         [nq, rerank_top_k] float32 scores, then thr_rerank_order takes the maximum per candidate
         and applies the reference's stable sort."""
+        if scopes is not None:
+            raise N.NativeError(SCOPES_REFUSED)
         w = {"lexical": 0.7, "semantic": 0.8, "graph": 1.0}
         w.update(weights or {})
         L = self.local

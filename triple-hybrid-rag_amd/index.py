@@ -16,6 +16,8 @@ Layout in HBM (per shard of n documents, D dims):
               doclen float32 [n], idf float64 [V] (global), avgdl (global)
     graph     entity CSR (replicated) + entity->chunk mention CSR (this shard's chunks)
     tokens    float16 [n, T_d, 128] late-interaction token matrices
+    attributes int32 [n] per name (set_attributes; "collection" = doc_coll): what a scope tests
+               (index_scope.ScopedSearch: scope_plan, the row-list and the label routes)
 
 Changing a live index (reserve_rows, append_rows, delete_rows) and the record of which buffer holds
 which of these arrays is the base class, ``index_mutate.MutableIndex``.
@@ -33,6 +35,7 @@ import torch
 
 from . import _native as N
 from .index_mutate import MutableIndex, _refuse_when_unusable, _Storage
+from .index_scope import ScopedSearch, ScopePlan
 
 log = logging.getLogger(__name__)
 
@@ -56,7 +59,7 @@ class BatchResult:
     rescued: object = 0
 
 
-class GpuIndex(MutableIndex):
+class GpuIndex(ScopedSearch, MutableIndex):
     # what an index has before anything sets it (also: one made without __init__, as the host tests do)
     _side = None                # the second HIP stream of side_channels, made on first use
     _shortlist_of = None        # what the candidate lists in the dense workspace belong to (dense_shortlist)
@@ -80,6 +83,7 @@ class GpuIndex(MutableIndex):
         self.graph = None
         self.tokens = None
         self.doc_coll = None
+        self._attrs = {}
         self.tokens_packed = False
         # scratch memory of the searches, grown on demand and kept (_scratch)
         self._ws: Optional[torch.Tensor] = None
@@ -320,7 +324,8 @@ class GpuIndex(MutableIndex):
 
     @_refuse_when_unusable
     def dense_search(self, queries: torch.Tensor, k: int, kprime: Optional[int] = None,
-                     rescue: bool = True, sync: bool = True, collections=None, floor_exchange=None):
+                     rescue: bool = True, sync: bool = True, collections=None, floor_exchange=None,
+                     scopes=None, scope_rows_max: Optional[int] = None, _labels=None):
         """Exact cosine top-k -> (scores f64, ids i64, counts i32, n_rescued).  Queries the
         error-bound certificate cannot prove exact (massive ties / duplicates) are redone on the
         exhaustive float64 path, on the device (thr_dense_rescue: no host read-back).
@@ -333,7 +338,20 @@ class GpuIndex(MutableIndex):
         / thr_dense_finish_f16): rows that cannot be among the k best of ALL shards are not
         rescored, the returned list may hold fewer than k rows and is this shard's part of the
         global top-k (merge the shards' lists with thr_merge_topk).  Every shard must make the same
-        sequence of calls.  Used by the f16 scans only."""
+        sequence of calls.  Used by the f16 scans only.
+        scopes: per query a dict {attribute: value} / an int32 [nq, C] table over attribute_names()
+        (-1 = any), or a ScopePlan (scope_plan): only rows that satisfy the query's scope are ranked.
+        Resolving the scopes reads the P + 1 row pointers of the P distinct scopes back (the route
+        depends on the row counts); a ScopePlan made beforehand avoids that, for sync=False callers.
+        A scope of at most ``scope_rows_max`` rows (default SCOPE_ROWS_MAX; 0 = never) is ranked
+        over its row list (thr_dense_topk_rows), a wider one through this search with the scope
+        labels as doc_coll: the same bits either way.  Not together with ``collections``."""
+        if scopes is not None:
+            if collections is not None:
+                raise ValueError("dense_search: pass scopes= or collections=, not both")
+            if floor_exchange is not None:
+                raise N.NativeError("dense_search: scopes= is not supported on a document shard (floor_exchange)")
+            return self._dense_scoped(queries, k, kprime, rescue, sync, scopes, scope_rows_max)
         queries = self._t(queries, torch.float32)
         nq = queries.shape[0]
         self._shortlist_of = None     # (the workspace's candidate lists are about to be overwritten)
@@ -349,11 +367,11 @@ class GpuIndex(MutableIndex):
                     hi = min(nq, lo + step)
                     s_, i_, c_, r_ = self.dense_search(queries[lo:hi], k, kprime, rescue, sync,
                                                        None if coll is None else coll[lo:hi],
-                                                       floor_exchange)
+                                                       floor_exchange, _labels=_labels)
                     S[lo:hi], I[lo:hi], cnt[lo:hi] = s_, i_, c_
                     n_rescued = n_rescued + r_
                 return S, I, cnt, n_rescued
-        dc, qc = self._qcoll(collections, nq)
+        dc, qc = self._qcoll(collections, nq, _labels)
         if self.shortlist == "exact":
             S, I, cnt, _ = N.dense_topk_exact(self.docs, self.dnorm, queries, k, self.doc_base, dc, qc)
             return S, I, cnt, (0 if sync else torch.zeros(1, dtype=torch.int32, device=self.device))
@@ -437,25 +455,34 @@ class GpuIndex(MutableIndex):
         else:
             N.dense_scan_probe(self.docs, self.inv_norm, queries, self._ws)
 
-    def _qcoll(self, collections, nq: int):
+    def _qcoll(self, collections, nq: int, labels=None):
+        """(doc_coll, query_coll) of a filtered search; ``labels``: a scope plan's row labels in
+        the place of the collection ids."""
         if collections is None:
             return None, None
-        if self.doc_coll is None:
+        if self.doc_coll is None and labels is None:
             raise N.NativeError("collection filter without set_collections()")
         qc = self._t(collections, torch.int32)
         if qc.shape != (nq,):
             raise N.NativeError("collections: one id per query")
-        return self.doc_coll, qc
+        return (self.doc_coll if labels is None else labels), qc
 
     @_refuse_when_unusable
     def bm25_search(self, query_terms: torch.Tensor, k: int, collections=None,
-                    conjunctive: bool = False, prune: bool = True, dense_rows: bool = True):
+                    conjunctive: bool = False, prune: bool = True, dense_rows: bool = True, scopes=None,
+                    _labels=None):
         """collections: int32 [nq] collection id per query (-1 = unfiltered) or None.
+        scopes: as dense_search -- every scope, thin or wide, filters through the scope labels
+        (groups of disjoint scopes, one call per group); idf / avgdl stay the corpus'.
         One call takes at most N.THR_BM25_MAX_QUERIES (2^20) queries; a larger batch is refused."""
+        if scopes is not None:
+            if collections is not None:
+                raise ValueError("bm25_search: pass scopes= or collections=, not both")
+            return self._bm25_scoped(query_terms, k, scopes, conjunctive, prune, dense_rows)
         L = self.lex
         qt = self._t(query_terms, torch.int32)
         N.bm25_check_batch(qt.shape[0])
-        dc, qc = self._qcoll(collections, qt.shape[0])
+        dc, qc = self._qcoll(collections, qt.shape[0], _labels)
         need = N.bm25_workspace_bytes(qt.shape[0], qt.shape[1], k)
         # ONE lexical workspace per index, used from whichever stream the caller is on (the main
         # one, or the side stream of side_channels / GpuIndexClient's deferred RPC): the stream of
@@ -500,7 +527,8 @@ class GpuIndex(MutableIndex):
 
     # ------------------------------------------------------------ pipeline
     @_refuse_when_unusable
-    def side_channels(self, query_terms, lexical_top_k: int, query_seeds, graph_top_k: int, hops: int):
+    def side_channels(self, query_terms, lexical_top_k: int, query_seeds, graph_top_k: int, hops: int,
+                      scopes=None):
         """The lexical and graph channels of a batch on a second HIP stream, so that they run
         beside the dense channel instead of after it: they do not depend on it before the fusion,
         they are latency-bound (one workgroup per query, a few per CU), and the dense pipeline has
@@ -513,7 +541,7 @@ class GpuIndex(MutableIndex):
         if not (want_lex or want_gra):
             return None, None, (lambda: None)
         if os.environ.get("THR_SIDE_STREAM") == "0" or self.device.type != "cuda":
-            lex = self.bm25_search(query_terms, lexical_top_k) if want_lex else None
+            lex = self.bm25_search(query_terms, lexical_top_k, scopes=scopes) if want_lex else None
             gra = self.graph_search(query_seeds, graph_top_k, hops) if want_gra else None
             return lex, gra, (lambda: None)
         self.side_stream()
@@ -523,7 +551,7 @@ class GpuIndex(MutableIndex):
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(self._side)
         with torch.cuda.stream(self._side):
-            lex = self.bm25_search(query_terms, lexical_top_k) if want_lex else None
+            lex = self.bm25_search(query_terms, lexical_top_k, scopes=scopes) if want_lex else None
             gra = self.graph_search(query_seeds, graph_top_k, hops) if want_gra else None
         for res in (lex, gra):
             if res is not None:
@@ -549,14 +577,20 @@ class GpuIndex(MutableIndex):
                        semantic_top_k: int = 100, lexical_top_k: int = 50, graph_top_k: int = 50,
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
                        qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100,
-                       rescue: bool = True) -> BatchResult:
+                       rescue: bool = True, scopes=None, scope_rows_max: Optional[int] = None) -> BatchResult:
         """plan.semantic/lexical/graph_top_k = 100/50/50 and weights 0.7/0.8/1.0 are the
-        reference's QueryPlan defaults (src/voice_agent/rag2/query_planner.py:23-50)."""
+        reference's QueryPlan defaults (src/voice_agent/rag2/query_planner.py:23-50).
+        scopes: as dense_search, resolved once for the batch; the dense and the lexical channel
+        rank inside each query's scope.  The graph channel takes no filter (neither does the
+        reference's, retrieval.py:316-356): an org's entities mention only that org's chunks."""
+        if scopes is not None:
+            scopes = self.scope_plan(scopes, queries.shape[0])
         w = {"lexical": 0.7, "semantic": 0.8, "graph": 1.0}
         w.update(weights or {})
         ch = {}
-        lex, gra, join = self.side_channels(query_terms, lexical_top_k, query_seeds, graph_top_k, hops)
-        Ss, Is, Cs, nres = self.dense_search(queries, semantic_top_k, rescue=rescue, sync=False)
+        lex, gra, join = self.side_channels(query_terms, lexical_top_k, query_seeds, graph_top_k, hops, scopes)
+        Ss, Is, Cs, nres = self.dense_search(queries, semantic_top_k, rescue=rescue, sync=False, scopes=scopes,
+                                             scope_rows_max=scope_rows_max)
         ch["semantic"] = (Ss, Is, Cs)
         join()
         Il = Ig = None

@@ -52,6 +52,7 @@ class HostIndex:
     tokens: Optional[np.ndarray] = None   # f16 [n, T, 128]
     store: Optional[CorpusStore] = None
     derived: Optional[Dict[str, Any]] = None   # GpuIndex.export_derived(): saved with the index, reused by to_gpu()
+    attributes: Optional[Dict[str, np.ndarray]] = None   # per-row int32 columns a scope tests (GpuIndex.set_attributes)
 
     def to_gpu(self, doc_base: int = 0):
         from .index import GpuIndex
@@ -64,6 +65,8 @@ class HostIndex:
                           self.men_conf)
         if self.tokens is not None:
             idx.set_tokens(self.tokens)
+        if self.attributes:
+            idx.set_attributes(self.attributes)
         return idx
 
 
@@ -289,6 +292,9 @@ def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
                                  "the deleted rows' with the remap delete_rows returned) before save()")
         elif stale or _mutated_since_sync(hi, g):
             hi.tokens = g.tokens.cpu().numpy()
+    names = g.attribute_names() if hasattr(g, "attribute_names") else []
+    if names:
+        hi.attributes = {name: g.attribute(name).cpu().numpy() for name in names}
     hi._synced = (weakref.ref(g), getattr(g, "_mutations", 0))
     hi.derived = None   # (computed for the old rows; save(hi, path, gpu_index) exports the current ones)
     return hi
@@ -311,6 +317,14 @@ def save(hi: HostIndex, path: str, gpu_index=None) -> None:
         if arr is not None:
             np.save(os.path.join(path, name + ".npy"), arr, allow_pickle=False)
     meta: Dict[str, Any] = {"avgdl": hi.avgdl, "format": 2}
+    if hi.attributes:    # (optional: a directory without the key loads as before)
+        names = sorted(hi.attributes)
+        for i, name in enumerate(names):
+            col = np.ascontiguousarray(hi.attributes[name], dtype=np.int32)
+            if col.shape != (len(hi.docs),):
+                raise ValueError(f"attribute {name!r}: one int32 per row ({len(hi.docs)}), got shape {col.shape}")
+            np.save(os.path.join(path, f"attr_{i}.npy"), col, allow_pickle=False)
+        meta["attributes"] = names
     derived = gpu_index.export_derived() if gpu_index is not None else hi.derived
     for name in _DERIVED_ARRAYS:   # a directory saved before may hold derived arrays this index does not have
         fp = os.path.join(path, "derived_" + name + ".npy")
@@ -373,4 +387,5 @@ def load(path: str, mmap: bool = True) -> HostIndex:
                                 collections=cols.get("collections"), vocab=vocab,
                                 entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"],
                                 content_hashes=cols.get("content_hashes"))
-    return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, **arrays)
+    attributes = {name: arr(f"attr_{i}") for i, name in enumerate(meta.get("attributes", []))} or None
+    return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, attributes=attributes, **arrays)

@@ -178,12 +178,16 @@ class MutableIndex:
         """The per-document arrays the index has (leading dimension = rows; docs16: whole tiles)."""
         arrs = {name: getattr(self, name) for name in _Storage.ROWS}
         arrs["doclen"] = self.lex["doclen"] if self.lex is not None else None
+        for name, col in (getattr(self, "_attrs", None) or {}).items():    # attribute columns (set_attributes)
+            arrs["attr:" + name] = col
         return {k: v for k, v in arrs.items() if v is not None}
 
     def _install_rows(self, rows: Dict[str, Tuple[torch.Tensor, torch.Tensor]]) -> None:
         for name, (_, view) in rows.items():
             if name == "doclen":
                 self.lex["doclen"] = view
+            elif name.startswith("attr:"):
+                self._attrs = dict(self._attrs, **{name[5:]: view})
             else:
                 setattr(self, name, view)
         self._store.held.update(rows)
@@ -260,12 +264,28 @@ class MutableIndex:
             raise N.NativeError(f"{who}: {name} must be an integer array, got {t.dtype}")
         return t
 
-    def _validate_append(self, docs, lex, collections, tokens, mentions, n_rows) -> dict:
+    def _check_attributes_part(self, attributes, m: int):
+        have = set(getattr(self, "_attrs", None) or {})
+        if set(attributes) != have:
+            raise N.NativeError(f"append_rows: attributes must hold exactly the index's columns {sorted(have)}, "
+                                f"got {sorted(attributes)}")
+        out = {}
+        for name, col in attributes.items():
+            c = self._host_or_device(col, f"attributes[{name!r}]", True)
+            if tuple(c.shape) != (m,):
+                raise N.NativeError(f"append_rows: attributes[{name!r}]: one value per appended row")
+            out[name] = c
+        return out
+
+    def _validate_append(self, docs, lex, collections, tokens, mentions, n_rows, attributes=None) -> dict:
         """Everything about an append that can be refused before any device work: which parts are
         required (exactly the channels the index has), shapes, dtypes, id ranges.  -> the parts as
         tensors where the caller left them + the batch size."""
         m, docs = self._check_dense_part(docs, n_rows)
         out = dict(m=m, docs=docs)
+        attributes = dict(attributes or {})
+        if "collection" in attributes and collections is None:
+            collections = attributes.pop("collection")
         for name, have, part, check, required, absent in (
                 ("lex", self.lex, lex, self._check_lex_part,
                  "this index has a lexical channel: lex=(doc, term, tf, n_vocab) is required",
@@ -283,6 +303,9 @@ class MutableIndex:
             if (have is None) != (part is None):
                 raise N.NativeError("append_rows: " + (required if part is None else absent))
             out[name] = None if part is None else check(part, m)
+        if (getattr(self, "_attrs", None) or {}) and not attributes:
+            raise N.NativeError("append_rows: this index has attribute columns: attributes={name: [m]} is required")
+        out["attributes"] = self._check_attributes_part(attributes, m)
         return out
 
     def _check_collections_part(self, collections, m: int):
@@ -403,7 +426,7 @@ class MutableIndex:
 
     @_refuse_when_unusable
     def append_rows(self, docs, lex=None, collections=None, tokens=None, mentions=None,
-                    n_rows: Optional[int] = None) -> range:
+                    n_rows: Optional[int] = None, attributes=None) -> range:
         """Append m chunks to the live index -> the range of their LOCAL doc ids (add doc_base for
         the global ones).  Afterwards every device array is, to the bit, what a fresh build over
         all the rows would hold, and the next search sees the rows.
@@ -414,6 +437,8 @@ class MutableIndex:
                       (n_vocab >= the old one); a negative term is a token outside the
                       vocabulary (counts toward its chunk's length only);
           collections int32 [m];   tokens float16 [m, d_tokens, tok_dim];
+          attributes  {name: int32 [m]} for exactly the columns set_attributes gave the index
+                      ("collection" may come here instead of ``collections``);
           mentions    (entity, chunk, conf or None): entity ids of EXISTING entities, chunk ids
                       local to the batch, in any order (stored by entity, then chunk, stably: the
                       order index_build.build_graph gives the same rows).
@@ -421,7 +446,7 @@ class MutableIndex:
         before the first change and the new arrays are swapped in last (_commit): a failure leaves
         the index answering over the old rows.  Synchronises the main and the side stream (not a
         query-path call).  Not supported on a document shard of a sharded index."""
-        P = self._validate_append(docs, lex, collections, tokens, mentions, n_rows)
+        P = self._validate_append(docs, lex, collections, tokens, mentions, n_rows, attributes)
         m, n_old = P["m"], self.n_docs
         if m == 0:
             return range(n_old, n_old)
@@ -439,6 +464,8 @@ class MutableIndex:
             self._sync_streams()
         if P["collections"] is not None:
             self._extend(new, "doc_coll", self.doc_coll, self._t(P["collections"], torch.int32), n_old)
+        for name, col in P["attributes"].items():
+            self._extend(new, "attr:" + name, self._attrs[name], self._t(col, torch.int32), n_old)
         if P["tokens"] is not None:
             tok = self._t(P["tokens"], torch.float16)
             self._extend(new, "tokens", self.tokens, N.maxsim_pack(tok) if self.tokens_packed else tok,
