@@ -294,7 +294,8 @@ int thr_csr_compact(const int64_t *rowptr, int64_t rows, int64_t nnz, const int3
  * (database/migrations/20260114_rag2_schema.sql:341-410), the RAG 2.0 ones p_collection, the RAG 1.0
  * ones p_category / p_source_document (src/voice_agent/retrieval/hybrid_search.py:227-231), all applied
  * in SQL BEFORE the LIMIT.  A scope is a conjunction of equalities over per-row int32 attribute
- * columns; a batch names n_preds distinct ones.
+ * columns; a batch names n_preds distinct ones.  The dense, lexical and graph scorers all filter by
+ * the labels written here (doc_coll / query_coll; the graph channel: thr_graph_topk_scoped, a4).
  *   h_cols [n_cols]: a HOST array of device pointers, each column int32 [n_docs];
  *   preds int32 [n_preds, n_cols]: the value a row must hold per column, -1 = any value, a value
  *      below -1 matches no row (a name the store has never seen);
@@ -444,6 +445,29 @@ int thr_graph_topk(const int64_t *ent_rowptr, const int32_t *ent_col, int64_t n_
                    int n_queries, int max_seeds, int hops, int k, double *out_scores,
                    int64_t *out_ids, int32_t *out_counts, uint32_t *out_flags, void *workspace,
                    size_t workspace_bytes, thr_stream_t stream);
+/* thr_graph_topk inside a scope.  The reference's graph search filters every entity and relation
+ * query by tenant (.eq("org_id", org_id), src/voice_agent/rag2/graph_search.py:154-230): a tenant's
+ * graph list holds that tenant's chunks only.  doc_label int32 [n_chunks] (one label per LOCAL
+ * chunk) and query_label int32 [n_queries] (negative = no filter) are the doc_coll / query_coll
+ * convention of thr_dense_topk* / thr_bm25_topk, the labels thr_scope_resolve writes: chunk c is in
+ * the result of query q only if query_label[q] < 0 or doc_label[c] == query_label[q].  The walk is
+ * not filtered (entities carry no attributes: BFS distances are thr_graph_topk's), and an in-scope
+ * chunk's score has thr_graph_topk's bits (its mentions in (entity asc, mention) order, float64).
+ * Same workspace (thr_graph_workspace_bytes), tiers, flags, padding and order.  In the two on-chip
+ * tiers only mentions that are in the shard AND in the scope take a contribution slot (16 lanes of
+ * a wave per reached entity count and compact them), so the contribution capacities bound the scope's
+ * mentions, not the graph's; the entity capacities are unchanged.  The third tier skips the chunks
+ * whose label does not match.  Null doc_label / query_label: THR_ERR_INVALID. */
+int thr_graph_topk_scoped(const int64_t *ent_rowptr, const int32_t *ent_col, int64_t n_entities,
+                          const int64_t *men_rowptr, const int32_t *men_chunk, const float *men_conf,
+                          const int64_t *tmen_rowptr /* [n_chunks+1] or NULL */,
+                          const int32_t *tmen_ent, const float *tmen_conf,
+                          int64_t chunk_base, int64_t n_chunks,
+                          const int32_t *doc_label /* [n_chunks] */,
+                          const int32_t *query_label /* [n_queries] */, const int32_t *query_seeds,
+                          int n_queries, int max_seeds, int hops, int k, double *out_scores,
+                          int64_t *out_ids, int32_t *out_counts, uint32_t *out_flags, void *workspace,
+                          size_t workspace_bytes, thr_stream_t stream);
 
 /* a5+a6  candidate merge + weighted Reciprocal Rank Fusion, bit-for-bit the
  * float64 arithmetic and stable ordering of RAG2Retriever._retrieve_candidates

@@ -88,6 +88,8 @@ _SIGNATURES = {
     "thr_graph_workspace_bytes": (_sz, [_i32, _i64]),
     "thr_graph_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32,
                               _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "thr_graph_topk_scoped": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                     _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_rrf_fuse": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
                             _vp, _vp, _vp, _vp, _vp]),
     "thr_rrf_fuse_standalone": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
@@ -817,6 +819,25 @@ def graph_topk(ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, query_seeds
                workspace: Optional[torch.Tensor] = None):
     """-> (scores, ids, counts, flags).  ``transposed`` = (tmen_rowptr i64 [n_chunks+1], tmen_ent
     i32, tmen_conf f32) from ``graph_transpose_mentions`` enables the capacity-free third tier."""
+    return _graph_call("thr_graph_topk", ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, query_seeds,
+                       hops, k, chunk_base, n_chunks, transposed, workspace, None)
+
+
+def graph_topk_scoped(ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, query_seeds, hops: int,
+                      k: int, chunk_base: int, n_chunks: int, doc_label, query_label, transposed=None,
+                      workspace: Optional[torch.Tensor] = None):
+    """thr_graph_topk_scoped: graph_topk over the chunks of each query's scope -> (scores, ids,
+    counts, flags).  doc_label i32 [n_chunks] (scope_resolve's labels, or any per-chunk labelling),
+    query_label i32 [nq] (negative = no filter): chunk c counts for query q only if its label is
+    the query's.  Both are required: an unfiltered search is graph_topk."""
+    if doc_label is None or query_label is None:
+        raise NativeError("graph_topk_scoped: doc_label and query_label are required (graph_topk is the unfiltered call)")
+    return _graph_call("thr_graph_topk_scoped", ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf,
+                       query_seeds, hops, k, chunk_base, n_chunks, transposed, workspace, (doc_label, query_label))
+
+
+def _graph_call(entry, ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, query_seeds, hops, k, chunk_base,
+                n_chunks, transposed, workspace, labels):
     per = _dev(ent_rowptr, torch.int64, "ent_rowptr", 1)
     pec = _dev(ent_col, torch.int32, "ent_col", 1)
     pmr = _dev(men_rowptr, torch.int64, "men_rowptr", 1)
@@ -836,15 +857,21 @@ def graph_topk(ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, query_seeds
     nq, ms = query_seeds.shape
     if ms > THR_GRAPH_MAX_SEEDS or k > THR_TOPK_MAX:
         raise NativeError("graph: too many seeds per query or k too large")
+    scoped = ()
+    if labels is not None:
+        doc_label, query_label = labels
+        scoped = (_dev(doc_label, torch.int32, "doc_label", 1), _dev(query_label, torch.int32, "query_label", 1))
+        if doc_label.shape[0] != n_chunks or query_label.shape[0] != nq:
+            raise NativeError("graph: doc_label holds one label per chunk of the shard, query_label one per query")
     need = int(load().thr_graph_workspace_bytes(nq, n_ent if transposed is not None else 0))
     ws = workspace
     if ws is None or ws.numel() * ws.element_size() < need:
         ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ent_rowptr.device)
     S, I, cnt, flg = _alloc_out(nq, k, ent_rowptr.device)
-    _check(load().thr_graph_topk(per, pec, n_ent, pmr, pmc, pmw, ptr, pte, ptw, chunk_base,
-                                 n_chunks, pqs, nq, ms, hops, k, S.data_ptr(), I.data_ptr(),
-                                 cnt.data_ptr(), flg.data_ptr(), ws.data_ptr(), need, _stream()),
-           "thr_graph_topk")
+    _check(getattr(load(), entry)(per, pec, n_ent, pmr, pmc, pmw, ptr, pte, ptw, chunk_base, n_chunks, *scoped,
+                                  pqs, nq, ms, hops, k, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
+                                  flg.data_ptr(), ws.data_ptr(), need, _stream()),
+           entry)
     return S, I, cnt, flg
 
 

@@ -35,6 +35,10 @@ clear a tenant this way, tests/test_rag2_e2e.py:276-293):
 
 A delete removes the chunks from the live index (``GpuIndex.delete_rows``: the next ``retrieve()``
 no longer sees them) and from the store; an update is a delete followed by an insert.
+
+One client serves one tenant (``org_id=``) or, over a store with a per-row ``org_ids`` column and no
+``org_id`` of its own, all of them: ``p_org_id`` then selects the rows a call ranks (scoped queries,
+the graph channel included -- the reference's WHERE org_id = $1 and .eq("org_id", org_id)).
 """
 from __future__ import annotations
 
@@ -73,6 +77,7 @@ class CorpusStore:
     entity_names: List[str] = field(default_factory=list)
     doc_base: int = 0
     content_hashes: Optional[List[Optional[str]]] = None            # the dedup key of the ingest (nullable)
+    org_ids: Optional[List[Optional[str]]] = None                   # per-row tenant (rows' ``org_id``): one store, many orgs
 
     def __post_init__(self):
         self._row_of = {cid: i for i, cid in enumerate(self.child_ids)}
@@ -108,6 +113,9 @@ class CorpusStore:
             raise ValueError("the store has no collection column: rows cannot carry a collection")
         if self.collections is not None and not isinstance(self.collections, list):
             self.collections = list(self.collections)
+        # (a store without the column ignores the rows' org_id: the single-tenant ingest sends it too)
+        if self.org_ids is not None and not isinstance(self.org_ids, list):
+            self.org_ids = list(self.org_ids)
         if self.content_hashes is None:
             self.content_hashes = [None] * n0
         elif not isinstance(self.content_hashes, list):
@@ -121,6 +129,8 @@ class CorpusStore:
             self.modalities.append(r.get("modality", "text"))
             if self.collections is not None:
                 self.collections.append(r.get("collection"))
+            if self.org_ids is not None:
+                self.org_ids.append(r.get("org_id"))
             self.content_hashes.append(r.get("content_hash"))
             self._row_of[r["id"]] = n0 + i
             if tokenizer is not None:
@@ -147,7 +157,7 @@ class CorpusStore:
         dead = set(gone)
         # (a loaded store keeps its columns as read-only blobs: they become lists here, as in append)
         names = ["child_ids", "parent_ids", "document_ids", "texts", "pages", "modalities"]
-        names += [c for c in ("collections", "content_hashes") if getattr(self, c) is not None]
+        names += [c for c in ("collections", "content_hashes", "org_ids") if getattr(self, c) is not None]
         lost = {self.content_hashes[i] for i in gone} if self.content_hashes is not None else set()
         for name in names:
             col = getattr(self, name)
@@ -253,7 +263,7 @@ class LazyRows(collections.abc.Sequence):
 
 
 class _TableQuery:
-    def __init__(self, fetch, by_hash=None, insert=None, org_id=None, delete=None):
+    def __init__(self, fetch, by_hash=None, insert=None, org_id=None, delete=None, tenants=False):
         self._fetch = fetch
         self._by_hash = by_hash       # content_hash lookup (rag_child_chunks only)
         self._insert = insert         # row writer (the two chunk tables)
@@ -265,6 +275,8 @@ class _TableQuery:
         self._rows: Optional[List[Dict[str, Any]]] = None
         self._limit: Optional[int] = None
         self._foreign = False         # eq("org_id", another tenant): nothing of this index matches
+        self._tenants = tenants       # a multi-tenant client: eq("org_id", x) is a row filter like any other
+        self._org_eq: Optional[List[Any]] = None
 
     def select(self, *_cols, **_kw):
         return self
@@ -272,6 +284,11 @@ class _TableQuery:
     def eq(self, *a, **_kw):
         if len(a) == 2 and a[0] == "org_id" and self._org_id is not None and a[1] not in (None, self._org_id):
             self._foreign = True
+        if self._tenants and len(a) == 2 and a[0] == "org_id":
+            self._org_eq = [a[1]]
+            if self._filters is not None:
+                self._filters.append(("org_id", [a[1]]))
+            return self
         if self._filters is not None and len(a) == 2 and a[0] != "org_id":
             self._filters.append((a[0], [a[1]]))
         return self
@@ -283,7 +300,7 @@ class _TableQuery:
         empty the index)."""
         if self._delete is None:
             raise ValueError("this table is read-only in the GPU index")
-        self._filters = []
+        self._filters = [] if self._org_eq is None else [("org_id", list(self._org_eq))]
         return self
 
     def insert(self, rows):
@@ -315,10 +332,11 @@ class _TableQuery:
             return _Reply([] if self._foreign else self._delete(self._filters))
         if self._rows is not None:
             return _Reply(self._insert(self._rows))
+        org = {} if self._org_eq is None else {"org": self._org_eq[0]}
         if self._hashes is not None:
-            rows = [] if self._foreign else self._by_hash(self._hashes)
+            rows = [] if self._foreign else self._by_hash(self._hashes, **org)
         else:
-            rows = self._fetch(self._ids or [])
+            rows = self._fetch(self._ids or [], **org)
         return _Reply(rows[: self._limit] if self._limit is not None else rows)
 
 
@@ -327,6 +345,7 @@ class GpuIndexClient:
 
     defers_readback = True   # rag2_lexical_search honours ``_defer`` (see _lexical)
     sets_collections = True  # derives the index's per-doc collection ids from the store's rows
+    multi_tenant = False     # set by __init__: no org_id of its own over a store with an org_ids column
 
     def __init__(self, index: GpuIndex, store: CorpusStore, org_id: Optional[str] = None,
                  token_embedder: Any = None, lexical_and: bool = False,
@@ -341,7 +360,14 @@ class GpuIndexClient:
         ``image_rows[j]``.
         collection_names: fixes the collection name -> id mapping (sorted names of the WHOLE
         corpus): the shards of a document-sharded index must agree on it (sharded_client.py);
-        default: the names this store's rows carry."""
+        default: the names this store's rows carry.
+        org_id: the one tenant this client serves -- any other ``p_org_id`` is answered with no rows.
+        None over a store that has an ``org_ids`` column makes the client MULTI-TENANT: one index,
+        one store, every tenant.  The index gets an ``"org"`` attribute column (the ids of the sorted
+        distinct names; one it already has is checked against the store's column), each RPC and
+        ``graph_chunks`` rank inside {"org": p_org_id} (+ "collection") through the index's scopes,
+        a missing or unknown org gets no rows, ``table().eq("org_id", x)`` filters rows, and an
+        insert needs ``org_id`` on every row."""
         self.lexical_and = bool(lexical_and)
         self.image_index = image_index
         self.image_rows = None if image_rows is None else [int(r) for r in image_rows]
@@ -364,6 +390,44 @@ class GpuIndexClient:
             if index.doc_coll is None and self.sets_collections:
                 index.set_collections(np.array([self._coll_id.get(c, -2) if c is not None else -2
                                                 for c in store.collections], dtype=np.int32))
+        # one client, many tenants: no org_id of its own over a store whose rows name theirs.  Every RPC
+        # then ranks inside {"org": p_org_id} (GpuIndex scopes), the graph channel included.
+        self.multi_tenant = org_id is None and getattr(store, "org_ids", None) is not None
+        self._org_code: Dict[Any, int] = {}
+        self._plans: Dict[Any, Any] = {}    # (index, org, collection) -> the one-query ScopePlan
+        if self.multi_tenant:
+            if "org" in index.attribute_names():
+                # a column that came with the index (a saved one: ids given at inserts never move, so they
+                # need not be the sorted order any more): the numbering is read off the rows, once
+                for o, c in zip(store.org_ids, index.attribute("org").cpu().tolist()):
+                    if c != (-1 if o is None else self._org_code.setdefault(o, c)):
+                        raise ValueError("the index's \"org\" attribute does not follow the store's org_ids column")
+                if len(set(self._org_code.values())) != len(self._org_code) or min(self._org_code.values(), default=0) < 0:
+                    raise ValueError("the index's \"org\" attribute gives two orgs of the store the same id, or one none")
+            else:
+                self._org_code = {o: i for i, o in enumerate(sorted({o for o in store.org_ids if o is not None}))}
+            for ix, rows in ((index, None), (image_index, self.image_rows)):
+                if ix is not None and "org" not in ix.attribute_names():
+                    orgs = store.org_ids if rows is None else [store.org_ids[r] for r in rows]
+                    ix.set_attributes({"org": np.array([self._org_code.get(o, -1) for o in orgs], dtype=np.int32)})
+
+    def _scope(self, org, collection=None, index=None):
+        """Multi-tenant: the ScopePlan of a one-query call inside ``org`` (and ``collection``), made
+        once per (org, collection) and kept until the index changes -- a request then resolves no
+        scope and reads no row pointers back.  None: no row can match (a missing org, or one the
+        store has never seen: what ``WHERE org_id = $1`` gives)."""
+        code = self._org_code.get(org) if org is not None else None
+        if code is None:
+            return None
+        index = self.index if index is None else index
+        key = (id(index), org, collection)
+        plan = self._plans.get(key)
+        if plan is None or not index.scope_plan_current(plan, 1):
+            scope = {"org": code}
+            if collection is not None and index.doc_coll is not None:
+                scope["collection"] = self._coll_id.get(collection)     # (None: a name no row carries)
+            plan = self._plans[key] = index.scope_plan([scope], 1)
+        return plan
 
     def _qcoll(self, collection):
         """int32 [1] collection id of a one-query call, None when unfiltered; a name no row
@@ -376,34 +440,48 @@ class GpuIndexClient:
     def rpc(self, name: str, params: Dict[str, Any]):
         if self.org_id is not None and params.get("p_org_id") not in (None, self.org_id):
             return _Reply([])  # data isolation: another tenant's index
+        # multi-tenant: p_org_id is the scope of the call (otherwise it was checked above, and the
+        # channel methods are called as they always were: subclasses override them)
+        org = {"org": params.get("p_org_id")} if self.multi_tenant else {}
         if name == "rag2_semantic_search":
             return _Reply(self._semantic(params["p_embedding"], int(params.get("p_limit", 100)),
-                                         params.get("p_collection")))
+                                         params.get("p_collection"), **org))
         if name == "rag2_lexical_search":
             return _Reply(self._lexical(params["p_query"], int(params.get("p_limit", 50)),
-                                        params.get("p_collection"), defer=bool(params.get("_defer"))))
+                                        params.get("p_collection"), defer=bool(params.get("_defer")), **org))
         if name == "rag2_hybrid_rrf_search":
             return _Reply(self._hybrid_rrf(params))
         if name == "kb_chunks_vector_search":   # legacy RAG 1.0 (20260113_halfvec_4000.sql:70-105)
-            rows = self._semantic(params["p_embedding"], int(params.get("p_limit", 50)), None)
+            rows = self._semantic(params["p_embedding"], int(params.get("p_limit", 50)), None, **org)
             return _Reply([self._legacy_row(r, "similarity") for r in rows])
         if name == "kb_chunks_fts_pt":          # legacy RAG 1.0 (20260113_add_kb_chunks.sql:152-190)
-            rows = self._lexical(params["p_query"], int(params.get("p_limit", 50)), None)
+            rows = self._lexical(params["p_query"], int(params.get("p_limit", 50)), None, **org)
             return _Reply([self._legacy_row(r, "rank") for r in rows])
         if name == "kb_chunks_image_search":    # legacy RAG 1.0 (20260113_add_kb_chunks.sql:236-268)
-            return _Reply(self._image(params["p_image_embedding"], int(params.get("p_limit", 10))))
+            return _Reply(self._image(params["p_image_embedding"], int(params.get("p_limit", 10)), **org))
         raise ValueError(f"unknown RPC {name!r}")
 
-    def _image(self, embedding, limit: int) -> List[Dict[str, Any]]:
+    def _scoped(self, org, collection=None, index=None) -> Optional[dict]:
+        """The filter arguments of a one-query search: ``collections=`` as always, or, multi-tenant,
+        ``scopes=`` the cached plan of (org, collection); None = answer no rows."""
+        if not self.multi_tenant:
+            return {} if index is not None else {"collections": self._qcoll(collection)}
+        plan = self._scope(org, collection, index)
+        return None if plan is None else {"scopes": plan}
+
+    def _image(self, embedding, limit: int, org=None) -> List[Dict[str, Any]]:
         """Cosine top-``limit`` over the image vectors (exact; the SQL orders by ``<=>``)."""
         if self.image_index is None:
+            return []
+        within = self._scoped(org, None, self.image_index)
+        if within is None:
             return []
         q = torch.tensor([list(map(float, embedding))], dtype=torch.float32,
                          device=self.image_index.device)
         if q.shape[1] != self.image_index.dim:
             raise ValueError(f"image embedding has {q.shape[1]} dims, index has {self.image_index.dim}")
         k = min(N.THR_DENSE_MAX_K, limit)
-        S, I, cnt, _ = self.image_index.dense_search(q, k)
+        S, I, cnt, _ = self.image_index.dense_search(q, k, **within)
         out = []
         for j, sc in zip(I[0].tolist()[:int(cnt[0])], S[0].tolist()):
             row = self.store.result_row(self.image_rows[int(j) - self.image_index.doc_base])
@@ -429,8 +507,9 @@ class GpuIndexClient:
         limit = int(params.get("p_limit", 50))
         coll = params.get("p_collection")
         wide = min(N.THR_RRF_MAX_PER_CHANNEL, 2 * limit)
-        lex = self._lexical(params["p_query"], wide, coll)
-        sem = self._semantic(params["p_embedding"], wide, coll)
+        org = {"org": params.get("p_org_id")} if self.multi_tenant else {}
+        lex = self._lexical(params["p_query"], wide, coll, **org)
+        sem = self._semantic(params["p_embedding"], wide, coll, **org)
 
         def ids(rows):
             t = torch.full((1, max(len(rows), 1)), -1, dtype=torch.int64, device=self.index.device)
@@ -498,12 +577,15 @@ class GpuIndexClient:
                         "page": pg[i], "modality": md[i], score_key: sc})
         return out
 
-    def _semantic(self, embedding, limit: int, collection):
+    def _semantic(self, embedding, limit: int, collection, org=None):
         if len(embedding) != self.index.dim:
             raise ValueError(f"embedding has {len(embedding)} dims, index has {self.index.dim}")
+        within = self._scoped(org, collection)
+        if within is None:
+            return []
         q = self._upload(embedding, torch.float32, self.index.device)
         k = min(N.THR_DENSE_MAX_K, limit)
-        S, I, _, _ = self.index.dense_search(q, k, collections=self._qcoll(collection), sync=False)
+        S, I, _, _ = self.index.dense_search(q, k, sync=False, **within)
         scores, ids = self._download(S, I)
         return self._rows(ids, scores, len(ids), "similarity", limit)
 
@@ -527,7 +609,7 @@ class GpuIndexClient:
             return None
         return terms[: N.THR_BM25_MAX_TERMS]
 
-    def _lexical(self, query: str, limit: int, collection, defer: bool = False):
+    def _lexical(self, query: str, limit: int, collection, defer: bool = False, org=None):
         """defer=True (``_defer`` in the RPC's params; RAG2Retriever sets it): the kernels are
         enqueued on the index's side stream and the rows are read back when first looked at --
         the retriever issues its semantic RPC in between, and the two channels overlap."""
@@ -541,20 +623,22 @@ class GpuIndexClient:
         terms = self._query_terms(query)
         if terms is None:
             return []
+        within = self._scoped(org, collection)
+        if within is None:
+            return []
         # (fixed width: one pinned buffer, one workspace size, whatever the number of terms)
         qt = self._upload(terms + [-1] * (N.THR_BM25_MAX_TERMS - len(terms)), torch.int32, self.index.device)
         k = min(N.THR_TOPK_MAX, limit)
         if not defer or self.index.device.type != "cuda":
-            S, I, _ = self.index.bm25_search(qt, k, collections=self._qcoll(collection),
-                                             conjunctive=self.lexical_and)
+            S, I, _ = self.index.bm25_search(qt, k, conjunctive=self.lexical_and, **within)
             scores, ids = self._download(S, I)
             return self._rows(ids, scores, len(ids), "rank", limit)
         side = self.index.side_stream()
         main = torch.cuda.current_stream(self.index.device)
         side.wait_stream(main)              # the upload was enqueued on the main stream
-        qc = self._qcoll(collection)
+        qc = within.get("collections")
         with torch.cuda.stream(side):
-            S, I, _ = self.index.bm25_search(qt, k, collections=qc, conjunctive=self.lexical_and)
+            S, I, _ = self.index.bm25_search(qt, k, conjunctive=self.lexical_and, **within)
         for t in (qt, qc):
             if t is not None:
                 t.record_stream(side)
@@ -575,6 +659,8 @@ class GpuIndexClient:
 
     # -------------------------------------------------------------- ingest
     def _check_org(self, rows: Sequence[Dict[str, Any]]) -> None:
+        if self.multi_tenant and any(r.get("org_id") is None for r in rows):
+            raise ValueError("insert refused: this client serves several tenants, every row needs its org_id")
         if self.org_id is not None and any(r.get("org_id") not in (None, self.org_id) for r in rows):
             raise ValueError("insert refused: the rows belong to another org_id than this index "
                              "(data isolation, as rpc() answers another tenant with no rows)")
@@ -636,6 +722,11 @@ class GpuIndexClient:
                     self._coll_id[c] = max(self._coll_id.values(), default=-1) + 1
             parts["collections"] = np.array([self._coll_id[r["collection"]] if r.get("collection") is not None
                                              else -2 for r in rows], dtype=np.int32)
+        if self.multi_tenant:
+            org_code = dict(self._org_code)
+            for r in rows:   # an org no earlier row carries gets the next id (ids never move)
+                org_code.setdefault(r["org_id"], max(org_code.values(), default=-1) + 1)
+            parts["attributes"] = {"org": np.array([org_code[r["org_id"]] for r in rows], dtype=np.int32)}
         if idx.tokens is not None:
             if any(r.get("tokens") is None for r in rows):
                 raise ValueError("the index has a late-interaction token store: every inserted row needs its "
@@ -652,6 +743,10 @@ class GpuIndexClient:
                                  np.asarray(mw, dtype=np.float32))
         idx.append_rows(**parts)
         st.append(rows, tokenizer=self.tokenizer if getattr(idx, "lex", None) is not None else None)
+        if self.multi_tenant:
+            self._org_code = org_code
+            self._settle_deferred()   # (a deferred search may still read the plans' labels)
+            self._plans.clear()       # (resolved over the old rows)
         if hasattr(self, "_by_text"):
             del self._by_text
         return [{"id": r["id"]} for r in rows]
@@ -671,10 +766,16 @@ class GpuIndexClient:
 
     # -------------------------------------------------------------- delete
     def _child_rows_where(self, filters, columns=("id", "document_id", "parent_id")) -> List[int]:
-        """Row indices of the child chunks that match every (column, values) filter."""
+        """Row indices of the child chunks that match every (column, values) filter; a multi-tenant
+        client also takes ``org_id`` (the store's per-row column)."""
         st = self.store
         rows: Optional[set] = None
         for column, values in filters:
+            if column == "org_id" and self.multi_tenant:
+                want = set(values)
+                hit = {i for i, v in enumerate(st.org_ids) if v in want}
+                rows = hit if rows is None else rows & hit
+                continue
             if column not in columns:
                 raise ValueError(f"delete: rag_child_chunks rows are addressed by {' / '.join(columns)}, not {column!r}")
             if column == "id":
@@ -686,11 +787,10 @@ class GpuIndexClient:
             rows = hit if rows is None else rows & hit
         return sorted(rows or ())
 
-    def _delete_rows(self, rows: List[int]) -> List[Dict[str, Any]]:
-        """Remove store rows ``rows`` (sorted, distinct) from the index, then from the store."""
-        if not rows:
-            return []
-        # a deferred reply issued before the delete holds local ids that are about to shift
+    def _settle_deferred(self) -> None:
+        """Read back every deferred reply that is still unresolved: before a delete shifts the local
+        ids they hold, and before the cached scope plans are dropped (a deferred lexical search may
+        still be reading a plan's labels on the side stream)."""
         self._pending_lex = None
         for ref in getattr(self, "_lazy", ()):
             lazy = ref()
@@ -700,6 +800,13 @@ class GpuIndexClient:
                 except Exception:   # (its own caller sees that failure when it looks at the rows)
                     pass
         self._lazy = []
+
+    def _delete_rows(self, rows: List[int]) -> List[Dict[str, Any]]:
+        """Remove store rows ``rows`` (sorted, distinct) from the index, then from the store."""
+        if not rows:
+            return []
+        # a deferred reply issued before the delete holds local ids that are about to shift
+        self._settle_deferred()
         images = None
         if self.image_index is not None:
             dead = set(rows)
@@ -708,6 +815,8 @@ class GpuIndexClient:
                 raise N.NativeError("delete refused: every row of the image index would be deleted: build a new index")
         self.index.delete_rows(np.asarray(rows, dtype=np.int64))       # index first: a refusal leaves both untouched
         deleted = self.store.delete(rows)
+        if self.multi_tenant:
+            self._plans.clear()       # (resolved over the old rows)
         if self.image_index is not None:
             if images:
                 self.image_index.delete_rows(np.asarray(images, dtype=np.int64))
@@ -730,11 +839,17 @@ class GpuIndexClient:
 
     def _delete_parents_where(self, filters) -> List[Dict[str, Any]]:
         """Parent rows by ``id`` / ``document_id`` (a parent belongs to one document: the one its
-        children name) -> the deleted parent rows; their children go with them (schema :106)."""
+        children name) -> the deleted parent rows; their children go with them (schema :106).
+        Multi-tenant, ``org_id`` restricts the delete to that org's chunks: a parent that other
+        orgs' chunks still name loses the org's children and stays."""
         st = self.store
         pids: Optional[set] = None
+        orgs: Optional[set] = None
         for column, values in filters:
-            if column == "id":
+            if column == "org_id" and self.multi_tenant:
+                orgs = set(values) if orgs is None else orgs & set(values)
+                hit = {p for p, o in zip(st.parent_ids, st.org_ids) if o in orgs and p in st.parents}
+            elif column == "id":
                 hit = {v for v in values if v in st.parents}
             elif column == "document_id":
                 want = set(values)
@@ -745,22 +860,35 @@ class GpuIndexClient:
         pids = pids or set()
         if not pids:
             return []
-        self._delete_rows([i for i, p in enumerate(st.parent_ids) if p in pids])
+        self._delete_rows([i for i, p in enumerate(st.parent_ids)
+                           if p in pids and (orgs is None or st.org_ids[i] in orgs)])
+        if orgs is not None:
+            pids -= set(st.parent_ids)      # (still named by another org's chunks)
         return [st.parents.pop(p) for p in sorted(pids, key=list(st.parents).index)]
 
     def _delete_documents_where(self, filters) -> List[Dict[str, Any]]:
         """Documents by ``id`` -> [{"id": d}, ...] of those that had chunks; their children and
-        the parents those reference go with them (schema :65, :107)."""
+        the parents those reference go with them (schema :65, :107).  Multi-tenant, ``org_id``
+        restricts the delete to that org's chunks (alone: every document of the org): a document
+        or parent that other orgs' chunks still name loses the org's chunks and stays."""
         st = self.store
         docs: Optional[set] = None
+        orgs: Optional[set] = None
         for column, values in filters:
-            if column != "id":
+            if column == "org_id" and self.multi_tenant:
+                orgs = set(values) if orgs is None else orgs & set(values)
+                values = {d for d, o in zip(st.document_ids, st.org_ids) if o in orgs}
+            elif column != "id":
                 raise ValueError(f"delete: rag_documents rows are addressed by id, not {column!r}")
             docs = set(values) if docs is None else docs & set(values)
-        rows = [i for i, d in enumerate(st.document_ids) if d in (docs or ())]
+        rows = [i for i, d in enumerate(st.document_ids)
+                if d in (docs or ()) and (orgs is None or st.org_ids[i] in orgs)]
         found = list(dict.fromkeys(st.document_ids[i] for i in rows))
         pids = {st.parent_ids[i] for i in rows}
         self._delete_rows(rows)
+        if orgs is not None:
+            pids -= set(st.parent_ids)
+            found = [d for d in found if d not in set(st.document_ids)]
         for p in pids:
             st.parents.pop(p, None)
         return [{"id": d} for d in found]
@@ -768,23 +896,38 @@ class GpuIndexClient:
     # -------------------------------------------------------------- tables
     def table(self, name: str) -> _TableQuery:
         if name == "rag_child_chunks":
-            def fetch(ids):
+            def fetch(ids, **within):       # (within: {"org": x} of a multi-tenant eq("org_id", x))
                 rows = []
                 for cid in ids:
                     i = self.store.row_index(cid)
-                    if i is not None:
+                    if i is not None and ("org" not in within or self.store.org_ids[i] == within["org"]):
                         rows.append(self.store.child_row(i))
                 return rows
 
-            def by_hash(hashes):
-                return [{"content_hash": h} for h in dict.fromkeys(hashes) if self.store.has_hash(h)]
+            def by_hash(hashes, **within):
+                if "org" not in within:
+                    return [{"content_hash": h} for h in dict.fromkeys(hashes) if self.store.has_hash(h)]
+                own = {h for h, o in zip(self.store.content_hashes or (), self.store.org_ids) if o == within["org"]}
+                return [{"content_hash": h} for h in dict.fromkeys(hashes) if h is not None and h in own]
             return _TableQuery(fetch, by_hash=by_hash, insert=self.insert_children, org_id=self.org_id,
-                               delete=self._delete_children_where)
+                               delete=self._delete_children_where, tenants=self.multi_tenant)
         if name == "rag_parent_chunks":
-            return _TableQuery(lambda ids: [dict(self.store.parents[p]) for p in ids
-                                            if p in self.store.parents], insert=self.insert_parents,
-                               org_id=self.org_id, delete=self._delete_parents_where)
+            def parents(ids, **within):     # (within an org: the parents that org's chunks name)
+                st = self.store
+                own = None if "org" not in within else \
+                    {p for p, o in zip(st.parent_ids, st.org_ids) if o == within["org"]}
+                return [dict(st.parents[p]) for p in ids if p in st.parents and (own is None or p in own)]
+            return _TableQuery(parents, insert=self.insert_parents, org_id=self.org_id,
+                               delete=self._delete_parents_where, tenants=self.multi_tenant)
         # tenant discovery of the tool layer (tools/crm_knowledge.py:89-101 in the reference)
+        if name in ("rag_documents", "organizations") and self.multi_tenant:
+            key = "org_id" if name == "rag_documents" else "id"
+
+            def tenants(_ids, **within):    # (the orgs that hold rows now, in order of first appearance)
+                return [{key: o} for o in dict.fromkeys(self.store.org_ids)
+                        if o is not None and ("org" not in within or o == within["org"])]
+            return _TableQuery(tenants, tenants=True,
+                               delete=self._delete_documents_where if name == "rag_documents" else None)
         if name == "rag_documents":
             return _TableQuery(lambda _ids: [{"org_id": self.org_id}] if self.org_id else [], org_id=self.org_id,
                                delete=self._delete_documents_where)
@@ -846,9 +989,19 @@ class GpuIndexClient:
     def entity_name(self, e: int) -> str:
         return self.store.entity_names[e]
 
-    def graph_chunks(self, seeds: List[int], top_k: int, hops: int = 2) -> List[str]:
+    def graph_chunks(self, seeds: List[int], top_k: int, hops: int = 2, org_id=None) -> List[str]:
+        """The chunk ids of the graph channel, best first.  A multi-tenant client scores ``org_id``'s
+        chunks only (graph_search(scopes=): the reference filters by .eq("org_id", org_id),
+        graph_search.py:154-230); the seeds come from ``find_entities``, which is global -- entity
+        names carry no org, isolation is at the chunk."""
+        within = {}
+        if self.multi_tenant:
+            plan = self._scope(org_id)
+            if plan is None:
+                return []
+            within = {"scopes": plan}
         qs = self._upload(seeds + [-1] * (N.THR_GRAPH_MAX_SEEDS - len(seeds)), torch.int32, self.index.device)
-        S, I, _ = self.index.graph_search(qs, min(N.THR_TOPK_MAX, top_k), hops)
+        S, I, _ = self.index.graph_search(qs, min(N.THR_TOPK_MAX, top_k), hops, **within)
         _, ids = self._download(S, I)
         return [self.store.child_ids[int(g) - self.store.doc_base] for g in ids]
 

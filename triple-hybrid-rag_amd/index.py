@@ -506,12 +506,25 @@ class GpuIndex(ScopedSearch, MutableIndex):
                            dense=L["dense"] if prune and dense_rows else None)
 
     @_refuse_when_unusable
-    def graph_search(self, query_seeds: torch.Tensor, k: int, hops: int = 2):
+    def graph_search(self, query_seeds: torch.Tensor, k: int, hops: int = 2, scopes=None, _labels=None):
+        """-> (scores f64, ids i64, counts i32).  scopes: as dense_search -- only chunks that satisfy
+        the query's scope are scored and ranked (thr_graph_topk_scoped over the scope labels: groups of
+        disjoint scopes, one call per group).  The walk over the entities is not filtered: entities
+        carry no attributes, isolation is at the chunk.  ``_labels``: (doc labels, query labels) of
+        one such call."""
+        if scopes is not None:
+            return self._graph_scoped(query_seeds, k, hops, scopes)
         G = self.graph
         # three tiers on the device (small / full on-chip capacities, then a capacity-free walk
         # in global memory): no flag to read back, nothing to raise in the middle of a batch
         seeds = self._t(query_seeds, torch.int32)
         ws = self._scratch("_ws_graph", N.graph_workspace_bytes(seeds.shape[0], G["ent_rowptr"].shape[0] - 1))
+        if _labels is not None:
+            S, I, cnt, _ = N.graph_topk_scoped(G["ent_rowptr"], G["ent_col"], G["men_rowptr"],
+                                               G["men_chunk"], G["men_conf"], seeds, hops, k, self.doc_base,
+                                               self.n_docs, _labels[0], _labels[1],
+                                               transposed=self._graph_transposed(), workspace=ws)
+            return S, I, cnt
         S, I, cnt, _ = N.graph_topk(G["ent_rowptr"], G["ent_col"], G["men_rowptr"],
                                     G["men_chunk"], G["men_conf"], seeds, hops, k, self.doc_base,
                                     self.n_docs, transposed=self._graph_transposed(),
@@ -528,21 +541,23 @@ class GpuIndex(ScopedSearch, MutableIndex):
     # ------------------------------------------------------------ pipeline
     @_refuse_when_unusable
     def side_channels(self, query_terms, lexical_top_k: int, query_seeds, graph_top_k: int, hops: int,
-                      scopes=None):
+                      scopes=None, scope_graph: bool = False):
         """The lexical and graph channels of a batch on a second HIP stream, so that they run
         beside the dense channel instead of after it: they do not depend on it before the fusion,
         they are latency-bound (one workgroup per query, a few per CU), and the dense pipeline has
         stretches that leave CUs idle (sample pass, shortlist, the gather-bound rescoring, the
         tail of the scan).  Returns (lexical result or None, graph result or None, join): call
         ``join()`` on the main stream before the results are read there.  THR_SIDE_STREAM=0 keeps
-        everything on one stream."""
+        everything on one stream.  ``scopes`` filters the lexical channel, and with ``scope_graph``
+        the graph channel too (graph_search(scopes=))."""
+        gscopes = scopes if scope_graph else None
         want_lex = query_terms is not None and self.lex is not None
         want_gra = query_seeds is not None and self.graph is not None
         if not (want_lex or want_gra):
             return None, None, (lambda: None)
         if os.environ.get("THR_SIDE_STREAM") == "0" or self.device.type != "cuda":
             lex = self.bm25_search(query_terms, lexical_top_k, scopes=scopes) if want_lex else None
-            gra = self.graph_search(query_seeds, graph_top_k, hops) if want_gra else None
+            gra = self.graph_search(query_seeds, graph_top_k, hops, scopes=gscopes) if want_gra else None
             return lex, gra, (lambda: None)
         self.side_stream()
         main = torch.cuda.current_stream(self.device)
@@ -552,7 +567,7 @@ class GpuIndex(ScopedSearch, MutableIndex):
                 t.record_stream(self._side)
         with torch.cuda.stream(self._side):
             lex = self.bm25_search(query_terms, lexical_top_k, scopes=scopes) if want_lex else None
-            gra = self.graph_search(query_seeds, graph_top_k, hops) if want_gra else None
+            gra = self.graph_search(query_seeds, graph_top_k, hops, scopes=gscopes) if want_gra else None
         for res in (lex, gra):
             if res is not None:
                 for t in res:
@@ -577,18 +592,26 @@ class GpuIndex(ScopedSearch, MutableIndex):
                        semantic_top_k: int = 100, lexical_top_k: int = 50, graph_top_k: int = 50,
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
                        qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100,
-                       rescue: bool = True, scopes=None, scope_rows_max: Optional[int] = None) -> BatchResult:
+                       rescue: bool = True, scopes=None, scope_rows_max: Optional[int] = None,
+                       scope_graph: bool = False) -> BatchResult:
         """plan.semantic/lexical/graph_top_k = 100/50/50 and weights 0.7/0.8/1.0 are the
         reference's QueryPlan defaults (src/voice_agent/rag2/query_planner.py:23-50).
         scopes: as dense_search, resolved once for the batch; the dense and the lexical channel
-        rank inside each query's scope.  The graph channel takes no filter (neither does the
-        reference's, retrieval.py:316-356): an org's entities mention only that org's chunks."""
+        rank inside each query's scope.
+        scope_graph: True passes the batch's ScopePlan to the graph channel too (on the side stream):
+        a chunk outside the query's scope is neither scored nor ranked there, so no channel list and
+        no fused id leaves the scope.  The reference's graph search filters by tenant -- every entity
+        and relation query carries .eq("org_id", org_id), graph_search.py:154-230 -- and by nothing
+        else (no p_collection there, retrieval.py:316-356).  False (the default) keeps the graph
+        channel unfiltered under ``scopes=``: right only where an org's entities mention that org's
+        chunks alone."""
         if scopes is not None:
             scopes = self.scope_plan(scopes, queries.shape[0])
         w = {"lexical": 0.7, "semantic": 0.8, "graph": 1.0}
         w.update(weights or {})
         ch = {}
-        lex, gra, join = self.side_channels(query_terms, lexical_top_k, query_seeds, graph_top_k, hops, scopes)
+        lex, gra, join = self.side_channels(query_terms, lexical_top_k, query_seeds, graph_top_k, hops, scopes,
+                                            scope_graph=scope_graph and scopes is not None)
         Ss, Is, Cs, nres = self.dense_search(queries, semantic_top_k, rescue=rescue, sync=False, scopes=scopes,
                                              scope_rows_max=scope_rows_max)
         ch["semantic"] = (Ss, Is, Cs)

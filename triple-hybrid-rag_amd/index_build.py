@@ -234,7 +234,8 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
         if any("collection" in r for r in child_rows) else None,
         vocab=vocab, entity_names=[e.get("name", "") for e in entity_rows], doc_base=doc_base,
         content_hashes=[r.get("content_hash") for r in child_rows]
-        if any(r.get("content_hash") is not None for r in child_rows) else None)
+        if any(r.get("content_hash") is not None for r in child_rows) else None,
+        org_ids=[r.get("org_id") for r in child_rows] if any("org_id" in r for r in child_rows) else None)
     hi = HostIndex(docs=docs, rowptr=rowptr, post_doc=pd, post_tf=ptf, doclen=dl, idf=idf,
                    avgdl=avgdl, store=store)
     if entity_rows:
@@ -249,7 +250,7 @@ _ARRAYS = ("docs", "rowptr", "post_doc", "post_tf", "doclen", "idf", "ent_rowptr
 _DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf")
 _DERIVED_SCALARS = ("doc_rel_err", "f16_layout", "lexical_tag", "dense_stride")
 _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modalities", "collections",
-                   "entity_names", "content_hashes")
+                   "entity_names", "content_hashes", "org_ids")
 _NO_PAGE = np.iinfo(np.int32).min   # store_pages.npy: the SQL column is nullable (page INT)
 
 
@@ -386,6 +387,7 @@ def load(path: str, mmap: bool = True) -> HostIndex:
                                 modalities=cols["modalities"], parents=ms["parents"],
                                 collections=cols.get("collections"), vocab=vocab,
                                 entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"],
-                                content_hashes=cols.get("content_hashes"))
+                                content_hashes=cols.get("content_hashes"),
+                                org_ids=cols.get("org_ids"))    # (None: a directory saved without the column)
     attributes = {name: arr(f"attr_{i}") for i, name in enumerate(meta.get("attributes", []))} or None
     return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, attributes=attributes, **arrays)

@@ -16,7 +16,9 @@ on the device (``scope_plan``: thr_scope_resolve) and routes every query:
 
 Both routes return the same bits (the float64 rescoring of the float32 rows, (score desc, id asc)),
 so ``scope_rows_max`` only moves time.  BM25 always filters through the labels (idf / avgdl stay
-corpus-wide, as across collections and shards); the graph channel takes no filter.
+corpus-wide, as across collections and shards), and so does the graph channel where it is asked to
+(graph_search(scopes=), retrieve_batch(scope_graph=True): thr_graph_topk_scoped -- the walk over the
+entities is unfiltered, a chunk outside the scope is not scored).
 """
 from __future__ import annotations
 
@@ -162,6 +164,12 @@ class ScopedSearch:
                 tab[i, names.index(name)] = NO_ROW if value is None or int(value) < 0 else int(value)
         return names, tab
 
+    def scope_plan_current(self, plan: ScopePlan, n_queries: int) -> bool:
+        """Does ``plan`` still hold for a batch of n_queries on this index?  (Made for that batch size,
+        no mutation and no column replaced since.)  What a caller that keeps plans asks before reuse."""
+        return plan.qscope.shape[0] == n_queries and plan.n_docs == self.n_docs and \
+            plan.mutations == getattr(self, "_mutations", 0) and plan.columns == self._column_key()
+
     def scope_plan(self, scopes, n_queries: int) -> ScopePlan:
         """Resolve the distinct scopes of a batch on the device (thr_scope_resolve) -> ScopePlan.
         ``scopes``: per query a dict {attribute: value} (None / {} = unscoped), or an int32 [nq, C]
@@ -173,8 +181,7 @@ class ScopedSearch:
         (set_attributes / set_collections), on the index that made it; pass it as ``scopes=`` to
         search without the host work and the read-back."""
         if isinstance(scopes, ScopePlan):
-            if scopes.qscope.shape[0] != n_queries or scopes.n_docs != self.n_docs or \
-                    scopes.mutations != getattr(self, "_mutations", 0) or scopes.columns != self._column_key():
+            if not self.scope_plan_current(scopes, n_queries):
                 raise ValueError("scopes: this ScopePlan was made for another batch size, another index, or before "
                                  "the index or its attribute columns changed")
             return scopes
@@ -254,28 +261,42 @@ class ScopedSearch:
                 put(idx, self.dense_search(sub, k, kprime, rescue, sync, collections=qc, _labels=plan.labels[gi]))
         return S, I, cnt, n_rescued
 
-    def _bm25_scoped(self, query_terms, k: int, scopes, conjunctive: bool, prune: bool, dense_rows: bool):
-        qt = self._t(query_terms, torch.int32)
-        nq = qt.shape[0]
-        plan = self.scope_plan(scopes, nq)
-        if not plan.groups:
-            return self.bm25_search(qt, k, None, conjunctive, prune, dense_rows)
+    def _per_group(self, plan: ScopePlan, nq: int, call):
+        """``call(at, labels, query_label)`` once per group of disjoint scopes -- ``at``: the device indices
+        of the group's queries (None: the whole batch), ``labels``: the group's row labels, ``query_label``
+        int32: each query's index in the group -- and the results put back in batch order.  The unscoped
+        queries ride with the first group (query label -1: no filter)."""
         qs = plan.qscope
         out = None
         for gi in range(len(plan.groups)):
-            # the unscoped queries ride with the first group (query_coll -1: no filter)
             mask = ((qs >= 0) & (plan.local[np.maximum(qs, 0), 0] == gi)) | ((qs < 0) & (gi == 0))
             idx = np.nonzero(mask)[0]
             if not idx.size:
                 continue
-            qc = np.where(qs[idx] >= 0, plan.local[np.maximum(qs[idx], 0), 1], -1).astype(np.int32)
-            at = torch.from_numpy(idx).to(self.device)
-            res = self.bm25_search(qt[at].contiguous(), k, torch.from_numpy(qc).to(self.device), conjunctive,
-                                   prune, dense_rows, _labels=plan.labels[gi])
-            if len(plan.groups) == 1 and idx.size == nq:
+            ql = np.where(qs[idx] >= 0, plan.local[np.maximum(qs[idx], 0), 1], -1).astype(np.int32)
+            whole = len(plan.groups) == 1 and idx.size == nq
+            at = None if whole else torch.from_numpy(idx).to(self.device)
+            res = call(at, plan.labels[gi], torch.from_numpy(ql).to(self.device))
+            if whole:
                 return res
             if out is None:
                 out = tuple(torch.empty((nq,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device) for r in res)
             for o, r in zip(out, res):
                 o[at] = r
         return out
+
+    def _bm25_scoped(self, query_terms, k: int, scopes, conjunctive: bool, prune: bool, dense_rows: bool):
+        qt = self._t(query_terms, torch.int32)
+        plan = self.scope_plan(scopes, qt.shape[0])
+        if not plan.groups:
+            return self.bm25_search(qt, k, None, conjunctive, prune, dense_rows)
+        return self._per_group(plan, qt.shape[0], lambda at, labels, ql: self.bm25_search(
+            qt if at is None else qt[at].contiguous(), k, ql, conjunctive, prune, dense_rows, _labels=labels))
+
+    def _graph_scoped(self, query_seeds, k: int, hops: int, scopes):
+        seeds = self._t(query_seeds, torch.int32)
+        plan = self.scope_plan(scopes, seeds.shape[0])
+        if not plan.groups:
+            return self.graph_search(seeds, k, hops)
+        return self._per_group(plan, seeds.shape[0], lambda at, labels, ql: self.graph_search(
+            seeds if at is None else seeds[at].contiguous(), k, hops, _labels=(labels, ql)))

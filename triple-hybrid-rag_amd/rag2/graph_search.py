@@ -56,7 +56,12 @@ class GraphSearcher:
         seeds = client.find_entities(keywords, limit=top_k)
         if not seeds:
             return GraphSearchResult([], [], [], [], "hip_csr")
-        chunk_ids = client.graph_chunks(seeds, top_k, self.hops)
+        if getattr(client, "multi_tenant", False):
+            # one index, many tenants: the chunks are scored inside org_id (the reference filters every
+            # entity and relation query by .eq("org_id", org_id), graph_search.py:154-230)
+            chunk_ids = client.graph_chunks(seeds, top_k, self.hops, org_id=org_id)
+        else:
+            chunk_ids = client.graph_chunks(seeds, top_k, self.hops)
         nodes = [GraphNode(id=str(e), label="entity", properties={"name": client.entity_name(e)})
                  for e in seeds]
         return GraphSearchResult(nodes=nodes[:top_k], edges=[], paths=[], chunk_ids=chunk_ids,

@@ -72,6 +72,9 @@ class _ShardEndpoint(GpuIndexClient):
         merge_fn(scores [W, 1, k], ids [W, 1, k], k) -> (scores [1, k], ids [1, k]): the per-query
         merge of the gathered shard lists; default thr_merge_topk (tests of the control flow on a
         CPU-only box inject their own)."""
+        if getattr(store, "org_ids", None) is not None:
+            raise N.NativeError("a sharded index client serves one tenant: this store carries a per-row org_ids "
+                                "column (scoped queries over a document-sharded index are not built)")
         super().__init__(index, store, org_id=org_id, token_embedder=token_embedder,
                          lexical_and=lexical_and, collection_names=collection_names)
         if not dist.is_initialized():
