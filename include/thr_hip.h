@@ -516,7 +516,10 @@ int thr_fuse_post(const int64_t *ids, const double *scores, const int32_t *ranks
  * Stands where Qwen3VLReranker._rerank_batch_native is called,
  * retrieval.py:427 (src/voice_agent/retrieval/reranker.py:287-354).
  * cand [nq, n_cand] are LOCAL doc indices into dtok, negative = padding
- * (score -inf).  q_tokens, d_tokens multiples of 32; tok_dim multiple of 16. */
+ * (score -inf).  q_tokens, d_tokens multiples of 32; tok_dim one of 16, 32, 64, 96, 128, 192, 256
+ * (one kernel each).  Any other shape is THR_ERR_UNSUPPORTED, from thr_maxsim_pack too and before a
+ * pointer is looked at.  n_queries is not bounded by the grid: a batch above the device's
+ * gridDim.y limit is launched in slices. */
 int thr_maxsim(const uint16_t *qtok /* f16 [nq,q_tokens,tok_dim] */, int n_queries, int q_tokens,
                const uint16_t *dtok /* f16 [n_docs,d_tokens,tok_dim], or its packed image */,
                int64_t n_docs, int d_tokens, int tok_dim, const int32_t *cand, int n_cand,
@@ -539,7 +542,8 @@ int thr_rerank_order(const float *scores /* [n_lists][nq,n] */, int n_lists, int
                      double *out_scores /* [nq,top_k] */, int32_t *out_counts, thr_stream_t stream);
 /* Index build: re-lay the token store fragment-major ([doc][32-token tile][k-step][lane][8
  * halves], the register image of the MFMA operand) so thr_maxsim(dtok_packed = 1) reads 1 KiB
- * contiguous per load instruction.  Out of place; same size as dtok. */
+ * contiguous per load instruction.  Out of place; same size as dtok.  Takes exactly the shapes
+ * thr_maxsim scores: a store no later rerank could read is refused here. */
 int thr_maxsim_pack(const uint16_t *dtok, int64_t n_docs, int d_tokens, int tok_dim,
                     uint16_t *packed, thr_stream_t stream);
 

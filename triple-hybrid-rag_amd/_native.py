@@ -28,6 +28,8 @@ THR_TOPK_MAX = 128
 THR_SCOPE_MAX_COLS = 8
 THR_SCOPE_MAX_PREDS = 4096
 THR_SCOPE_MAX_QUERIES = 1 << 20
+# token dims thr_maxsim has a kernel for (csrc/maxsim.hip THR_MS_KSTEPS, times 16)
+MAXSIM_TOK_DIMS = (16, 32, 64, 96, 128, 192, 256)
 ABI_VERSION = 9
 
 _lib = None
@@ -982,12 +984,21 @@ def fuse_post(ids, scores, ranks=None, counts=None, channel_scores=(None, None, 
 
 
 # --------------------------------------------------------------------- a8
+def maxsim_check_tokens(what: str, tok_dim: int, *n_tokens: int) -> None:
+    """The shapes thr_maxsim_pack / thr_maxsim / thr_maxsim_ids take, refused here with the
+    list in the message (the library answers the same shapes with THR_ERR_UNSUPPORTED)."""
+    if any(n <= 0 or n % 32 for n in n_tokens):
+        raise NativeError(f"{what}: q_tokens / d_tokens must be positive multiples of 32, got {n_tokens}")
+    if tok_dim not in MAXSIM_TOK_DIMS:
+        raise NativeError(f"{what}: tok_dim {tok_dim} is not supported: the MaxSim kernels take tok_dim in "
+                          f"{list(MAXSIM_TOK_DIMS)}")
+
+
 def maxsim_pack(dtok: torch.Tensor) -> torch.Tensor:
     """Row-major token store -> fragment-major image for maxsim(..., packed=True)."""
     pdt = _dev(dtok, torch.float16, "dtok", 3)
     nd, dt, td = dtok.shape
-    if dt % 32 or td % 16:
-        raise NativeError("maxsim: d_tokens must be a multiple of 32, tok_dim of 16")
+    maxsim_check_tokens("maxsim_pack", td, dt)
     out = torch.empty_like(dtok)
     _check(load().thr_maxsim_pack(pdt, nd, dt, td, out.data_ptr(), _stream()), "thr_maxsim_pack")
     return out
@@ -1003,8 +1014,7 @@ def maxsim(qtok: torch.Tensor, dtok: torch.Tensor, cand: torch.Tensor,
     nd, dt, td2 = dtok.shape
     if td != td2 or cand.shape[0] != nq:
         raise NativeError("maxsim: shape mismatch")
-    if qt % 32 or dt % 32 or td % 16:
-        raise NativeError("maxsim: q_tokens/d_tokens must be multiples of 32, tok_dim of 16")
+    maxsim_check_tokens("maxsim", td, qt, dt)
     out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
     _check(load().thr_maxsim(pq, nq, qt, pdt, nd, dt, td, pc, cand.shape[1], out.data_ptr(),
                              1 if packed else 0, _stream()), "thr_maxsim")
@@ -1022,8 +1032,7 @@ def maxsim_ids(qtok: torch.Tensor, dtok: torch.Tensor, cand_ids: torch.Tensor, i
     nd, dt, td2 = dtok.shape
     if td != td2 or cand_ids.shape[0] != nq:
         raise NativeError("maxsim: shape mismatch")
-    if qt % 32 or dt % 32 or td % 16:
-        raise NativeError("maxsim: q_tokens/d_tokens must be multiples of 32, tok_dim of 16")
+    maxsim_check_tokens("maxsim_ids", td, qt, dt)
     out = torch.empty(cand_ids.shape, dtype=torch.float32, device=qtok.device)
     _check(load().thr_maxsim_ids(pq, nq, qt, pdt, nd, dt, td, pc, int(id_base), cand_ids.shape[1],
                                  out.data_ptr(), 1 if packed else 0, _stream()), "thr_maxsim_ids")

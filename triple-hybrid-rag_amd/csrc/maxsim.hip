@@ -21,8 +21,9 @@
 // thr_maxsim_pack re-lays the store FRAGMENT-MAJOR at index build -- [doc][tile of 32
 // tokens][k-step][lane][8 halves], the exact register image of the A operand -- so a load
 // instruction reads 1 KiB contiguous and each line is touched once (PACKED = true).
-// fp16*fp16 products are exact in the fp32 accumulator; only the 128-term
-// accumulation rounds (tests: 1e-4 absolute on scores <= 32).
+// fp16*fp16 products are exact in the fp32 accumulator; only the accumulation rounds
+// (tests/test_gpu_maxsim.py: the float64 bits wherever the float32 sums are exact, the float32
+// forward-error bound of the inputs elsewhere, 1e-4 absolute at 128 x 128 unit-norm tokens).
 // Algorithmic bytes per (q, c): d_tokens*tok_dim*2 (32 KiB at 128x128); flops 2*q_tokens*d_tokens*tok_dim.
 #include "thr_common.hpp"
 
@@ -33,7 +34,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MS_THREADS = 256;
 constexpr int MS_WAVES = MS_THREADS / WAVE;
-constexpr int MS_MAX_KSTEPS = 16;  // tok_dim <= 256
 
 // row-major tokens -> fragment-major: one thread per 16-byte chunk
 __global__ __launch_bounds__(256) void maxsim_pack_kernel(const _Float16* __restrict__ dtok,
@@ -119,13 +119,47 @@ __global__ __launch_bounds__(MS_THREADS) void maxsim_kernel(
 
 using namespace thr;
 
+// tok_dim / 16 of the scorer's instantiations.  THE list: the switch of launch_maxsim and the
+// shape check of every entry point (thr_maxsim_pack included: a store the scorer cannot read is
+// refused where the tokens enter) are both made from it; _native.MAXSIM_TOK_DIMS restates it and
+// tests/test_maxsim_host.py holds the two together.
+#define THR_MS_KSTEPS(X) X(1) X(2) X(4) X(6) X(8) X(12) X(16)
+
+static bool tok_dim_supported(int tok_dim) {
+    if (tok_dim <= 0 || tok_dim % 16) return false;
+    switch (tok_dim / 16) {
+#define THR_MS_LABEL(KS) case KS:
+        THR_MS_KSTEPS(THR_MS_LABEL)
+#undef THR_MS_LABEL
+        return true;
+        default:
+            return false;
+    }
+}
+
+// Shapes are refused before any pointer is looked at (host arithmetic: no GPU needed to ask).
+static bool tokens_supported(int n_tokens, int tok_dim) {
+    return n_tokens > 0 && n_tokens % 32 == 0 && tok_dim_supported(tok_dim);
+}
+
+// Largest gridDim.y of the current device (65535 when it cannot be asked)
+static int max_grid_y() {
+    static int gy = 0;
+    if (!gy) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+            gy = prop.maxGridSize[1];
+        if (gy <= 0) gy = 65535;
+    }
+    return gy;
+}
+
 extern "C" int thr_maxsim_pack(const uint16_t* dtok, int64_t n_docs, int d_tokens, int tok_dim,
                                uint16_t* packed, thr_stream_t stream) {
     clear_status();
+    THR_RETURN_IF(!tokens_supported(d_tokens, tok_dim), THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(!dtok || !packed || dtok == packed || n_docs <= 0, THR_ERR_INVALID);
-    THR_RETURN_IF(d_tokens <= 0 || d_tokens % 32 || tok_dim <= 0 || tok_dim % 16 ||
-                      tok_dim / 16 > MS_MAX_KSTEPS,
-                  THR_ERR_UNSUPPORTED);
     const int64_t n_chunks = n_docs * d_tokens * (tok_dim / 8);
     THR_RETURN_IF((n_chunks + 255) / 256 > 0x7fffffffll, THR_ERR_UNSUPPORTED);
     hipLaunchKernelGGL(maxsim_pack_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0,
@@ -139,33 +173,37 @@ static int launch_maxsim(const uint16_t* qtok, int n_queries, int q_tokens, cons
                          const int64_t* cand_ids, int64_t id_base, int n_cand, float* out_scores,
                          int dtok_packed, thr_stream_t stream) {
     clear_status();
+    THR_RETURN_IF(!tokens_supported(q_tokens, tok_dim) || !tokens_supported(d_tokens, tok_dim),
+                  THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(!qtok || !dtok || (!cand && !cand_ids) || !out_scores, THR_ERR_INVALID);
     THR_RETURN_IF(n_queries <= 0 || n_docs <= 0 || n_cand <= 0, THR_ERR_INVALID);
-    THR_RETURN_IF(q_tokens <= 0 || q_tokens % 32 || d_tokens <= 0 || d_tokens % 32 ||
-                      tok_dim <= 0 || tok_dim % 16 || tok_dim / 16 > MS_MAX_KSTEPS,
-                  THR_ERR_UNSUPPORTED);
-    dim3 grid((n_cand + MS_WAVES - 1) / MS_WAVES, n_queries);
-    const _Float16* Q = reinterpret_cast<const _Float16*>(qtok);
     const _Float16* Dk = reinterpret_cast<const _Float16*>(dtok);
     hipStream_t st = (hipStream_t)stream;
+    // queries sit on gridDim.y: a batch above the device's limit goes out in slices of at most
+    // that many queries, each a launch of its own over its rows of qtok, cand / cand_ids and out
+    const int slice = max_grid_y();
+    for (int q0 = 0; q0 < n_queries; q0 += slice) {
+        dim3 grid((n_cand + MS_WAVES - 1) / MS_WAVES, n_queries - q0 < slice ? n_queries - q0 : slice);
+        const _Float16* Q = reinterpret_cast<const _Float16*>(qtok) + (int64_t)q0 * q_tokens * tok_dim;
+        const int32_t* C = cand ? cand + (int64_t)q0 * n_cand : nullptr;
+        const int64_t* G = cand_ids ? cand_ids + (int64_t)q0 * n_cand : nullptr;
+        float* out = out_scores + (int64_t)q0 * n_cand;
 #define THR_MS_CASE(KS)                                                                          \
     case KS:                                                                                     \
         if (dtok_packed)                                                                         \
             hipLaunchKernelGGL((maxsim_kernel<KS, true>), grid, dim3(MS_THREADS), 0, st, Q,      \
-                               q_tokens, Dk, n_docs, d_tokens, cand, cand_ids, id_base, n_cand,  \
-                               out_scores);                                                      \
+                               q_tokens, Dk, n_docs, d_tokens, C, G, id_base, n_cand, out);      \
         else                                                                                     \
             hipLaunchKernelGGL((maxsim_kernel<KS, false>), grid, dim3(MS_THREADS), 0, st, Q,     \
-                               q_tokens, Dk, n_docs, d_tokens, cand, cand_ids, id_base, n_cand,  \
-                               out_scores);                                                      \
+                               q_tokens, Dk, n_docs, d_tokens, C, G, id_base, n_cand, out);      \
         break;
-    switch (tok_dim / 16) {
-        THR_MS_CASE(1) THR_MS_CASE(2) THR_MS_CASE(4) THR_MS_CASE(6) THR_MS_CASE(8)
-        THR_MS_CASE(12) THR_MS_CASE(16)
-        default:
-            return THR_ERR_UNSUPPORTED;
-    }
+        switch (tok_dim / 16) {
+            THR_MS_KSTEPS(THR_MS_CASE)
+            default:
+                return THR_ERR_UNSUPPORTED;
+        }
 #undef THR_MS_CASE
+    }
     return launch_status();
 }
 
@@ -180,7 +218,6 @@ extern "C" int thr_maxsim_ids(const uint16_t* qtok, int n_queries, int q_tokens,
                               int64_t n_docs, int d_tokens, int tok_dim, const int64_t* cand_ids,
                               int64_t id_base, int n_cand, float* out_scores, int dtok_packed,
                               thr_stream_t stream) {
-    THR_RETURN_IF(!cand_ids, THR_ERR_INVALID);
     return launch_maxsim(qtok, n_queries, q_tokens, dtok, n_docs, d_tokens, tok_dim, nullptr, cand_ids,
                          id_base, n_cand, out_scores, dtok_packed, stream);
 }

@@ -275,8 +275,13 @@ class GpuIndex(ScopedSearch, MutableIndex):
 
     def set_tokens(self, dtok, pack: bool = True) -> "GpuIndex":
         """Late-interaction token store f16 [n, d_tokens, tok_dim].  pack=True keeps it in the
-        fragment-major layout of thr_maxsim_pack (the row-major copy is dropped)."""
+        fragment-major layout of thr_maxsim_pack (the row-major copy is dropped).  d_tokens is a
+        multiple of 32 and tok_dim one of _native.MAXSIM_TOK_DIMS."""
         tok = self._t(dtok, torch.float16)
+        if tok.dim() != 3:
+            raise N.NativeError("set_tokens: tokens must be [n, d_tokens, tok_dim]")
+        # a store the scorer has no kernel for is refused here, packed or not, not at the first query
+        N.maxsim_check_tokens("set_tokens", int(tok.shape[2]), int(tok.shape[1]))
         self.tokens_packed = bool(pack)
         self.tokens = N.maxsim_pack(tok) if pack else tok
         return self

@@ -318,6 +318,8 @@ class MutableIndex:
         tk = self._host_or_device(tokens, "tokens")
         if tk.ndim != 3 or tk.shape[0] != m or tuple(tk.shape[1:]) != tuple(self.tokens.shape[1:]):
             raise N.NativeError(f"append_rows: tokens must be [{m}, {self.tokens.shape[1]}, {self.tokens.shape[2]}]")
+        # (set_tokens applies the same check: this one holds for a store that came another way)
+        N.maxsim_check_tokens("append_rows: tokens", int(tk.shape[2]), int(tk.shape[1]))
         return tk
 
     def _check_dense_part(self, docs, n_rows):
