@@ -103,13 +103,7 @@ __global__ __launch_bounds__(CC_THREADS) void csr_compact_scan(const int32_t* __
     int64_t sum = 0;
     for (int64_t i = lo; i < hi; ++i) sum += slice_count[i];
     s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < CC_THREADS; d <<= 1) {      // inclusive Hillis-Steele over the 256 sums
-        const int64_t add = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += add;
-        __syncthreads();
-    }
+    block_inclusive_scan<CC_THREADS>(s_sum);        // over the 256 sums
     int64_t run = s_sum[threadIdx.x] - sum;
     for (int64_t i = lo; i < hi; ++i) {
         slice_base[i] = run;

@@ -25,6 +25,9 @@
 //                               accumulation (the oracle's contract), sorted (score desc, row asc),
 //                               certified with the scan's error bound
 //   K5 thr_dense_rescue         [dense_exact.hip] uncertified queries redone exhaustively
+// Beside the pipeline, the same float64 arithmetic without a shortlist: thr_dense_topk_exact over every row
+// [dense_exact.hip] and thr_dense_topk_rows over a scope's row list [dense_rows.hip], both merged by
+// merge_lists [dense_exact.hip].
 // Algorithmic HBM bytes of K3 = n_docs * dim * 4 per tile pass.
 //
 // This unit is the host side of a batch: the knobs, the work plan and its workspace, the grid of a

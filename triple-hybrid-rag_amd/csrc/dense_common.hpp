@@ -203,5 +203,10 @@ int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& 
 int launch_bucket(const DensePlan& P, hipStream_t st);
 int launch_band(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, const DensePhase& S, int nseg);
 int launch_rescore(const DensePlan& P, const DenseIndex& X, const DenseBatch& B);
+// dense_exact.hip, for dense_rows.hip: the [q][slab][k] lists of every query -> its top k (ids + id_base,
+// flags CERTIFIED|EXACT); a query whose scope is outside [0, n_scopes) gets the empty list
+int launch_merge_scoped(const double* slab_s, const int64_t* slab_id, int n_queries, int n_slabs, int k,
+                        int64_t id_base, const int32_t* query_scope, int n_scopes, double* out_scores,
+                        int64_t* out_ids, int32_t* out_counts, uint32_t* out_flags, hipStream_t st);
 
 }  // namespace thr

@@ -1,5 +1,5 @@
 // Dense channel, the exhaustive path and the merges: thr_dense_topk_exact, thr_dense_rescue (K5 of
-// the pipeline, dense.hip) and thr_merge_topk.
+// the pipeline, dense.hip) and thr_merge_topk; the merge of thr_dense_topk_rows (dense_rows.hip).
 #include "dense_common.hpp"
 
 namespace thr {
@@ -87,7 +87,11 @@ __global__ __launch_bounds__(EX_THREADS) void exact_slab_topk(
     }
 }
 
-// merges n_lists ranked lists of k_in per query (layout [n_lists? no: q-major]) -> top k_out
+// merges n_lists ranked lists of k_in per query (entry j of list l of query q at
+// q * q_stride + l * list_stride + j) -> top k_out, ids + id_add, padded with (-inf, -1).
+// GATED (thr_dense_topk_rows): a query whose query_scope is outside [0, P) gets the empty list -- its
+// lists were never written.  The ungated flavour ignores query_scope and P.
+template <bool GATED>
 __global__ __launch_bounds__(256) void merge_lists(const double* __restrict__ in_s,
                                                    const int64_t* __restrict__ in_id,
                                                    int64_t q_stride, int64_t list_stride,
@@ -97,8 +101,9 @@ __global__ __launch_bounds__(256) void merge_lists(const double* __restrict__ in
                                                    int64_t* __restrict__ out_id,
                                                    int32_t* __restrict__ out_counts,
                                                    uint32_t* __restrict__ out_flags,
-                                                   const uint32_t* __restrict__ skip_certified = nullptr,
-                                                   int32_t* __restrict__ n_done = nullptr) {
+                                                   const uint32_t* __restrict__ skip_certified,
+                                                   int32_t* __restrict__ n_done,
+                                                   const int32_t* __restrict__ query_scope, int P) {
     if (skip_certified && (skip_certified[blockIdx.x] & THR_FLAG_CERTIFIED)) return;
     if (n_done && threadIdx.x == 0) atomicAdd(n_done, 1);
     __shared__ double b_s[EX_CAP];
@@ -107,22 +112,27 @@ __global__ __launch_bounds__(256) void merge_lists(const double* __restrict__ in
     __shared__ double t_s;
     __shared__ int64_t t_id;
     const int q = blockIdx.x;
-    BlockTopK<EX_CAP, EX_THREADS> tk;
-    tk.init(b_s, b_id, &b_cnt, &t_s, &t_id, k_out);
-    const int total = n_lists * k_in;
-    for (int base = 0; base < total; base += blockDim.x) {
-        int i = base + threadIdx.x;
-        bool ok = i < total;
-        double s = -INFINITY;
-        int64_t id = INT64_MAX;
-        if (ok) {
-            int64_t o = (int64_t)q * q_stride + (int64_t)(i / k_in) * list_stride + (i % k_in);
-            s = in_s[o];
-            id = in_id[o];
+    bool live = true;
+    if constexpr (GATED) live = query_scope[q] >= 0 && query_scope[q] < P;
+    int n = 0;
+    if (live) {
+        BlockTopK<EX_CAP, EX_THREADS> tk;
+        tk.init(b_s, b_id, &b_cnt, &t_s, &t_id, k_out);
+        const int total = n_lists * k_in;
+        for (int base = 0; base < total; base += blockDim.x) {
+            int i = base + threadIdx.x;
+            bool ok = i < total;
+            double s = -INFINITY;
+            int64_t id = INT64_MAX;
+            if (ok) {
+                int64_t o = (int64_t)q * q_stride + (int64_t)(i / k_in) * list_stride + (i % k_in);
+                s = in_s[o];
+                id = in_id[o];
+            }
+            tk.push(ok && s > -INFINITY && id >= 0 && id != INT64_MAX, s, id);
         }
-        tk.push(ok && s > -INFINITY && id >= 0 && id != INT64_MAX, s, id);
+        n = tk.finish();
     }
-    int n = tk.finish();
     for (int i = threadIdx.x; i < k_out; i += blockDim.x) {
         out_s[(int64_t)q * k_out + i] = i < n ? b_s[i] : -INFINITY;
         out_id[(int64_t)q * k_out + i] = i < n ? b_id[i] + id_add : -1;
@@ -245,10 +255,22 @@ static int exact_topk(const float* docs, const double* dnorm, int64_t n_docs, in
                        slab_s, slab_id, certified, doc_coll, query_coll);
     int rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(merge_lists, dim3(n_queries), dim3(256), 0, st, slab_s, slab_id,
+    hipLaunchKernelGGL(merge_lists<false>, dim3(n_queries), dim3(256), 0, st, slab_s, slab_id,
                        (int64_t)EX_SLABS * k, (int64_t)k, EX_SLABS, k, k, id_base,
                        THR_FLAG_CERTIFIED | THR_FLAG_EXACT, out_scores, out_ids, out_counts,
-                       out_flags, certified, n_rescued);
+                       out_flags, certified, n_rescued, (const int32_t*)nullptr, 0);
+    return launch_status();
+}
+
+// thr_dense_topk_rows (dense_rows.hip): the n_slabs lists of k of every query, [q][slab][k], ranked by
+// the gated merge_lists
+int thr::launch_merge_scoped(const double* slab_s, const int64_t* slab_id, int n_queries, int n_slabs, int k,
+                             int64_t id_base, const int32_t* query_scope, int n_scopes, double* out_scores,
+                             int64_t* out_ids, int32_t* out_counts, uint32_t* out_flags, hipStream_t st) {
+    hipLaunchKernelGGL(merge_lists<true>, dim3(n_queries), dim3(256), 0, st, slab_s, slab_id,
+                       (int64_t)n_slabs * k, (int64_t)k, n_slabs, k, k, id_base,
+                       THR_FLAG_CERTIFIED | THR_FLAG_EXACT, out_scores, out_ids, out_counts, out_flags,
+                       (const uint32_t*)nullptr, (int32_t*)nullptr, query_scope, n_scopes);
     return launch_status();
 }
 
@@ -297,8 +319,9 @@ extern "C" int thr_merge_topk(const double* in_scores, const int64_t* in_ids, in
                            out_scores, out_ids, out_counts);
         return launch_status();
     }
-    hipLaunchKernelGGL(merge_lists, dim3(n_queries), dim3(256), 0, (hipStream_t)stream, in_scores,
+    hipLaunchKernelGGL(merge_lists<false>, dim3(n_queries), dim3(256), 0, (hipStream_t)stream, in_scores,
                        in_ids, (int64_t)k_in, list_stride, n_lists, k_in, k_out,
-                       (int64_t)0, 0u, out_scores, out_ids, out_counts, (uint32_t*)nullptr);
+                       (int64_t)0, 0u, out_scores, out_ids, out_counts, (uint32_t*)nullptr,
+                       (const uint32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr, 0);
     return launch_status();
 }

@@ -1,7 +1,8 @@
-// What the graph channel's kernels share (graph.hip: thr_graph_topk; graph_scope.hip:
-// thr_graph_topk_scoped): capacities of the two on-chip tiers, the LDS hash set and sort of the walk,
-// the distance bytes of the global-memory tier.  The workspace layout is one: GR_MAX_CON float64
-// contribution values per query, then GR_FB_BLOCKS distance arrays (thr_graph_workspace_bytes).
+// What the graph channel's kernels share (graph.hip: thr_graph_topk and thr_graph_topk_scoped):
+// capacities of the two on-chip tiers, the LDS hash set and sort of the walk, the ranking tail behind
+// the placed contributions, the distance bytes of the global-memory tier.  The workspace layout is one:
+// GR_MAX_CON float64 contribution values per query, then GR_FB_BLOCKS distance arrays
+// (thr_graph_workspace_bytes).
 #pragma once
 #include "thr_common.hpp"
 
@@ -37,11 +38,12 @@ __device__ __forceinline__ bool gr_insert(uint32_t* keys, uint8_t* dist, uint32_
 
 // block-wide bitonic sort of uint64 keys, ascending, n = power of two.  Thread t takes PAIR t of a
 // stage (i = t with a zero bit inserted at j, partner i | j): every thread of every trip does a
-// compare-exchange (the i ^ j form leaves half of them idle).
+// compare-exchange (the i ^ j form leaves half of them idle).  The stride is the constant GR_THREADS that
+// every graph kernel is launched with.
 __device__ inline void sort_u64_asc(uint64_t* a, int n) {
     for (int k = 2; k <= n; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < n / 2; t += blockDim.x) {
+            for (int t = threadIdx.x; t < n / 2; t += GR_THREADS) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
                 const bool up = (i & k) == 0;
                 const uint64_t x = a[i], y = a[p];
@@ -67,7 +69,7 @@ __device__ __forceinline__ uint32_t gr_dist(const uint8_t* dist, uint32_t e) {
     return (w >> (8 * (e & 3))) & 0xffu;
 }
 
-// The on-chip walk of one query, shared by graph_topk_kernel and graph_scoped_kernel: seeds at level 0,
+// The on-chip walk of one query, shared by both flavours of graph_topk_kernel: seeds at level 0,
 // level-synchronous BFS over the entity CSR into the LDS hash set (keys / hdist, emptied by the caller)
 // and the reached list, then the reached entities sorted ascending with their distances (through `big`).
 // -> the number of reached entities kept (at most C::MAX_ENT; `overflow` is set beyond).  The whole
@@ -141,6 +143,62 @@ __device__ __forceinline__ int gr_walk_onchip(
         __syncthreads();
     }
     return nr;
+}
+
+// A query's ranked list -> its k output slots, padded with (-inf, -1), its count and its flags.
+__device__ __forceinline__ void gr_write_topk(const double* b_s, const int64_t* b_id, int n, int q, int k,
+                                              int64_t chunk_base, uint32_t flags, double* __restrict__ out_s,
+                                              int64_t* __restrict__ out_id, int32_t* __restrict__ out_cnt,
+                                              uint32_t* __restrict__ out_flags) {
+    for (int i = threadIdx.x; i < k; i += GR_THREADS) {
+        out_s[(int64_t)q * k + i] = i < n ? b_s[i] : -INFINITY;
+        out_id[(int64_t)q * k + i] = i < n ? b_id[i] + chunk_base : -1;
+    }
+    if (threadIdx.x == 0) {
+        out_cnt[q] = n;
+        out_flags[q] = flags;
+    }
+}
+
+// The tail of an on-chip tier, behind the placed contributions: big[0 .. nc) holds the keys
+// (local chunk << 32 | position, ~0 for a slot that counts for nothing), con_val[position] the values.
+// Keys padded to a power of two and sorted; each chunk's segment summed left to right in float64 by
+// the thread that owns its head; streaming block top-k (b_s / b_id may alias bytes the emitter used:
+// they are first written here, behind the sort's barriers); the padded write.
+template <typename C>
+__device__ __forceinline__ void gr_rank_and_write(
+    uint64_t* big, int nc, const double* __restrict__ con_val, double* b_s, int64_t* b_id, int* b_cnt,
+    double* th_s, int64_t* th_id, const int& overflow, int q, int k, int64_t chunk_base,
+    double* __restrict__ out_s, int64_t* __restrict__ out_id, int32_t* __restrict__ out_cnt,
+    uint32_t* __restrict__ out_flags) {
+    const int ncp = next_pow2(nc > 1 ? nc : 2);
+    for (int i = nc + threadIdx.x; i < ncp; i += GR_THREADS) big[i] = ~0ull;
+    __syncthreads();
+    sort_u64_asc(big, ncp);
+    __threadfence_block();
+
+    // ---- segmented left-to-right sums + top-k ----
+    BlockTopK<C::CAP, GR_THREADS> tk;
+    tk.init(b_s, b_id, b_cnt, th_s, th_id, k);
+    for (int base = 0; base < nc; base += GR_THREADS) {
+        const int i = base + threadIdx.x;
+        bool head = false;
+        double score = 0.0;
+        int64_t chunk = 0;
+        if (i < nc && big[i] != ~0ull) {
+            const uint32_t c = (uint32_t)(big[i] >> 32);
+            head = (i == 0) || ((uint32_t)(big[i - 1] >> 32) != c);
+            if (head) {
+                chunk = c;
+                for (int j = i; j < nc && big[j] != ~0ull && (uint32_t)(big[j] >> 32) == c; ++j)
+                    score = __dadd_rn(score, con_val[(uint32_t)big[j]]);
+            }
+        }
+        tk.push(head, score, chunk);
+    }
+    const int n = tk.finish();
+    gr_write_topk(b_s, b_id, n, q, k, chunk_base, overflow ? THR_FLAG_OVERFLOW : THR_FLAG_CERTIFIED, out_s,
+                  out_id, out_cnt, out_flags);
 }
 
 // The walk of one query in GLOBAL memory (third tier of both entry points): the workgroup's distance

@@ -137,6 +137,20 @@ __device__ __forceinline__ int next_pow2(int v) {
     return p;
 }
 
+// Block-wide inclusive scan (Hillis-Steele) of tmp[0 .. THREADS) in LDS, in place.  Every thread has
+// written tmp[threadIdx.x] before the call; the function ends behind a barrier and the total is
+// tmp[THREADS - 1].  All THREADS threads of the block call it together.
+template <int THREADS, typename T>
+__device__ __forceinline__ void block_inclusive_scan(T* tmp) {
+    __syncthreads();
+    for (int off = 1; off < THREADS; off <<= 1) {
+        const T v = threadIdx.x >= off ? tmp[threadIdx.x - off] : 0;
+        __syncthreads();
+        tmp[threadIdx.x] += v;
+        __syncthreads();
+    }
+}
+
 // Streaming block top-k: threads push (score,id) pairs that beat the current threshold; when the
 // LDS buffer fills it is cut back.  All threads of the block (THREADS of them) must call push() /
 // compact() / finish() together.
