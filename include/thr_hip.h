@@ -114,8 +114,8 @@ int thr_dense_topk_exact(const float *docs, const double *dnorm, int64_t n_docs,
 
 /* Device-side completion of thr_dense_topk / thr_dense_topk_f16: every query whose flags lack
  * THR_FLAG_CERTIFIED is redone on the exhaustive float64 path and overwritten in place (flags
- * become CERTIFIED | EXACT); *n_rescued (a DEVICE int32, may be NULL) is incremented per redone
- * query.  No host read-back: a batch runs end to end without a synchronisation. */
+ * become CERTIFIED | EXACT); *n_rescued (a DEVICE int32, may be NULL; it need not be initialised)
+ * is set to the number of redone queries.  No host read-back: a batch runs end to end without a synchronisation. */
 size_t thr_dense_rescue_workspace_bytes(int n_queries, int k);
 int thr_dense_rescue(const float *docs, const double *dnorm, int64_t n_docs, int dim,
                      int64_t id_base, const float *queries, int n_queries, int k,

@@ -300,7 +300,7 @@ def dense_rescue(docs, dnorm, queries, S, I, cnt, flg, id_base: int = 0,
     need = int(load().thr_dense_rescue_workspace_bytes(nq, k))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=docs.device)
-    n_rescued = torch.zeros(1, dtype=torch.int32, device=docs.device)
+    n_rescued = torch.empty(1, dtype=torch.int32, device=docs.device)   # (thr_dense_rescue writes the zero)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_rescue(pd, pn, n, d, id_base, pq, nq, k, pdc, pqc, S.data_ptr(), I.data_ptr(),
                                    cnt.data_ptr(), flg.data_ptr(), n_rescued.data_ptr(),

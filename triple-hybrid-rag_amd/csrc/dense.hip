@@ -8,9 +8,12 @@
 //
 // Pipeline per batch of queries (all kernels on one stream, no host sync):
 //   K0 pack_queries_f16         [dense_scan_f16q.hip] (default scan) queries -> fragment-major f16 register image
-//   K1 scan<MODE_ALL>           score a strided SAMPLE of row groups for every query tile
-//   K2 kth_select               [dense_select.hip] tau[q] ~ the ks-th largest sample score: about
-//                               `aim` rows of the corpus will pass it
+//   K1 scan<MODE_ALL>           score a strided SAMPLE of row groups for every query tile.  The
+//                               register-resident scans keep each lane's SAMPLE_TOP best per query in
+//                               registers and write only those; the other flavours write every score
+//   K2 kth_select[_top]         [dense_select.hip] tau[q] ~ the ks-th largest sample score (of the
+//                               lanes' kept values: never above it): about `aim` rows of the corpus
+//                               will pass it
 //   K3 scan<MODE_FILTER>        THE dominant kernel: stream the corpus once per query tile,
 //                               emit (score, row) >= tau[q].  Default: dense_scan_f16qs (f16
 //                               MFMA over the normalised f16 copy, queries in registers);
@@ -39,11 +42,15 @@
 
 namespace thr {
 
+constexpr double QREG_AIM_1M = 1448.0;   // see make_plan
+constexpr int QREG_KS = 32;
 // The A/B knobs, each read once per process (the layout of the f16 copy depends on them).
 struct DenseKnobs {
     bool forced_q;   // THR_DENSE_F16=q: dense_scan_f16q (4-wave blocks) at every dim
     int shape;       // THR_DENSE_MFMA=32: the 32x32x16 MFMA shape, else 16 (16x16x32)
     bool forced32;   // THR_DENSE_QW=32: 32 queries per wave at dim 1024 too
+    double aim_1m;   // THR_DENSE_AIM: candidates per query the register-resident scans aim at on 1M rows
+    int ks;          // THR_DENSE_KS: their sample rank (both: the sweep of profiles/dense_threshold_pass.md)
 };
 static const DenseKnobs& dense_knobs() {
     static const DenseKnobs knobs = [] {
@@ -54,6 +61,10 @@ static const DenseKnobs& dense_knobs() {
         K.shape = (e && atoi(e) == 32) ? 32 : 16;
         e = getenv("THR_DENSE_QW");
         K.forced32 = e && atoi(e) == 32;
+        e = getenv("THR_DENSE_AIM");
+        K.aim_1m = (e && atof(e) >= 64.0) ? atof(e) : QREG_AIM_1M;
+        e = getenv("THR_DENSE_KS");
+        K.ks = (e && atoi(e) >= 4 && atoi(e) <= 64) ? atoi(e) : QREG_KS;
         return K;
     }();
     return knobs;
@@ -74,7 +85,6 @@ int qreg_shape(int) { return dense_knobs().shape; }
 int qreg_qw(int dim) {
     return (dim == 1024 && !qreg_staggered(dim) && qreg_shape(dim) == 16 && !dense_knobs().forced32) ? 48 : 32;
 }
-constexpr int QREG_MAX_SEG = 1024;
 // The register-resident scans address a lane's candidate segment with a 32-bit byte offset from
 // the start of the candidate area ((q * CAND_CAP + segment start) * sizeof(Cand)): a batch may
 // hold as many (padded) queries as keep every offset below 2^32.
@@ -106,14 +116,22 @@ static DensePlan make_plan(void* ws, int64_t n_docs, int n_queries, int kprime, 
     // sigma away), and the sample pass + select cost a third of what ks = k' = 192 did.
     // The register-resident scan keeps one candidate segment per lane (no shared tile list), so
     // only the cost matters there: ks = 32 (spread ~1/6) halves the sample pass and the select.
-    const int ks_cap = p.packed ? 32 : 64;
+    const int ks_cap = p.packed ? dense_knobs().ks : 64;
     p.ksample = kprime < ks_cap ? kprime : ks_cap;
     // (the sample must grow with the corpus: a capped sample lets n / S * ks rows through, which
     // overflows the candidate lists of every query on a 10M-row shard)
-    // The sample pass costs ~ n * ks / aim, the scan's emit + K4's candidate read ~ aim: at 1M rows
-    // the two meet at aim = 4096 (profiles/r2_scan_tau_experiment.json), so aim follows sqrt(n)
-    // below that; never under 8 k' (k' = 128: 1024 = k' + 7 sigma of the passing count at ks = 64).
-    double aim = (p.packed ? 2896.0 : 4096.0) * sqrt((double)n_docs / 1.0e6);   // (ks / 64 under the root)
+    // The sample pass costs ~ n * ks / aim, the scan's emit + K4's candidate read ~ aim: for the scans
+    // that write every sample score the two meet at aim = 4096 at 1M rows
+    // (profiles/r2_scan_tau_experiment.json), so aim follows sqrt(n) below that; never under 8 k'
+    // (k' = 128: 1024 = k' + 7 sigma of the passing count at ks = 64).
+    // The register-resident scans' sample pass writes a lane's SAMPLE_TOP best only, so it costs its
+    // flops alone (~2.4 ns per sample row and 2048 queries) and the optimum sits lower: measured at
+    // 1M x 768 x 2048, k' = 192 (profiles/dense_threshold_pass.md), aim 2896 -> 1536 takes 75 us off the
+    // filter scan's emit and 5 off select_band for 31 more in the sample pass, and the 8 k' floor is
+    // what holds it there: 1448 sqrt(n / 1M), i.e. the floor up to 1.1M rows at k' = 192.  ks stays 32:
+    // 24 and 16 sample fewer rows (-15 / -31 us) but sit within the spread of the sum, and the
+    // passing count's spread grows to 1/5 and 1/4 of its mean.
+    double aim = (p.packed ? dense_knobs().aim_1m : 4096.0) * sqrt((double)n_docs / 1.0e6);   // (ks / 64 under the root)
     const double aim_lo = 8.0 * kprime < 4096.0 ? 8.0 * kprime : 4096.0;
     aim = aim < aim_lo ? aim_lo : aim > 4096.0 ? 4096.0 : aim;
     int64_t target = (int64_t)((double)n_docs * (double)p.ksample / aim);
@@ -132,12 +150,14 @@ static DensePlan make_plan(void* ws, int64_t n_docs, int n_queries, int kprime, 
     p.tau = A.take<float>(qpad);
     p.qerr = A.take<float>(qpad);
     if (kind != KIND_F16) p.qerr = nullptr;
-    // (cnt and tcnt are zeroed by one memset; the register-resident scan keeps one count per segment)
+    // (cnt and tcnt are zeroed by one memset; the register-resident scan keeps one count per segment
+    // and writes every one of them itself)
     p.cnt = A.take<int>(qpad * (p.packed ? QREG_MAX_SEG : 1));
     p.tcnt = A.take<int>(p.ntiles);
     p.cand = A.take<Cand>(qpad * CAND_CAP);
     p.tlist = A.take<Cand>((size_t)p.ntiles * p.tile_cap);
-    p.sample = A.take<float>(qpad * (size_t)p.sample_docs);
+    // the sample pass's output: every score (row-major), or the lanes' SAMPLE_TOP best per segment
+    p.sample = A.take<float>(p.packed ? qpad * (size_t)QREG_MAX_SEG * SAMPLE_TOP : qpad * (size_t)p.sample_docs);
     p.qfrag = A.take<_Float16>(p.packed ? qpad * (size_t)dim : 0);
     p.sel_rows = A.take<int32_t>(qpad * SEL_BIG_BAND);
     p.sel_meta = A.take<int32_t>(4 * qpad);
@@ -176,7 +196,7 @@ bool scan_nt(bool shared_rows) { return !shared_rows; }
 
 // K1 / K3: the scan of the plan's flavour in one mode.  MODE_ALL scores the sample rows for every
 // query; MODE_FILTER streams the corpus and emits the candidates (*nseg: the segments per query of
-// the register-resident scan's candidate area; the other scans fill tile lists).
+// the register-resident scan's candidate area, or of its sample area; the other scans fill tile lists).
 template <int MODE>
 static int launch_scan(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, int* nseg = nullptr) {
     constexpr bool all = MODE == MODE_ALL;
@@ -184,12 +204,13 @@ static int launch_scan(const DensePlan& P, const DenseIndex& X, const DenseBatch
     const float* tau = all ? nullptr : P.tau;
     float* smp = all ? P.sample : nullptr;
     const int64_t ld = all ? P.sample_docs : 0;
-    const int32_t* doc_coll = all ? nullptr : X.doc_coll;
-    const int32_t* query_coll = all ? nullptr : B.query_coll;
+    // (the register-resident sample pass applies the collection filter itself: it keeps no row identity)
     if (P.packed)
         return launch_scan_f16q<MODE>(X.dim, X.docs16, P.qfrag, P.ntiles, units, stride, tau,
-                                      all ? nullptr : P.cnt, all ? nullptr : P.cand, smp, ld, B.st,
-                                      nseg, doc_coll, query_coll, B.n_queries);
+                                      all ? nullptr : P.cnt, all ? nullptr : P.cand, smp, B.st,
+                                      nseg, X.doc_coll, B.query_coll, B.n_queries);
+    const int32_t* doc_coll = all ? nullptr : X.doc_coll;
+    const int32_t* query_coll = all ? nullptr : B.query_coll;
     int* tcnt = all ? nullptr : P.tcnt;
     Cand* tlist = all ? nullptr : P.tlist;
     const int tile_cap = all ? 0 : P.tile_cap;
@@ -205,21 +226,26 @@ static int launch_scan(const DensePlan& P, const DenseIndex& X, const DenseBatch
 // K0..K4 for every scan flavour (S.phase: all of it, or one side of the shards' exchange).
 static int dense_pipeline(const DensePlan& P, const DenseIndex& X, const DenseBatch& B,
                           const DensePhase& S) {
-    int rc, nseg = 0;   // nseg: see launch_scan
+    int rc, nseg = 0, sample_nseg = 0;   // see launch_scan
     if (S.phase != PIPE_FINISH) {
-        hipError_t e = hipMemsetAsync(P.cnt, 0, (char*)P.cand - (char*)P.cnt, B.st);   // cnt + tcnt
-        if (e != hipSuccess) return (int)e;
+        // cnt + tcnt.  Not for the register-resident scan: every block of it, the waves of padding
+        // queries included, ends by writing the count of each (query, segment) it owns, the blocks
+        // of a launch own all qpad x nseg of them, select_band reads no other, and tcnt is unused.
+        if (!P.packed) {
+            hipError_t e = hipMemsetAsync(P.cnt, 0, (char*)P.cand - (char*)P.cnt, B.st);
+            if (e != hipSuccess) return (int)e;
+        }
         if (P.packed && (rc = launch_pack_queries(X.dim, B.queries, B.n_queries, P.qpad, P.qfrag, P.qerr, B.st)))
             return rc;
-        if (P.sampled && (rc = launch_scan<MODE_ALL>(P, X, B))) return rc;
-        if ((rc = launch_threshold(P, X, B))) return rc;
+        if (P.sampled && (rc = launch_scan<MODE_ALL>(P, X, B, &sample_nseg))) return rc;
+        if ((rc = launch_threshold(P, X, B, P.packed ? sample_nseg : 0))) return rc;
         if ((rc = launch_scan<MODE_FILTER>(P, X, B, &nseg))) return rc;
         // (the register-resident scan writes the per-query lists itself)
         if (!P.packed && (rc = launch_bucket(P, B.st))) return rc;
     } else if (P.packed) {
         // the candidate area's layout as the filter scan of the shortlist call left it (a size query)
         if ((rc = launch_scan_f16q<MODE_FILTER, true>(X.dim, X.docs16, P.qfrag, P.ntiles, P.groups, 1,
-                                                      nullptr, nullptr, nullptr, nullptr, 0, B.st, &nseg)))
+                                                      nullptr, nullptr, nullptr, nullptr, B.st, &nseg)))
             return rc;
     }
     if ((rc = launch_band(P, X, B, S, nseg))) return rc;
@@ -445,7 +471,7 @@ extern "C" int thr_dense_scan_stamps_f16(const uint16_t* docs16, int64_t n_docs,
     int blocks = 0;
     int rc = launch_scan_f16q<MODE_FILTER, true>(
         dim, reinterpret_cast<const _Float16*>(docs16), P.qfrag, P.ntiles, P.groups, 1, P.tau, P.cnt,
-        P.cand, nullptr, 0, (hipStream_t)stream, nullptr, nullptr, nullptr, n_queries, stamps, &blocks);
+        P.cand, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, n_queries, stamps, &blocks);
     *h_n_waves = blocks * qreg_waves(dim);
     return rc;
 }

@@ -19,6 +19,8 @@ constexpr int ROW_BITS = 27;               // tile-list entries pack (query-in-t
 constexpr uint32_t ROW_MASK = (1u << ROW_BITS) - 1;
 constexpr int ROW_BITS_F16 = 25;           // f16 shortlist scans: up to 96 queries per tile -> 7 bits
 constexpr int SEL_BIG_BAND = 1024;         // rows a query's shortlist may hold (K4a -> K4b): the row stride of sel_rows
+constexpr int QREG_MAX_SEG = 1024;         // most candidate / sample segments per query of the register-resident scans
+constexpr int SAMPLE_TOP = 4;              // sample scores a lane of the register-resident scans keeps per query and segment
 constexpr int CS_BINS = 4096;              // histogram bins of the coarse selects = most values select_band ranks in their place
 
 struct Cand {
@@ -188,7 +190,7 @@ int launch_scan_f16(int dim, int nq, const float* rows32, const float* inv_norm,
 template <int MODE, bool PROF = false>
 int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int n_qtiles,
                      int64_t n_row_tiles, int64_t tile_stride, const float* tau, int* seg_cnt,
-                     Cand* cand, float* sample, int64_t sample_ld, hipStream_t st,
+                     Cand* cand, float* sample, hipStream_t st,
                      int* nseg_out = nullptr, const int32_t* doc_coll = nullptr,
                      const int32_t* query_coll = nullptr, int n_queries = 1 << 30,
                      unsigned long long* stamps = nullptr, int* n_blocks = nullptr);
@@ -197,9 +199,10 @@ int launch_pack_queries(int dim, const float* queries, int n_queries, int qpad, 
 // docs16 == null: the rounding error alone (measure_f16_error)
 int launch_quantize_f16(const float* docs, int64_t n_docs, int dim, _Float16* docs16,
                         unsigned int* max_rel_err, hipStream_t st);
-// dense_select.hip: K2 (the sampled and the unsampled form), K3b, K4a (nseg: segments per query of
-// the candidate area as the register-resident scan left it, else 0); dense_rescore.hip: K4b, both sizes
-int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& B);
+// dense_select.hip: K2 (the sampled and the unsampled form; sample_nseg: segments per query of the
+// register-resident sample pass, else 0), K3b, K4a (nseg: segments per query of the candidate area as
+// the register-resident scan left it, else 0); dense_rescore.hip: K4b, both sizes
+int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, int sample_nseg);
 int launch_bucket(const DensePlan& P, hipStream_t st);
 int launch_band(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, const DensePhase& S, int nseg);
 int launch_rescore(const DensePlan& P, const DenseIndex& X, const DenseBatch& B);

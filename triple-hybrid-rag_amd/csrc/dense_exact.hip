@@ -31,7 +31,8 @@ __global__ __launch_bounds__(EX_THREADS) void exact_slab_topk(
     const float* __restrict__ docs, const double* __restrict__ dnorm, int64_t n_docs, int dim,
     const float* __restrict__ queries, int n_queries, int k, double* __restrict__ slab_s,
     int64_t* __restrict__ slab_id, const uint32_t* __restrict__ skip_certified,
-    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll) {
+    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll,
+    int32_t* __restrict__ n_done) {
     extern __shared__ float lds_qv[];
     __shared__ double b_s[EX_CAP];
     __shared__ int64_t b_id[EX_CAP];
@@ -41,6 +42,8 @@ __global__ __launch_bounds__(EX_THREADS) void exact_slab_topk(
     __shared__ double s_qn;
     __shared__ unsigned long long s_todo;
     const int slab = blockIdx.x;
+    // the counter merge_lists adds to in the next launch starts at zero (no fill launch of the caller's)
+    if (n_done && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_done = 0;
     // queries strided over gridDim.y, at most 64 per block: in rescue mode (skip_certified) the
     // grid is small and one ballot tells the block which of its queries still need the work
     // (instead of one mostly-empty block per query)
@@ -252,7 +255,7 @@ static int exact_topk(const float* docs, const double* dnorm, int64_t n_docs, in
     int64_t* slab_id = (int64_t*)(slab_s + (size_t)n_queries * EX_SLABS * k);
     hipLaunchKernelGGL(exact_slab_topk, dim3(EX_SLABS, grid_y), dim3(EX_THREADS),
                        sizeof(float) * dim, st, docs, dnorm, n_docs, dim, queries, n_queries, k,
-                       slab_s, slab_id, certified, doc_coll, query_coll);
+                       slab_s, slab_id, certified, doc_coll, query_coll, n_rescued);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(merge_lists<false>, dim3(n_queries), dim3(256), 0, st, slab_s, slab_id,
@@ -288,8 +291,8 @@ extern "C" int thr_dense_topk_exact(const float* docs, const double* dnorm, int6
 
 // Device-side completion of thr_dense_topk[_f16]: the queries whose flags lack
 // THR_FLAG_CERTIFIED are redone on the exhaustive float64 path, in place, with no host read-back
-// (workgroups of certified queries exit at once).  *n_rescued (device int32) is incremented
-// once per redone query.
+// (workgroups of certified queries exit at once).  *n_rescued (device int32) is set to the number
+// of redone queries: zeroed by the first kernel, incremented once per redone query by the second.
 extern "C" int thr_dense_rescue(const float* docs, const double* dnorm, int64_t n_docs, int dim,
                                 int64_t id_base, const float* queries, int n_queries, int k,
                                 const int32_t* doc_coll, const int32_t* query_coll,

@@ -9,7 +9,7 @@ namespace thr {
 template <int MODE, bool PROF>
 int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int n_qtiles,
                             int64_t n_row_tiles, int64_t tile_stride, const float* tau, int* seg_cnt,
-                            Cand* cand, float* sample, int64_t sample_ld, hipStream_t st,
+                            Cand* cand, float* sample, hipStream_t st,
                             int* nseg_out, const int32_t* doc_coll,
                             const int32_t* query_coll, int n_queries,
                             unsigned long long* stamps, int* n_blocks) {
@@ -28,7 +28,7 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
     return launch_lds(dense_scan_f16qs<DIM, MODE, SHAPE>, grid, dim3(QS_NW * 64),                 \
                       QStag<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,       \
                       n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,    \
-                      sample, sample_ld, doc_coll, query_coll, n_queries);
+                      sample, doc_coll, query_coll, n_queries);
     if (stag) {
         if (dim == 512 && shape == 32) THR_QS_LAUNCH(512, 32)
         if (dim == 512) THR_QS_LAUNCH(512, 16)
@@ -40,7 +40,7 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
     return launch_lds(dense_scan_f16q<DIM, MODE, PROF, SHAPE>, grid, dim3(Q_NW * 64),             \
                       QScan<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,       \
                       n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,    \
-                      sample, sample_ld, doc_coll, query_coll, n_queries, stamps);
+                      sample, doc_coll, query_coll, n_queries, stamps);
     switch (dim) {
         case 512: if (shape == 16) THR_Q_LAUNCH(512, 16) THR_Q_LAUNCH(512, 32)
         case 768: if (shape == 16) THR_Q_LAUNCH(768, 16) THR_Q_LAUNCH(768, 32)
@@ -87,7 +87,7 @@ int launch_quantize_f16(const float* docs, int64_t n_docs, int dim, _Float16* do
 
 #define THR_INSTANTIATE(MODE, PROF)                                                                    \
     template int launch_scan_f16q<MODE, PROF>(int, const _Float16*, const _Float16*, int, int64_t, int64_t, \
-                                              const float*, int*, Cand*, float*, int64_t, hipStream_t, int*, \
+                                              const float*, int*, Cand*, float*, hipStream_t, int*, \
                                               const int32_t*, const int32_t*, int, unsigned long long*, int*);
 THR_INSTANTIATE(MODE_ALL, false)
 THR_INSTANTIATE(MODE_FILTER, false)

@@ -308,6 +308,60 @@ struct QEmit {
     }
 };
 
+// MODE_ALL (the sample pass): what a lane keeps of the sample rows it scores -- for each of its NQL
+// queries the SAMPLE_TOP largest finite scores, in registers, sorted descending (a max / min pair per
+// kept value and accumulator register; NaN -- no such row, no embedding -- counts as -inf).  No score
+// goes to memory before the end of the launch, where the lane writes its SAMPLE_TOP values per query
+// to sample[q][segment][0..SAMPLE_TOP), segment = the (row slice, lane group) index of the filter
+// scan's candidate segments.  kth_select_top takes the ks-th largest of a query's values.
+// With a collection filter (qc != -1) only the sample rows of the query's collection count: the
+// row's collection is gathered for every finite score (the padding rows of the last tile are NaN,
+// so the gather never leaves doc_coll).  That is a dependent load per finite score of a filtered
+// query, and its wait drains the DMA queue as the filter scan's gather does: paid by filtered batches
+// in the sample pass only (~1 % of the rows), and NOT measured -- no filtered batch was profiled.
+template <int SHAPE>
+struct QTop {
+    static constexpr int NQL = QAcc<SHAPE>::NQL;
+    const int32_t* doc_coll;
+    int qc[NQL];
+    float t[NQL][SAMPLE_TOP];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int u = 0; u < NQL; ++u)
+#pragma unroll
+            for (int j = 0; j < SAMPLE_TOP; ++j) t[u][j] = -INFINITY;
+    }
+    template <int X>
+    __device__ __forceinline__ void one(const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
+        constexpr int qs = QAcc<SHAPE>::template qsel<X>();
+        float x = acc.template get<X>();
+        x = x == x ? x : -INFINITY;
+        if (doc_coll && qc[qs] != -1 && x > -INFINITY) {
+            const uint32_t row = row0 + (uint32_t)QAcc<SHAPE>::template row<X>(lane);
+            if (doc_coll[row] != qc[qs]) x = -INFINITY;
+        }
+#pragma unroll
+        for (int j = 0; j < SAMPLE_TOP; ++j) {   // t[qs] stays sorted; x carries the displaced value down
+            const float hi = fmaxf(t[qs][j], x);
+            x = fminf(t[qs][j], x);
+            t[qs][j] = hi;
+        }
+    }
+    template <int X>
+    __device__ __forceinline__ void all(const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
+        if constexpr (X < QAcc<SHAPE>::NREG) {
+            one<X>(acc, row0, lane);
+            all<X + 1>(acc, row0, lane);
+        }
+    }
+    // the lane's values of query q (u-th of the lane), segment seg of nseg
+    __device__ __forceinline__ void store(float* __restrict__ sample, int u, int64_t q, int nseg, int seg) const {
+        float* dst = sample + (q * nseg + seg) * SAMPLE_TOP;
+#pragma unroll
+        for (int j = 0; j < SAMPLE_TOP; ++j) dst[j] = t[u][j];
+    }
+};
+
 // qsx_steps with the emit of the PREVIOUS row tile's accumulators threaded through it (the 4-wave
 // kernel below, MODE_FILTER): a block of that kernel has ONE wave per SIMD, so while a wave runs
 // its epilogue nothing feeds the SIMD's matrix pipe -- the stamps put that at a quarter of a half
@@ -344,7 +398,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
     const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
     int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
     int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
-    float* __restrict__ sample_scores, int64_t sample_ld,
+    float* __restrict__ sample,
     const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries,
     unsigned long long* __restrict__ stamps = nullptr) {
     using C = QScan<DIM>;
@@ -371,13 +425,17 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
     QEmit<SHAPE> em;
     em.cand = cand;
     em.doc_coll = doc_coll;
+    QTop<SHAPE> top;   // MODE_ALL
+    top.doc_coll = doc_coll;
+    top.init();
     uint32_t start[NQL];
 #pragma unroll
     for (int u = 0; u < NQL; ++u) {
         const int q = q32 * QW + A::query(lane, u);
         em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
         // collection filter of this lane's query (-1: none): checked only for rows that pass tau
-        em.qc[u] = (MODE == MODE_FILTER && query_coll && q < n_queries) ? query_coll[q] : -1;
+        // (MODE_ALL: for the sample rows with a finite score)
+        em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
         start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
         em.slot[u] = start[u];
         em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
@@ -561,30 +619,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
 
         const int64_t t = first + i * step;
         if constexpr (MODE == MODE_ALL) {
-            if constexpr (SHAPE == 32) {
-                // accumulator registers 4g..4g+3 are 4 consecutive rows: one 16-byte store each
-                float* dst = sample_scores + (int64_t)(q32 * 32 + (lane & 31)) * sample_ld + t * 32 + 4 * (lane >> 5);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float sv = acc.v[4 * g + j];
-                        v[j] = sv == sv ? sv : -INFINITY;  // NaN: no such row / no embedding
-                    }
-                    *reinterpret_cast<f32x4*>(dst + 8 * g) = v;
-                }
-            } else {
-#pragma unroll
-                for (int x = 0; x < 2 * A::NQB; ++x) {   // tile (ra, qb): rows 16 ra + 4 g .. + 4 of query 16 qb + c
-                    f32x4 v = acc.t[x];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = v[j] == v[j] ? v[j] : -INFINITY;
-                    float* dst = sample_scores + (int64_t)(q32 * QW + 16 * (x % A::NQB) + (lane & 15)) * sample_ld +
-                                 t * 32 + 16 * (x / A::NQB) + 4 * (lane >> 4);
-                    *reinterpret_cast<f32x4*>(dst) = v;
-                }
-            }
+            top.template all<0>(acc, (uint32_t)(t * tile_stride * 32), lane);
         } else {
             em.template all<0>(acc, (uint32_t)(t * tile_stride * 32), lane);
         }
@@ -597,6 +632,9 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
 #pragma unroll
         for (int u = 0; u < NQL; ++u)
             seg_cnt[(int64_t)(q32 * QW + A::query(lane, u)) * nseg + my_seg] = (int)((em.slot[u] - start[u]) / sizeof(Cand));
+    } else {   // (idle waves too: -inf for their padding queries)
+#pragma unroll
+        for (int u = 0; u < NQL; ++u) top.store(sample, u, (int64_t)q32 * QW + A::query(lane, u), nseg, my_seg);
     }
     if constexpr (PROF) {
         if (lane == 0) {
@@ -648,7 +686,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
     int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
     int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
-    float* __restrict__ sample_scores, int64_t sample_ld,
+    float* __restrict__ sample,
     const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries) {
     using C = QStag<DIM>;
     using A = QAcc<SHAPE>;
@@ -672,13 +710,17 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     QEmit<SHAPE> em;
     em.cand = cand;
     em.doc_coll = doc_coll;
+    QTop<SHAPE> top;   // MODE_ALL
+    top.doc_coll = doc_coll;
+    top.init();
     uint32_t start[NQL];
 #pragma unroll
     for (int u = 0; u < NQL; ++u) {
         const int q = q32 * 32 + A::query(lane, u);
         em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
         // collection filter of this lane's query (-1: none): checked only for rows that pass tau
-        em.qc[u] = (MODE == MODE_FILTER && query_coll && q < n_queries) ? query_coll[q] : -1;
+        // (MODE_ALL: for the sample rows with a finite score)
+        em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
         start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
         em.slot[u] = start[u];
         em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
@@ -701,35 +743,9 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
                                                               (wave + p * QS_NW) * 1024),
             16, 0, 0);
     };
-    auto emit_all = [&](const A& acc, int64_t i) {   // MODE_ALL: the sample scores of tile i
-        const int64_t t = first + i * step;
-        if constexpr (SHAPE == 32) {
-            float* dst = sample_scores + (int64_t)(q32 * 32 + (lane & 31)) * sample_ld + t * 32 + 4 * (lane >> 5);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {   // registers 4g..4g+3 are 4 consecutive rows
-                f32x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float sv = acc.v[4 * g + j];
-                    v[j] = sv == sv ? sv : -INFINITY;   // NaN: no such row / no embedding
-                }
-                *reinterpret_cast<f32x4*>(dst + 8 * g) = v;
-            }
-        } else {
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {   // tile (ra, qb): rows 16 ra + 4 g .. + 4 of query 16 qb + c
-                f32x4 v = acc.t[x];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = v[j] == v[j] ? v[j] : -INFINITY;
-                float* dst = sample_scores + (int64_t)(q32 * 32 + 16 * (x & 1) + (lane & 15)) * sample_ld +
-                             t * 32 + 16 * (x >> 1) + 4 * (lane >> 4);
-                *reinterpret_cast<f32x4*>(dst) = v;
-            }
-        }
-    };
 #define QS_EMIT(i_)                                                                                \
     if constexpr (MODE == MODE_ALL) {                                                              \
-        emit_all(acc, (i_));                                                                       \
+        top.template all<0>(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32), lane);      \
     } else {                                                                                       \
         em.template all<0>(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32), lane);       \
     }
@@ -852,6 +868,9 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
 #pragma unroll
         for (int u = 0; u < NQL; ++u)
             seg_cnt[(int64_t)(q32 * 32 + A::query(lane, u)) * nseg + my_seg] = (int)((em.slot[u] - start[u]) / sizeof(Cand));
+    } else {   // (the waves of padding queries too: -inf)
+#pragma unroll
+        for (int u = 0; u < NQL; ++u) top.store(sample, u, (int64_t)q32 * 32 + A::query(lane, u), nseg, my_seg);
     }
 }
 

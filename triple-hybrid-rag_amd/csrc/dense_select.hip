@@ -1,5 +1,6 @@
 // Dense channel, selection: K2, K3b and K4a of the pipeline (dense.hip) and the shards' common floor.
-// kth_select turns the sample scores into the scan's threshold, bucket_candidates splits a tile's
+// kth_select (kth_select_top behind the register-resident scans, whose sample pass keeps only each
+// lane's best) turns the sample scores into the scan's threshold, bucket_candidates splits a tile's
 // candidate list by query, select_band picks the rows that get a float64 score (or, before the
 // shards' exchange, the query's top-m lower bounds), dense_floor_kernel is the k-th largest of the
 // exchanged bounds.  The launch functions at the end are what dense.hip calls.
@@ -294,6 +295,77 @@ __global__ __launch_bounds__(256) void kth_select(const float* __restrict__ samp
     if (threadIdx.x == 0) tau[q] = coarse_value(key);
 }
 
+// K2 of the register-resident scans: tau[q] = the kk-th largest of the n_vals = nseg * SAMPLE_TOP
+// values their sample pass kept of query q (sample[q][segment][0..SAMPLE_TOP), -inf padded; the
+// collection filter is already applied), by the exact radix select -- a few hundred values.
+// +inf for void queries, as kth_select; -inf when fewer than kk values are finite.
+// BOUND: the kept values are a subset of the query's sample scores (a segment holds its lane's
+// SAMPLE_TOP best), so the kk-th largest of them is AT MOST the kk-th largest sample score, and
+// equal to it unless one lane saw more than SAMPLE_TOP of the sample's kk best.  At most is the safe
+// side: a lower tau lets more rows through, and the certificate only needs "the scan emitted every
+// row >= tau".
+// (The select: 8-bit digits, the keys in registers -- n_vals <= QREG_MAX_SEG * SAMPLE_TOP = 4096 is
+// at most KT_REG per thread -- and the bin of a pass found by all 256 threads, one bin each: a scan
+// over the waves instead of block_radix_select_local's walk of one thread over the histogram: with
+// so few values per block that serial walk, four times per query, would be most of the kernel.)
+constexpr int KT_REG = 16;
+static_assert(QREG_MAX_SEG * SAMPLE_TOP <= 256 * KT_REG, "kth_select_top holds every kept value in registers");
+__global__ __launch_bounds__(256) void kth_select_top(const float* __restrict__ sample, int n_vals, int kk,
+                                                      const float* __restrict__ queries, int n_queries,
+                                                      int dim, float* __restrict__ tau) {
+    __shared__ int hist[256];
+    __shared__ int wsum[4];
+    __shared__ int bc[2];
+    __shared__ int flag;
+    const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (query_is_void(queries, n_queries, dim, q, &flag)) {
+        if (t == 0) tau[q] = INFINITY;
+        return;
+    }
+    if (n_vals < kk) {
+        if (t == 0) tau[q] = -INFINITY;
+        return;
+    }
+    // thread t takes values t, t + 256, .. (the slots past n_vals are not counted)
+    uint32_t key[KT_REG];
+#pragma unroll
+    for (int u = 0; u < KT_REG; ++u) {
+        const int i = t + u * 256;
+        key[u] = fkey(i < n_vals ? sample[(int64_t)q * n_vals + i] : -INFINITY);
+    }
+    uint32_t prefix = 0, mask = 0;
+    int remaining = kk;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hist[t] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KT_REG; ++u)
+            if (t + u * 256 < n_vals && (key[u] & mask) == prefix) atomicAdd(&hist[(key[u] >> shift) & 255], 1);
+        __syncthreads();
+        // thread t owns bin 255 - t: incl = the keys in its bin and in the larger ones
+        const int mine = hist[255 - t];
+        int incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, WAVE);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        for (int x = 0; x < wave; ++x) incl += wsum[x];
+        if (incl - mine < remaining && remaining <= incl) {   // (exactly one thread: remaining <= the keys left)
+            bc[0] = 255 - t;
+            bc[1] = incl - mine;
+        }
+        __syncthreads();
+        remaining -= bc[1];
+        prefix |= (uint32_t)bc[0] << shift;
+        mask |= 255u << shift;
+    }
+    if (t == 0) tau[q] = fkey_inv(prefix);
+}
+
 // K4: shortlist (select_band), then float64 rescoring, ordering, certificate (rescore_rank,
 // dense_rescore.hip).  One block per query in each.  They were one kernel until the counters showed
 // its two halves wanting different things: the selection is a chain of dependent memory round trips
@@ -305,7 +377,7 @@ __global__ __launch_bounds__(256) void kth_select(const float* __restrict__ samp
 //          histogram pass (a slightly wider band, never a narrower one); the first 16
 //          candidates per thread stay in registers across the passes.
 constexpr int SEL_THREADS = 256;
-constexpr int SEL_REG = 16;        // candidates per thread kept in registers (4096 per query; the scan aims at ~2900)
+constexpr int SEL_REG = 16;        // candidates per thread kept in registers (4096 per query; the scan aims at ~1500 to ~2900)
 constexpr int SEL_FLAT = 8192;     // candidates of the per-lane segments addressed through a flat LDS index
 static size_t band_lds_bytes(int dim) { return sizeof(float) * dim + sizeof(int) * CS_BINS; }
 // K4a: the shortlist of one query -- which candidate rows get a float64 score.  Light on
@@ -728,8 +800,14 @@ __global__ __launch_bounds__(256) void dense_floor_kernel(const float* __restric
 
 // ---- launches (dense.hip's pipeline) ----
 // K2.  Without a sample pass (a corpus the candidate lists hold anyway: sample_docs == 0) tau = -inf.
+// sample_nseg > 0: the sample area holds the kept values of the register-resident sample pass.
 // (the register-resident scan's query image comes with the query-side error term; kth_select then skips it)
-int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& B) {
+int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& B, int sample_nseg) {
+    if (P.sampled && sample_nseg > 0) {
+        hipLaunchKernelGGL(kth_select_top, dim3(P.qpad), dim3(256), 0, B.st, (const float*)P.sample,
+                           sample_nseg * SAMPLE_TOP, P.ksample, B.queries, B.n_queries, X.dim, P.tau);
+        return launch_status();
+    }
     hipLaunchKernelGGL(kth_select, dim3(P.qpad), dim3(256), 0, B.st,
                        P.sampled ? (const float*)P.sample : nullptr, P.sample_docs, (int)P.sample_docs,
                        P.ksample, B.queries, B.n_queries, X.dim, P.tau, P.packed ? nullptr : P.qerr,

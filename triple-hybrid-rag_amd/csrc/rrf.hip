@@ -73,6 +73,54 @@ __global__ __launch_bounds__(RRF_THREADS) void rrf_fuse_kernel(
     }
     __syncthreads();
 
+    // ONE channel given (a dense-only or lexical-only step: the other two are absent), no id twice
+    // in it and a weight >= 0: every position is a first sighting, its rank is its position, and
+    // w / (k + rank) does not grow with the rank (IEEE division and multiplication are monotone),
+    // so the stable sort below would leave the channel's order as it is -- the result is written
+    // straight from the list, the same bits, without the quadratic sighting, rank and sort loops.
+    // Duplicates are found with an open-addressing table of positions in `order` (not in use yet):
+    // of two equal ids the later insert meets the earlier one.  Anything else takes the general path.
+    if ((width[0] > 0) + (width[1] > 0) + (width[2] > 0) == 1) {   // (block-uniform)
+        const int ch = width[0] ? 0 : width[1] ? 1 : 2;
+        const double w = ch == 0 ? w_lex : ch == 1 ? w_sem : w_gra;
+        for (int i = t; i < RRF_SLOTS; i += RRF_THREADS) order[i] = -1;
+        __syncthreads();
+        const int n1 = len[ch];
+        int dup = 0;
+        if (t < n1) {
+            const int64_t id = L[ch][t];
+            uint32_t h = (uint32_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> 40);
+            for (;;) {
+                h &= RRF_SLOTS - 1;
+                const int prev = atomicCAS(&order[h], -1, t);
+                if (prev == -1) break;
+                if (L[ch][prev] == id) {
+                    dup = 1;
+                    break;
+                }
+                ++h;
+            }
+        }
+        if (!__syncthreads_or(dup) && w >= 0.0) {
+            for (int i = t; i < top_k; i += RRF_THREADS) {
+                const bool ok = i < n1;
+                const int r = i + 1;
+                double score = -INFINITY;
+                if (ok) {
+                    if (MODE == RRF_RAG2) score = __dadd_rn(0.0, __ddiv_rn(w, (double)(rrf_k + r)));
+                    else score = __dadd_rn(0.0, __dmul_rn(w, __ddiv_rn(1.0, (double)(rrf_k + r))));
+                }
+                out_ids[(int64_t)q * top_k + i] = ok ? L[ch][i] : -1;
+                out_scores[(int64_t)q * top_k + i] = score;
+                if (out_ranks)
+                    for (int c = 0; c < 3; ++c)
+                        out_ranks[((int64_t)q * top_k + i) * 3 + c] = (ok && c == ch) ? r : 0;
+            }
+            if (t == 0) out_counts[q] = n1 < top_k ? n1 : top_k;
+            return;
+        }
+    }
+
     // first sighting flags, channel by channel, and their running count = sighting position
     bool nw[3];
     int within[3];
