@@ -430,7 +430,12 @@ int thr_bm25_topk(const int64_t *rowptr /* [V+1] */, const int32_t *post_doc,
  * (src/voice_agent/rag2/graph_search.py:290-418; score form
  * triple-hybrid-rag/src/triple_hybrid_rag/graph/puppygraph.py:152-167).
  * men_chunk holds GLOBAL chunk ids; only [chunk_base, chunk_base+n_chunks)
- * are scored (document sharding).  ``workspace`` >= thr_graph_workspace_bytes. */
+ * are scored (document sharding).  ``workspace`` >= thr_graph_workspace_bytes.
+ * hops is 0..8 (more is THR_ERR_INVALID), max_seeds 1..THR_GRAPH_MAX_SEEDS, k 1..THR_TOPK_MAX.
+ * Edge targets (ent_col) and seeds outside [0, n_entities) are ignored: such an edge leads
+ * nowhere, such a seed is padding like -1.  In thr_graph_topk a mention of a chunk outside the
+ * shard still takes one of a tier's contribution slots (it counts towards the 2048 / 8192 below
+ * and for nothing in the scores); in thr_graph_topk_scoped only the mentions a query keeps do. */
 size_t thr_graph_workspace_bytes(int n_queries, int64_t n_entities /* 0: no fallback tier */);
 /* Three tiers, no host round trip: small on-chip capacities, full on-chip capacities for the
  * queries that overflowed them, and -- when the TRANSPOSED mention CSR is given (chunk ->
