@@ -145,7 +145,30 @@ int thr_dense_rescue(const float *docs, const double *dnorm, int64_t n_docs, int
  *                   doc_rel_err = max_d ||fp16(d) - d|| / ||d||, +inf when a value leaves the
  *                   float16 range, which thr_dense_topk_f16 rejects; 64 queries per pass, 32 at
  *                   dim 1024).
- * dim in {512, 768, 1024}. */
+ * dim in {512, 768, 1024}: the tuned kernels.  With docs16 == NULL every other row length that is
+ * a multiple of THR_DENSE_ANYDIM_STEP up to THR_DENSE_ANYDIM_MAX is taken too, by a third flavour:
+ *   the runtime-dim scan: the same interface as the docs16 == NULL scan (float32 rows rounded in
+ *                   registers, no copy, doc_rel_err as measured by thr_dense_quantize_f16 with
+ *                   docs16 == NULL, which takes these lengths), one v_mfma_f32_16x16x32_f16 per 32
+ *                   dims in a run-time loop; the query tile stays in LDS as float16, so its size
+ *                   follows the row length: 64 queries per pass up to dim 768, 32 up to 1536, 16
+ *                   beyond (thr_dense_f16_query_tile reports it).  The legacy 4000-d store
+ *                   (20260113_halfvec_4000.sql:70-105) and RAG2_EMBED_DIM_STORE settings other than
+ *                   the default (config.py:292) are what it is for.
+ * With docs16 != NULL such a length returns THR_ERR_UNSUPPORTED (sizes: 0). */
+#define THR_DENSE_ANYDIM_STEP 32
+#define THR_DENSE_ANYDIM_MAX 4096
+/* Which kernel serves docs16 == NULL calls of the CALLING THREAD at dim 512 / 768 / 1024, where both
+ * exist: THR_DENSE_F16_BY_DIM (the default: the tuned one) or THR_DENSE_F16_ANYDIM (the runtime-dim
+ * scan, for comparing the two at one shape).  Returns the previous selection; any other value only
+ * queries.  Sizes and results are the same either way: the two scans have the same query tile at
+ * these three lengths (64, 64, 32), so the plan, the workspace and the candidate lists that
+ * thr_dense_shortlist_f16 leaves for thr_dense_finish_f16 do not depend on the selection -- a pair of
+ * calls made under different selections is still a pair.  (The library checks that equality and
+ * ignores the selection should it ever not hold.)  A C caller that never calls this never sees it. */
+#define THR_DENSE_F16_BY_DIM 0
+#define THR_DENSE_F16_ANYDIM 1
+int thr_dense_f16_select(int flavour);
 size_t thr_dense_f16_copy_bytes(int64_t n_docs, int dim);
 /* queries per workgroup (= per pass over a row slice) of the f16 scan */
 int thr_dense_f16_query_tile(int dim, int packed /* docs16 != NULL */, int n_queries);

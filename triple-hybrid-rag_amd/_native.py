@@ -8,6 +8,7 @@ any kernel is launched.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Tuple
@@ -20,6 +21,9 @@ THR_FLAG_CERTIFIED = 1
 THR_FLAG_OVERFLOW = 2
 THR_FLAG_EXACT = 4
 THR_DENSE_MAX_K = 256
+THR_DENSE_ANYDIM_STEP = 32      # the runtime-dim f16 scan: row lengths that are a multiple of this ...
+THR_DENSE_ANYDIM_MAX = 4096     # ... up to this
+THR_DENSE_F16_BY_DIM, THR_DENSE_F16_ANYDIM = 0, 1   # thr_dense_f16_select
 THR_BM25_MAX_TERMS = 32
 THR_BM25_MAX_QUERIES = 1 << 20
 THR_GRAPH_MAX_SEEDS = 16
@@ -61,6 +65,7 @@ _SIGNATURES = {
     "thr_dense_f16_copy_bytes": (_sz, [_i64, _i32]),
     "thr_dense_f16_query_tile": (_i32, [_i32, _i32, _i32]),
     "thr_dense_f16_max_queries": (_i32, [_i32, _i32]),
+    "thr_dense_f16_select": (_i32, [_i32]),
     "thr_dense_topk_f16": (_i32, [_vp, _vp, _dbl, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32,
                                   _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_dense_shortlist_f16": (_i32, [_vp, _vp, _dbl, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp,
@@ -282,6 +287,26 @@ def dense_f16_query_tile(dim: int, packed: bool, n_queries: int) -> int:
 def dense_f16_max_queries(dim: int, packed: bool) -> int:
     """Largest batch of one thr_dense_topk_f16 call (32-bit candidate-segment offsets)."""
     return int(load().thr_dense_f16_max_queries(dim, 1 if packed else 0))
+
+
+def dense_anydim_ok(dim: int) -> bool:
+    """Row lengths the runtime-dim f16 scan (shortlist="f16-anydim") takes."""
+    return THR_DENSE_ANYDIM_STEP <= dim <= THR_DENSE_ANYDIM_MAX and dim % THR_DENSE_ANYDIM_STEP == 0
+
+
+@contextlib.contextmanager
+def dense_f16_flavour(anydim: bool):
+    """The f16 calls (docs16 None) made inside run the runtime-dim scan at dim 512 / 768 / 1024 too,
+    where the tuned kernel is the default (thr_dense_f16_select: per calling thread, restored on exit);
+    at every other length it is the only one and nothing is switched."""
+    if not anydim:
+        yield
+        return
+    before = load().thr_dense_f16_select(THR_DENSE_F16_ANYDIM)
+    try:
+        yield
+    finally:
+        load().thr_dense_f16_select(before)
 
 
 def dense_rescue_workspace_bytes(n_queries: int, k: int) -> int:

@@ -95,15 +95,27 @@ int qreg_max_queries(int dim) {
 }
 
 
+// Which scan streams the float32 rows of an f16 call without a copy: the tuned dense_scan_f16 at the row
+// lengths it is instantiated for, dense_scan_anydim at every other one it takes -- and at those three too
+// while the calling thread has selected it (thr_dense_f16_select: the A/B of both kernels at one shape).
+static thread_local int f16_selected = THR_DENSE_F16_BY_DIM;
+static bool f16_tuned_dim(int dim) { return dim == 512 || dim == 768 || dim == 1024; }
+static bool f16_dim_ok(int dim, bool packed) { return f16_tuned_dim(dim) || (!packed && anydim_ok(dim)); }
+static bool f16_anydim(int dim, bool packed) {
+    return !packed && anydim_ok(dim) && (!f16_tuned_dim(dim) || f16_selected == THR_DENSE_F16_ANYDIM);
+}
+
 // The work plan of a batch and its workspace carved from `ws`; from null, the plan and the size alone.
 static DensePlan make_plan(void* ws, int64_t n_docs, int n_queries, int kprime, int kind, int dim,
                            bool packed) {
     DensePlan p;
     p.kind = kind;
     p.packed = kind == KIND_F16 && packed;
-    p.nq = (kind == KIND_F16 && !p.packed) ? f16_pick_nq(dim) : 1;
+    p.anydim = kind == KIND_F16 && f16_anydim(dim, p.packed);
+    p.nq = (kind == KIND_F16 && !p.packed && !p.anydim) ? f16_pick_nq(dim) : 1;
     p.row_bits = (kind == KIND_F16 && !p.packed) ? ROW_BITS_F16 : ROW_BITS;
     p.qtile = p.packed ? qreg_qw(dim) * qreg_waves(dim)
+              : p.anydim ? anydim_qt(dim)
               : kind == KIND_F16 ? 32 * p.nq : MF_QT;
     p.ntiles = (n_queries + p.qtile - 1) / p.qtile;
     p.qpad = p.ntiles * p.qtile;
@@ -214,6 +226,10 @@ static int launch_scan(const DensePlan& P, const DenseIndex& X, const DenseBatch
     int* tcnt = all ? nullptr : P.tcnt;
     Cand* tlist = all ? nullptr : P.tlist;
     const int tile_cap = all ? 0 : P.tile_cap;
+    if (P.anydim)
+        return launch_scan_anydim<MODE>(X.dim, X.docs, X.inv_norm, X.n_docs, B.queries, B.n_queries, P.ntiles,
+                                        units, stride, tau, tcnt, tlist, tile_cap, smp, ld, B.st, doc_coll,
+                                        query_coll);
     if (P.kind == KIND_F16)
         return launch_scan_f16<MODE>(X.dim, P.nq, X.docs, X.inv_norm, X.n_docs, B.queries, B.n_queries,
                                      P.ntiles, units, stride, tau, tcnt, tlist, tile_cap, smp, ld, B.st,
@@ -298,19 +314,30 @@ extern "C" int thr_dense_topk(const float* docs, const double* dnorm, const floa
 extern "C" size_t thr_dense_f16_workspace_bytes(int64_t n_docs, int dim, int n_queries,
                                                 int kprime) {
     if (n_docs <= 0 || n_queries <= 0) return 0;
+    // (the two scans of float32 rows have the same query tile where both exist: one size serves either)
     const size_t a = make_plan(nullptr, n_docs, n_queries, kprime, KIND_F16, dim, false).total;
+    if (anydim_ok(dim) && !f16_tuned_dim(dim)) return a;   // (no copy scan at such a length)
     const size_t b = make_plan(nullptr, n_docs, n_queries, kprime, KIND_F16, dim, true).total;
     return a > b ? a : b;
 }
 
+extern "C" int thr_dense_f16_select(int flavour) {
+    const int before = f16_selected;
+    // both scans must plan the same query tile where the selection chooses between them
+    if (!f16_tiles_agree()) return before;
+    if (flavour == THR_DENSE_F16_BY_DIM || flavour == THR_DENSE_F16_ANYDIM) f16_selected = flavour;
+    return before;
+}
+
 extern "C" int thr_dense_f16_max_queries(int dim, int packed) {
-    if (dim != 512 && dim != 768 && dim != 1024) return 0;
+    if (!f16_dim_ok(dim, packed != 0)) return 0;
     return packed ? qreg_max_queries(dim) : INT32_MAX;
 }
 
 extern "C" int thr_dense_f16_query_tile(int dim, int packed, int n_queries) {
-    if (dim != 512 && dim != 768 && dim != 1024) return 0;
+    if (!f16_dim_ok(dim, packed != 0)) return 0;
     (void)n_queries;
+    if (f16_anydim(dim, packed != 0)) return anydim_qt(dim);
     return packed ? qreg_qw(dim) * qreg_waves(dim) : 32 * f16_pick_nq(dim);
 }
 
@@ -323,7 +350,8 @@ extern "C" int thr_dense_quantize_f16(const float* docs, int64_t n_docs, int dim
                                       float* max_rel_err, thr_stream_t stream) {
     clear_status();
     THR_RETURN_IF(!docs || !max_rel_err || n_docs <= 0 || dim <= 0, THR_ERR_INVALID);
-    THR_RETURN_IF(dim % 64 != 0, THR_ERR_UNSUPPORTED);
+    // (the copy is written in 64-dim stages; measuring alone takes what dense_scan_anydim takes)
+    THR_RETURN_IF(docs16 ? dim % 64 != 0 : dim % THR_DENSE_ANYDIM_STEP != 0, THR_ERR_UNSUPPORTED);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(max_rel_err, 0, sizeof(float), st);
     if (e != hipSuccess) return (int)e;
@@ -336,7 +364,7 @@ static int f16_args_ok(const float* docs, const uint16_t* docs16, double doc_rel
     (void)docs;
     THR_RETURN_IF((query_coll != nullptr) != (doc_coll != nullptr), THR_ERR_INVALID);
     THR_RETURN_IF(!(doc_rel_err >= 0.0) || !(doc_rel_err < 1.0), THR_ERR_INVALID);
-    THR_RETURN_IF(dim != 512 && dim != 768 && dim != 1024, THR_ERR_UNSUPPORTED);
+    THR_RETURN_IF(!f16_dim_ok(dim, docs16 != nullptr), THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(n_docs >= (int64_t)1 << ROW_BITS_F16, THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(docs16 != nullptr && n_queries > qreg_max_queries(dim), THR_ERR_UNSUPPORTED);
     return THR_OK;
@@ -444,7 +472,7 @@ extern "C" int thr_dense_scan_probe_f16(const float* docs, const uint16_t* docs1
                                         thr_stream_t stream) {
     clear_status();
     THR_RETURN_IF((!docs16 && !docs) || !inv_norm || !queries || !workspace, THR_ERR_INVALID);
-    THR_RETURN_IF(dim != 512 && dim != 768 && dim != 1024, THR_ERR_UNSUPPORTED);
+    THR_RETURN_IF(!f16_dim_ok(dim, docs16 != nullptr), THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(n_docs <= 0 || n_docs >= (int64_t)1 << ROW_BITS_F16 || n_queries <= 0,
                   THR_ERR_INVALID);
     THR_RETURN_IF(docs16 != nullptr && n_queries > qreg_max_queries(dim), THR_ERR_UNSUPPORTED);

@@ -101,6 +101,26 @@ inline size_t f16_lds_bytes(int dim, int nq) {
 }
 inline int f16_pick_nq(int dim) { return f16_lds_bytes(dim, 2) <= 160 * 1024 ? 2 : 1; }
 
+// runtime-dim f16 scan (dense_scan_anydim): any row length that is a multiple of THR_DENSE_ANYDIM_STEP up to
+// THR_DENSE_ANYDIM_MAX; queries per tile by row length -- the tile ([QT][dim] float16) stays in LDS beside
+// the waves' candidate buffers within the CU's 160 KiB (16 x 4096 x 2 B = 128 KiB + 16 KiB)
+inline bool anydim_ok(int dim) {
+    return dim >= THR_DENSE_ANYDIM_STEP && dim <= THR_DENSE_ANYDIM_MAX && dim % THR_DENSE_ANYDIM_STEP == 0;
+}
+// (at 512 / 768 / 1024, where thr_dense_f16_select lets either scan of float32 rows serve a call, this is
+// 32 * f16_pick_nq(dim): a plan, its workspace and the candidate lists a shortlist call leaves for its
+// finish call do not depend on the selection -- asserted below)
+inline int anydim_qt(int dim) { return dim <= 768 ? 64 : dim <= 1536 ? 32 : 16; }
+inline size_t anydim_lds_bytes(int dim) {
+    return sizeof(_Float16) * (size_t)anydim_qt(dim) * (size_t)dim + sizeof(Cand) * WBUF * H_WAVES;
+}
+
+inline bool f16_tiles_agree() {
+    for (int dim : {512, 768, 1024})
+        if (anydim_qt(dim) != 32 * f16_pick_nq(dim)) return false;
+    return true;
+}
+
 // fp32 error bound of the MFMA scans, relative to ||q||*||d||, in units of 2^-24: a dim-long fma chain
 inline double scan_eps(int dim) {
     const double u = 5.9604644775390625e-08;
@@ -112,6 +132,7 @@ inline double scan_eps(int dim) {
 constexpr int KIND_F32 = 0, KIND_F16 = 1;
 struct DensePlan {
     int kind;      // KIND_F32: float32 MFMA scan; KIND_F16: an f16 MFMA scan
+    bool anydim;   // KIND_F16, not packed: dense_scan_anydim (row length at run time) in the place of dense_scan_f16
     bool packed;   // KIND_F16 only: dense_scan_f16q[s] over the fragment-major copy (queries in registers,
                    // rows through LDS; the candidate area is written in per-lane segments), else float32
                    // rows rounded in flight
@@ -173,7 +194,8 @@ dim3 scan_grid(int ntiles, int64_t n_row_tiles, int waves, bool* shared_rows, in
                int m_cap = 64);
 bool scan_nt(bool shared_rows);
 
-// dense_scan_mfma.hip, dense_scan_f16.hip, dense_scan_f16q.hip: MODE_ALL and MODE_FILTER of each
+// dense_scan_mfma.hip, dense_scan_f16.hip, dense_scan_anydim.hip, dense_scan_f16q.hip: MODE_ALL and
+// MODE_FILTER of each
 template <int MODE>
 int launch_scan_mfma(int dim, const float* docs, const float* inv_norm, int64_t n_docs,
                      const float* queries, int n_queries, int ntiles, int64_t n_row_tiles,
@@ -186,6 +208,12 @@ int launch_scan_f16(int dim, int nq, const float* rows32, const float* inv_norm,
                     int64_t tile_stride, const float* tau, int* tile_cnt, Cand* tile_list,
                     int tile_cap, float* sample, int64_t sample_ld, hipStream_t st,
                     const int32_t* doc_coll = nullptr, const int32_t* query_coll = nullptr);
+template <int MODE>
+int launch_scan_anydim(int dim, const float* rows32, const float* inv_norm, int64_t n_docs,
+                       const float* queries, int n_queries, int ntiles, int64_t n_row_tiles,
+                       int64_t tile_stride, const float* tau, int* tile_cnt, Cand* tile_list,
+                       int tile_cap, float* sample, int64_t sample_ld, hipStream_t st,
+                       const int32_t* doc_coll = nullptr, const int32_t* query_coll = nullptr);
 // (PROF: the stamped kernel, MODE_FILTER only; without `stamps` a size query)
 template <int MODE, bool PROF = false>
 int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int n_qtiles,

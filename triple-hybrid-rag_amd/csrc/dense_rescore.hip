@@ -23,8 +23,11 @@ static size_t rescore_lds_bytes(int dim) {   // the query as float64 | the waves
 // One pass of a wave over its (up to) 8 U staged rows: U row groups of 8 per 32-dim chunk, 16 / U
 // (at most 8) chunks of them in flight in registers.  Lanes of the groups that are not staged
 // compute on stale LDS words; their slots are beyond the list and nothing reads the result.
-// dim / 32 is a multiple of 8 for every row length the scans are built for.
-template <int U>
+// dim / 32 is a multiple of 8 for every row length the tuned scans are built for; TAIL is the form for
+// the other lengths of dense_scan_anydim (any dim / 32 >= 1): the chunks in flight never pass the
+// row's last one and the trip of a chunk that does not exist is skipped (wave-uniform), so the sum
+// is the same sequential one in dimension order.
+template <int U, bool TAIL = false>
 //
 // dot += x * y as ONE v_fma_f64 per element: the product of two float32 values is exact in
 // float64 (48 significant bits), so fma(x, y, dot) rounds the same real number as the oracle's
@@ -37,13 +40,14 @@ __device__ __forceinline__ double rescore_pass(const f32x4* (&rp)[8], f32x4* sta
 #pragma unroll
     for (int dd = 0; dd < D; ++dd)
 #pragma unroll
-        for (int u = 0; u < U; ++u) nxt[dd][u] = rp[u][8 * dd];   // (nchunk >= D)
+        for (int u = 0; u < U; ++u) nxt[dd][u] = rp[u][8 * (TAIL && dd >= nchunk ? nchunk - 1 : dd)];   // (else nchunk >= D)
     double dot = 0.0;
 #pragma unroll 1
     for (int ck0 = 0; ck0 < nchunk; ck0 += D) {
 #pragma unroll
         for (int dd = 0; dd < D; ++dd) {
             const int ck = ck0 + dd;
+            if (TAIL && ck >= nchunk) break;
 #pragma unroll
             for (int u = 0; u < U; ++u) stage[(lrow + 8 * u) * RS_STRIDE + lch] = nxt[dd][u];
             // (the last trips re-request the last chunk)
@@ -69,7 +73,8 @@ __device__ __forceinline__ double rescore_pass(const f32x4* (&rp)[8], f32x4* sta
     return dot;
 }
 
-template <int NB>
+// TAIL: rescore_pass's tail form, for the row lengths of dense_scan_anydim with dim % 256 != 0
+template <int NB, bool TAIL = false>
 __global__ __launch_bounds__(RR_THREADS, 3) void rescore_rank(
     const float* __restrict__ docs, const double* __restrict__ dnorm, int dim, int64_t id_base,
     const float* __restrict__ queries, int k, double eps32, double doc_relerr,
@@ -127,10 +132,10 @@ __global__ __launch_bounds__(RR_THREADS, 3) void rescore_rank(
         // chunks of them in flight instead -- the pass is a chain of memory round trips.
         const int groups = rem / RR_WAVES / 8 + 1;
         double dot;
-        if (groups <= 1) dot = rescore_pass<1>(rp, stage, q64, nchunk, lane, lrow, lch);
-        else if (groups <= 2) dot = rescore_pass<2>(rp, stage, q64, nchunk, lane, lrow, lch);
-        else if (groups <= 4) dot = rescore_pass<4>(rp, stage, q64, nchunk, lane, lrow, lch);
-        else dot = rescore_pass<8>(rp, stage, q64, nchunk, lane, lrow, lch);
+        if (groups <= 1) dot = rescore_pass<1, TAIL>(rp, stage, q64, nchunk, lane, lrow, lch);
+        else if (groups <= 2) dot = rescore_pass<2, TAIL>(rp, stage, q64, nchunk, lane, lrow, lch);
+        else if (groups <= 4) dot = rescore_pass<4, TAIL>(rp, stage, q64, nchunk, lane, lrow, lch);
+        else dot = rescore_pass<8, TAIL>(rp, stage, q64, nchunk, lane, lrow, lch);
         if (jm < ns) s_s[jm] = dot;               // the raw dot product for now
         else if (jm == ns) s_qn = __dsqrt_rn(dot);  // ||q||
     }
@@ -191,14 +196,27 @@ __global__ __launch_bounds__(RR_THREADS, 3) void rescore_rank(
     }
 }
 
-// K4b: every query whose shortlist fits 256 rows, then the few whose band was wider.
+// K4b: every query whose shortlist fits 256 rows, then the few whose band was wider.  dim % 256 == 0:
+// the instantiation without the tail.  Beyond dim 1024 the query as float64 and the stage tiles (50 KiB
+// of dynamic LDS at dim 4096) pass 64 KiB together with the 1024-row kernel's 32 KiB of static lists:
+// those launches raise the function attribute first.
 int launch_rescore(const DensePlan& P, const DenseIndex& X, const DenseBatch& B) {
-    for (auto kern : {rescore_rank<THR_DENSE_MAX_K>, rescore_rank<SEL_BIG_BAND>}) {
-        hipLaunchKernelGGL(kern, dim3(B.n_queries), dim3(RR_THREADS), rescore_lds_bytes(X.dim), B.st,
-                           X.docs, X.dnorm, X.dim, X.id_base, B.queries, B.k, scan_eps(X.dim),
-                           X.doc_rel_err, P.qerr, P.sel_rows, P.sel_meta, B.out_scores, B.out_ids,
-                           B.out_counts, B.out_flags);
-        const int rc = launch_status();
+    const bool tail = X.dim % 256 != 0, big_lds = X.dim > 1024;
+    for (auto kern : {tail ? rescore_rank<THR_DENSE_MAX_K, true> : rescore_rank<THR_DENSE_MAX_K, false>,
+                      tail ? rescore_rank<SEL_BIG_BAND, true> : rescore_rank<SEL_BIG_BAND, false>}) {
+        int rc;
+        if (big_lds) {
+            rc = launch_lds(kern, dim3(B.n_queries), dim3(RR_THREADS), rescore_lds_bytes(X.dim), B.st,
+                            X.docs, X.dnorm, X.dim, X.id_base, B.queries, B.k, scan_eps(X.dim),
+                            X.doc_rel_err, (const float*)P.qerr, (const int32_t*)P.sel_rows,
+                            (const int32_t*)P.sel_meta, B.out_scores, B.out_ids, B.out_counts, B.out_flags);
+        } else {
+            hipLaunchKernelGGL(kern, dim3(B.n_queries), dim3(RR_THREADS), rescore_lds_bytes(X.dim), B.st,
+                               X.docs, X.dnorm, X.dim, X.id_base, B.queries, B.k, scan_eps(X.dim),
+                               X.doc_rel_err, P.qerr, P.sel_rows, P.sel_meta, B.out_scores, B.out_ids,
+                               B.out_counts, B.out_flags);
+            rc = launch_status();
+        }
         if (rc) return rc;
     }
     return THR_OK;

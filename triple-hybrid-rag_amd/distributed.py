@@ -152,7 +152,7 @@ class ShardedIndex:
         # shards agree once, here, and the floor is used only if all of them can
         self.floor = floor
         if self.world > 1 and floor:
-            ok = torch.tensor([1 if getattr(local, "shortlist", None) in ("f16", "f16-inline") else 0],
+            ok = torch.tensor([1 if getattr(local, "shortlist", None) in ("f16", "f16-inline", "f16-anydim") else 0],
                               dtype=torch.int32,
                               device="cpu" if dist.get_backend(group) == "gloo" else local.device)
             dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)
@@ -171,7 +171,7 @@ class ShardedIndex:
                             "(deletes from a document-sharded index are out of scope)")
 
     def _floor_exchange(self):
-        if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline"):
+        if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline", "f16-anydim"):
             return None
         if self.world > 4096:   # (the band kernel holds the shards' G * m bounds in 4096 LDS words)
             return None

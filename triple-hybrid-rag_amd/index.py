@@ -95,7 +95,7 @@ class GpuIndex(ScopedSearch, MutableIndex):
         self._mutations = 0     # appends + deletes so far (index_build.save: the host arrays are stale)
 
     # ------------------------------------------------------------ builders
-    SHORTLISTS = ("auto", "f32", "f16", "f16-inline", "exact")
+    SHORTLISTS = ("auto", "f32", "f16", "f16-inline", "f16-anydim", "exact")
     F16_DIMS = (512, 768, 1024)
     SCAN_DIMS = (256, 512, 768, 1024)   # row lengths the streaming shortlist scans are built for
     AUTO_COPY_FRACTION = 0.25    # of the device's memory: every shard the f16 scans can index (2^25 rows)
@@ -110,6 +110,11 @@ class GpuIndex(ScopedSearch, MutableIndex):
           "f16-inline" float32 rows rounded to float16 in registers, f16 matrix cores
                        (64 queries per pass, no extra memory);
           "f16"        additionally keeps a float16 copy of the rows and streams that;
+          "f16-anydim" as "f16-inline" (rows rounded in registers, no copy) by the scan that takes the row
+                       length at run time: any multiple of 32 up to 4096 -- 1536-, 2048-, 3072-d models,
+                       the 4000-d legacy store -- 64 queries per pass up to 768 dims, 32 up to 1536, 16
+                       beyond.  Opt-in: "auto" never picks it; at 512 / 768 / 1024 it runs beside the
+                       tuned kernels for comparison;
           "exact"      no shortlist pass: every row scored in float64 (thr_dense_topk_exact) -- any
                        row length that is a multiple of 4;
           ``derived``: the saved float16 image of a loaded index (export_derived), reused when
@@ -130,12 +135,19 @@ class GpuIndex(ScopedSearch, MutableIndex):
         self.dnorm, self.inv_norm = N.doc_norms(self.docs)
         self.docs16, self.doc_rel_err = (None, 0.0)
         auto = self._shortlist_auto = shortlist == "auto"
-        if self.dim not in self.SCAN_DIMS and shortlist != "exact":
+        if shortlist == "f16-anydim":
+            if not N.dense_anydim_ok(self.dim) or self.n_docs >= self.F16_MAX_ROWS:
+                raise N.NativeError(f"shortlist='f16-anydim' needs a row length that is a multiple of "
+                                    f"{N.THR_DENSE_ANYDIM_STEP} up to {N.THR_DENSE_ANYDIM_MAX} (got {self.dim}) "
+                                    f"and fewer than {self.F16_MAX_ROWS} rows")
+        elif self.dim not in self.SCAN_DIMS and shortlist != "exact":
             if not auto:
                 raise N.NativeError(f"shortlist={shortlist!r} needs a row length in {self.SCAN_DIMS}, got "
                                     f"{self.dim}: use shortlist='exact' (or 'auto')")
             log.warning("dense rows of %d dims: no streaming scan is built for that length, every search "
-                        "scores all %d rows in float64 (thr_dense_topk_exact)", self.dim, self.n_docs)
+                        "scores all %d rows in float64 (thr_dense_topk_exact)%s", self.dim, self.n_docs,
+                        "; shortlist='f16-anydim' scans it on the f16 matrix cores"
+                        if N.dense_anydim_ok(self.dim) else "")
             shortlist, auto = "exact", False
         if shortlist == "exact":
             self.shortlist = shortlist
@@ -161,7 +173,8 @@ class GpuIndex(ScopedSearch, MutableIndex):
             if not np.isfinite(self.doc_rel_err) or self.doc_rel_err > self.F16_MAX_REL_ERR:
                 if not auto:
                     raise N.NativeError("rows do not fit float16 (values >= 65504 or mostly below "
-                                        "6e-5 in magnitude): use shortlist='f32'")
+                                        "6e-5 in magnitude): use shortlist='f32'" +
+                                        ("" if self.dim in self.SCAN_DIMS else " or 'exact'"))
                 shortlist, self.docs16, self.doc_rel_err = "f32", None, 0.0
         self.shortlist = shortlist
         return self
@@ -385,16 +398,20 @@ class GpuIndex(ScopedSearch, MutableIndex):
         if self.shortlist != "f32":
             if floor_exchange is not None:
                 exchange, n_shards = floor_exchange
-                lb = N.dense_shortlist_f16(self.docs, self.docs16, self.doc_rel_err, self.inv_norm,
-                                           queries, kp, floor_width(k, n_shards), ws,
-                                           doc_coll=dc, query_coll=qc)
-                S, I, cnt, flg = N.dense_finish_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
-                                                    self.inv_norm, queries, k, kp, None, self.doc_base,
-                                                    ws, doc_coll=dc, query_coll=qc, lb_all=exchange(lb))
+                with self._f16_flavour():
+                    lb = N.dense_shortlist_f16(self.docs, self.docs16, self.doc_rel_err, self.inv_norm,
+                                               queries, kp, floor_width(k, n_shards), ws,
+                                               doc_coll=dc, query_coll=qc)
+                lb_all = exchange(lb)
+                with self._f16_flavour():
+                    S, I, cnt, flg = N.dense_finish_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
+                                                        self.inv_norm, queries, k, kp, None, self.doc_base,
+                                                        ws, doc_coll=dc, query_coll=qc, lb_all=lb_all)
             else:
-                S, I, cnt, flg = N.dense_topk_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
-                                                  self.inv_norm, queries, k, kp, self.doc_base, ws,
-                                                  doc_coll=dc, query_coll=qc)
+                with self._f16_flavour():
+                    S, I, cnt, flg = N.dense_topk_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
+                                                      self.inv_norm, queries, k, kp, self.doc_base, ws,
+                                                      doc_coll=dc, query_coll=qc)
         else:
             S, I, cnt, flg = N.dense_topk(self.docs, self.dnorm, self.inv_norm, queries, k, kp,
                                           self.doc_base, ws, doc_coll=dc, query_coll=qc)
@@ -408,8 +425,13 @@ class GpuIndex(ScopedSearch, MutableIndex):
     # The two halves of dense_search(floor_exchange=...) on their own, for a caller that holds
     # several shards in ONE process (tests, bench.py's shard proxy): shortlist on every shard,
     # stack the results, thr_dense_floor, finish on every shard.
+    def _f16_flavour(self):
+        """The native f16 calls of this index run under it: "f16-anydim" selects the runtime-dim scan at
+        the row lengths where the tuned kernel is the default."""
+        return N.dense_f16_flavour(self.shortlist == "f16-anydim")
+
     def _f16_call(self, queries, k, kprime, collections):
-        if self.shortlist not in ("f16", "f16-inline"):
+        if self.shortlist not in ("f16", "f16-inline", "f16-anydim"):
             raise N.NativeError("the shard floor is built for the f16 scans")
         queries = self._t(queries, torch.float32)
         if queries.shape[0] > self.max_batch():
@@ -424,8 +446,9 @@ class GpuIndex(ScopedSearch, MutableIndex):
                         collections=None) -> torch.Tensor:
         queries, kp, ws, dc, qc = self._f16_call(queries, k, kprime, collections)
         self._shortlist_of = None
-        lb = N.dense_shortlist_f16(self.docs, self.docs16, self.doc_rel_err, self.inv_norm, queries, kp,
-                                   floor_width(k, n_shards), ws, doc_coll=dc, query_coll=qc)
+        with self._f16_flavour():
+            lb = N.dense_shortlist_f16(self.docs, self.docs16, self.doc_rel_err, self.inv_norm, queries, kp,
+                                       floor_width(k, n_shards), ws, doc_coll=dc, query_coll=qc)
         # what the candidate lists in the workspace belong to: dense_finish refuses anything else
         self._shortlist_of = (queries.shape[0], kp, collections is not None, ws.data_ptr())
         return lb
@@ -441,9 +464,10 @@ class GpuIndex(ScopedSearch, MutableIndex):
             raise N.NativeError("dense_finish: the workspace does not hold the candidate lists of a matching "
                                 "dense_shortlist call (same batch size, k, collections; no other dense "
                                 "search on this index in between)")
-        S, I, cnt, flg = N.dense_finish_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
-                                            self.inv_norm, queries, k, kp, gfloor, self.doc_base, ws,
-                                            doc_coll=dc, query_coll=qc, lb_all=lb_all)
+        with self._f16_flavour():
+            S, I, cnt, flg = N.dense_finish_f16(self.docs, self.docs16, self.doc_rel_err, self.dnorm,
+                                                self.inv_norm, queries, k, kp, gfloor, self.doc_base, ws,
+                                                doc_coll=dc, query_coll=qc, lb_all=lb_all)
         flags0 = flg.clone()
         n_rescued = self._rescue(queries, k, S, I, cnt, flg, dc, qc) if rescue else 0
         return S, I, cnt, flags0, n_rescued
@@ -456,7 +480,8 @@ class GpuIndex(ScopedSearch, MutableIndex):
             raise N.NativeError("scan_probe needs a preceding dense_search on this index (and a shortlist scan)")
         queries = self._t(queries, torch.float32)
         if self.shortlist != "f32":
-            N.dense_scan_probe_f16(self.docs, self.docs16, self.inv_norm, queries, self._ws)
+            with self._f16_flavour():
+                N.dense_scan_probe_f16(self.docs, self.docs16, self.inv_norm, queries, self._ws)
         else:
             N.dense_scan_probe(self.docs, self.inv_norm, queries, self._ws)
 

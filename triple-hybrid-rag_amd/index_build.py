@@ -54,9 +54,11 @@ class HostIndex:
     derived: Optional[Dict[str, Any]] = None   # GpuIndex.export_derived(): saved with the index, reused by to_gpu()
     attributes: Optional[Dict[str, np.ndarray]] = None   # per-row int32 columns a scope tests (GpuIndex.set_attributes)
 
-    def to_gpu(self, doc_base: int = 0):
+    def to_gpu(self, doc_base: int = 0, shortlist: str = "auto"):
+        """``shortlist``: GpuIndex.set_dense's -- "f16-anydim" puts a 1536-d or the 4000-d legacy store
+        on the f16 matrix cores, where "auto" scores every row in float64."""
         from .index import GpuIndex
-        idx = GpuIndex(doc_base=doc_base).set_dense(self.docs, derived=self.derived)
+        idx = GpuIndex(doc_base=doc_base).set_dense(self.docs, shortlist=shortlist, derived=self.derived)
         if self.rowptr is not None:
             idx.set_lexical(self.rowptr, self.post_doc, self.post_tf, self.doclen, self.idf,
                             self.avgdl, K1, B, derived=self.derived)

@@ -391,7 +391,7 @@ class MutableIndex:
         -> (shortlist, float16 image of the tail tiles or None, doc_rel_err, first row of the tail)."""
         n_old, cur = self.n_docs, self.shortlist
         t0 = n_old // 32 * 32     # the last partially filled tile of 32 rows is re-quantised
-        if cur not in ("f16", "f16-inline"):
+        if cur not in ("f16", "f16-inline", "f16-anydim"):
             return cur, None, self.doc_rel_err, t0
         want = cur
         if self._shortlist_auto:
@@ -402,10 +402,10 @@ class MutableIndex:
         if want == "f16":         # (cur is "f16": growth never shrinks the copy)
             tail16, e = N.dense_quantize_f16(torch.cat([self.docs[t0:n_old], new]), keep_copy=True)
             err = max(self.doc_rel_err, e)
-        elif want == "f16-inline":
+        elif want in ("f16-inline", "f16-anydim"):    # ("f16-anydim" is never auto: want is cur)
             _, err = N.dense_quantize_f16(new, keep_copy=False)
             # (the copy's error is measured on the normalised rows: the in-flight rounding's is not)
-            old = self.doc_rel_err if cur == "f16-inline" else N.dense_quantize_f16(self.docs, keep_copy=False)[1]
+            old = self.doc_rel_err if cur != "f16" else N.dense_quantize_f16(self.docs, keep_copy=False)[1]
             err = max(err, old)
         if want != "f32" and (not np.isfinite(err) or err > self.F16_MAX_REL_ERR):
             if not self._shortlist_auto:
@@ -650,7 +650,7 @@ class MutableIndex:
         stage = torch.empty(max([per * (buf[0].numel() * buf.element_size()) for _, _, buf, _, per in moves] or [0]),
                             dtype=torch.uint8, device=self.device)
         plan = _MovePlan(src, n_new, moves, stage)
-        if self.docs is None or self.shortlist not in ("f16", "f16-inline"):
+        if self.docs is None or self.shortlist not in ("f16", "f16-inline", "f16-anydim"):
             return plan
         copy = self.shortlist == "f16"            # (else: float32 rows rounded in flight, nothing stored)
         n_tail = sum(len(range(start, n_new, per)) for name, _, _, start, per in moves if name == "docs")
