@@ -497,6 +497,46 @@ int thr_graph_topk_scoped(const int64_t *ent_rowptr, const int32_t *ent_col, int
                           int64_t *out_ids, int32_t *out_counts, uint32_t *out_flags, void *workspace,
                           size_t workspace_bytes, thr_stream_t stream);
 
+/* a4  seed entities from query keywords, for a batch.  Stands where SQLGraphFallback.find_entities
+ * is called (src/voice_agent/rag2/graph_search.py:151-176: per keyword of keywords[:5],
+ * rag_entities ... ILIKE '%kw%' LIMIT limit // len(keywords)); the result is the query_seeds table
+ * of thr_graph_topk.  Case folding is the caller's: names and keywords arrive lower-cased, as UTF-8
+ * bytes, and are compared as bytes (a byte match of valid UTF-8 is a code-point match).
+ *   name_bytes uint8: every name followed by ONE 0xFF separator byte (0xFF never occurs in UTF-8),
+ *      16-byte aligned; name_ptr int64 [n_entities + 1], name_ptr[0] = 0: name e is the bytes
+ *      [name_ptr[e], name_ptr[e + 1] - 1).  REQUIRED PADDING: the allocation holds at least
+ *      THR_ENTITY_MAX_NEEDLE further 0xFF bytes behind name_ptr[n_entities] -- the kernel reads a
+ *      window of that length at every position and nothing behind name_ptr[n_entities] + the padding;
+ *   needles uint8 [n_needles, THR_ENTITY_MAX_NEEDLE], 4-byte aligned + needle_len int32 [n_needles] in
+ *      0 .. THR_ENTITY_MAX_NEEDLE: the batch's keywords (the caller de-duplicates them; equal needles
+ *      are allowed).  Length 0 matches every entity; a length outside the range or a needle that
+ *      holds 0xFF matches none;
+ *   query_needles int32 [n_queries, THR_ENTITY_MAX_KEYWORDS]: the query's needles in keyword order,
+ *      -1 (or any index outside [0, n_needles)) = none; query_per int32 [n_queries]: the entities a
+ *      keyword may contribute, max(1, limit // len(keywords)) -- clamped to THR_GRAPH_MAX_SEEDS here,
+ *      which changes no result (only a keyword's first 16 matches can reach a list of 16);
+ *   seeds int32 [n_queries, THR_GRAPH_MAX_SEEDS] padded with -1, counts int32 [n_queries]: per
+ *      keyword in order its first query_per matching entities in ascending id, those already in the
+ *      list skipped (they still count towards query_per), cut at THR_GRAPH_MAX_SEEDS.
+ * One pass over the name bytes for all needles (a hash table keyed by a needle's first bytes, built by
+ * this call in the workspace: any number of needles, any number sharing a key), per needle its 16
+ * smallest matching ids by commuting atomic minima -- the same output every run, no workgroup waits
+ * for another, no host read-back -- then one thread per query.  The text is staged in slices of
+ * THR_ENTITY_SLICE_BYTES.  Refused before any launch: null pointers, n_entities outside 1 .. 2^31 - 1,
+ * n_queries outside 1 .. THR_ENTITY_MAX_QUERIES, n_needles outside 1 .. THR_ENTITY_MAX_KEYWORDS *
+ * n_queries, name_bytes not 16-byte, needles not 4-byte or workspace not 8-byte aligned (THR_ERR_INVALID; the size query returns 0), ``workspace``
+ * < thr_entity_match_workspace_bytes() (THR_ERR_WORKSPACE). */
+#define THR_ENTITY_MAX_NEEDLE 128
+#define THR_ENTITY_MAX_KEYWORDS 5
+#define THR_ENTITY_MAX_QUERIES (1 << 20)
+#define THR_ENTITY_SLICE_BYTES 8192
+size_t thr_entity_match_workspace_bytes(int64_t n_entities, int n_needles, int n_queries);
+int thr_entity_match(const uint8_t *name_bytes, const int64_t *name_ptr, int64_t n_entities,
+                     const uint8_t *needles, const int32_t *needle_len, int n_needles,
+                     const int32_t *query_needles, const int32_t *query_per, int n_queries,
+                     int32_t *seeds /* [nq, THR_GRAPH_MAX_SEEDS] */, int32_t *counts /* [nq] */,
+                     void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
 /* a5+a6  candidate merge + weighted Reciprocal Rank Fusion, bit-for-bit the
  * float64 arithmetic and stable ordering of RAG2Retriever._retrieve_candidates
  * / _fuse_rrf, src/voice_agent/rag2/retrieval.py:203-271, 358-376.

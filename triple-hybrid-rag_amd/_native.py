@@ -32,6 +32,10 @@ THR_TOPK_MAX = 128
 THR_SCOPE_MAX_COLS = 8
 THR_SCOPE_MAX_PREDS = 4096
 THR_SCOPE_MAX_QUERIES = 1 << 20
+THR_ENTITY_MAX_NEEDLE = 128     # bytes of a keyword's lowered UTF-8 thr_entity_match takes
+THR_ENTITY_MAX_KEYWORDS = 5
+THR_ENTITY_MAX_QUERIES = 1 << 20
+THR_ENTITY_SLICE_BYTES = 8192   # name bytes a workgroup of thr_entity_match stages at a time
 # token dims thr_maxsim has a kernel for (csrc/maxsim.hip THR_MS_KSTEPS, times 16)
 MAXSIM_TOK_DIMS = (16, 32, 64, 96, 128, 192, 256)
 ABI_VERSION = 9
@@ -97,6 +101,8 @@ _SIGNATURES = {
                               _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_graph_topk_scoped": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
                                      _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "thr_entity_match_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "thr_entity_match": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "thr_rrf_fuse": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
                             _vp, _vp, _vp, _vp, _vp]),
     "thr_rrf_fuse_standalone": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
@@ -900,6 +906,40 @@ def _graph_call(entry, ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, que
                                   flg.data_ptr(), ws.data_ptr(), need, _stream()),
            entry)
     return S, I, cnt, flg
+
+
+def entity_match(name_bytes, name_ptr, needles, needle_len, query_needles, query_per, workspace=None):
+    """thr_entity_match: the seed entities of a batch from its keywords -> (seeds i32 [nq, 16] padded
+    with -1, counts i32 [nq]).  name_bytes u8 / name_ptr i64 [E + 1]: the packed lowered names
+    (index_entities.pack_entity_names: 0xFF behind every name and THR_ENTITY_MAX_NEEDLE more behind
+    the last); needles u8 [M, 128] / needle_len i32 [M]: the batch's distinct lowered keywords;
+    query_needles i32 [nq, 5] (-1 = none), query_per i32 [nq].  No host read-back."""
+    pb = _dev(name_bytes, torch.uint8, "name_bytes", 1)
+    pp = _dev(name_ptr, torch.int64, "name_ptr", 1)
+    n_ent = name_ptr.shape[0] - 1
+    pn = _dev(needles, torch.uint8, "needles", 2)
+    pl = _dev(needle_len, torch.int32, "needle_len", 1)
+    M = needles.shape[0]
+    if needles.shape[1] != THR_ENTITY_MAX_NEEDLE or needle_len.shape[0] != M:
+        raise NativeError(f"entity_match: needles must be [M, {THR_ENTITY_MAX_NEEDLE}] with M lengths")
+    pq = _dev(query_needles, torch.int32, "query_needles", 2)
+    pr = _dev(query_per, torch.int32, "query_per", 1)
+    nq = query_needles.shape[0]
+    if query_needles.shape[1] != THR_ENTITY_MAX_KEYWORDS or query_per.shape[0] != nq:
+        raise NativeError(f"entity_match: query_needles must be [nq, {THR_ENTITY_MAX_KEYWORDS}] with nq per-values")
+    if not 1 <= nq <= THR_ENTITY_MAX_QUERIES:
+        raise NativeError(f"entity_match: 1 .. {THR_ENTITY_MAX_QUERIES} queries per call, got {nq}")
+    if n_ent < 1 or not 1 <= M <= THR_ENTITY_MAX_KEYWORDS * nq:
+        raise NativeError(f"entity_match: {n_ent} entities, {M} needles for {nq} queries")
+    need = int(load().thr_entity_match_workspace_bytes(n_ent, M, nq))
+    ws = workspace
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=name_bytes.device)
+    seeds = torch.empty((nq, THR_GRAPH_MAX_SEEDS), dtype=torch.int32, device=name_bytes.device)
+    counts = torch.empty(nq, dtype=torch.int32, device=name_bytes.device)
+    _check(load().thr_entity_match(pb, pp, n_ent, pn, pl, M, pq, pr, nq, seeds.data_ptr(), counts.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()), "thr_entity_match")
+    return seeds, counts
 
 
 def graph_transpose_mentions(men_rowptr, men_chunk, men_conf, chunk_base: int, n_chunks: int):

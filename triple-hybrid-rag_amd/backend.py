@@ -986,6 +986,29 @@ class GpuIndexClient:
                         break
         return found[: N.THR_GRAPH_MAX_SEEDS]
 
+    def find_entities_batch(self, keyword_lists: Sequence[List[str]], limit: int = 20, device: bool = False):
+        """``find_entities`` for a batch of queries, on the device (GpuIndex.find_entities: one
+        thr_entity_match call for all of them) -> one list of entity ids per query, equal to
+        ``[self.find_entities(k, limit) for k in keyword_lists]``.  device=True: the (seeds int32
+        [nq, 16], counts int32 [nq]) device tensors instead, for a caller that goes on to
+        index.retrieve_batch(query_seeds=seeds).  The names are uploaded on first use from
+        store.entity_names, as _entity_index() builds its index on first use; a query with a keyword
+        too long for the kernel is resolved by ``find_entities``."""
+        keyword_lists = [list(k) for k in keyword_lists]
+        idx = self.index
+        if not self.store.entity_names:
+            if device:
+                return (torch.full((len(keyword_lists), N.THR_GRAPH_MAX_SEEDS), -1, dtype=torch.int32, device=idx.device),
+                        torch.zeros(len(keyword_lists), dtype=torch.int32, device=idx.device))
+            return [[] for _ in keyword_lists]
+        if idx.entities is None or idx.entities["n"] != len(self.store.entity_names):
+            idx.set_entity_names(self.store.entity_names)
+        seeds, counts = idx.find_entities(keyword_lists, limit, long_keywords=self.find_entities)
+        if device:
+            return seeds, counts
+        rows, cnt = seeds.cpu().numpy(), counts.cpu().numpy()
+        return [rows[q, :cnt[q]].tolist() for q in range(len(keyword_lists))]
+
     def entity_name(self, e: int) -> str:
         return self.store.entity_names[e]
 

@@ -15,6 +15,8 @@ Layout in HBM (per shard of n documents, D dims):
     lexical   CSR by term: rowptr int64 [V+1], post_doc int32, post_tf int32,
               doclen float32 [n], idf float64 [V] (global), avgdl (global)
     graph     entity CSR (replicated) + entity->chunk mention CSR (this shard's chunks)
+    entities  uint8 lower-cased entity names, 0xFF-separated + int64 [E+1] offsets (set_entity_names;
+              index_entities.EntitySearch: find_entities, a batch's keywords -> its graph seeds)
     tokens    float16 [n, T_d, 128] late-interaction token matrices
     attributes int32 [n] per name (set_attributes; "collection" = doc_coll): what a scope tests
                (index_scope.ScopedSearch: scope_plan, the row-list and the label routes)
@@ -35,6 +37,7 @@ import torch
 
 from . import _native as N
 from .index_mutate import MutableIndex, _refuse_when_unusable, _Storage
+from .index_entities import EntitySearch
 from .index_scope import ScopedSearch, ScopePlan
 
 log = logging.getLogger(__name__)
@@ -59,7 +62,7 @@ class BatchResult:
     rescued: object = 0
 
 
-class GpuIndex(ScopedSearch, MutableIndex):
+class GpuIndex(ScopedSearch, EntitySearch, MutableIndex):
     # what an index has before anything sets it (also: one made without __init__, as the host tests do)
     _side = None                # the second HIP stream of side_channels, made on first use
     _shortlist_of = None        # what the candidate lists in the dense workspace belong to (dense_shortlist)
@@ -269,6 +272,9 @@ class GpuIndex(ScopedSearch, MutableIndex):
         return self
 
     def set_graph(self, ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf) -> "GpuIndex":
+        if self.entities is not None and self.entities["n"] != len(ent_rowptr) - 1:
+            raise ValueError(f"set_graph: {len(ent_rowptr) - 1} entities, the index holds {self.entities['n']} "
+                             "entity names (set_entity_names)")
         self.graph = dict(ent_rowptr=self._t(ent_rowptr, torch.int64),
                           ent_col=self._t(ent_col, torch.int32),
                           men_rowptr=self._t(men_rowptr, torch.int64),
