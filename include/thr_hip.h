@@ -364,7 +364,31 @@ int thr_dense_topk_rows(const float *docs, const double *dnorm, int64_t n_docs, 
  * Stands where SQL rag2_lexical_search (ts_rank_cd ... ORDER BY rank DESC
  * LIMIT k) is called, rag2_schema.sql:341-374 / retrieval.py:282-290; the
  * north-star mandates BM25 in its place.  ``query_terms`` is [nq, max_terms]
- * term ids, negative = padding.  idf[] and avgdl are corpus-GLOBAL. */
+ * term ids, negative = padding.  idf[] and avgdl are corpus-GLOBAL.
+ *
+ * INPUT CONTRACT of thr_bm25_bounds / thr_bm25_dense_rows / thr_bm25_topk.  idf, avgdl, doclen, k1
+ * and b are the caller's: a shard passes global statistics that do not follow from its own rows.
+ * The pruning is exact -- the same bits as scoring every posting -- for
+ *     avgdl > 0,   k1 >= 0,   0 <= b <= 1,   tf >= 1,   doclen >= 0,
+ *     every idf finite and either 0 or >= 1e-300.
+ * Then every impact lies in (0, k1 + 1] and every contribution idf * impact in [0, idf * (k1 + 1)]:
+ *  - idf >= 0: a quantised impact is rounded UP, and idf times it bounds the contribution from above
+ *    only for a non-negative idf.  The classic Robertson idf ln((N - df + 0.5) / (df + 0.5)) is
+ *    negative above df = N / 2: use the oracle's ln(1 + ...) form (bm25_idf), or clamp at 0.
+ *  - the quantiser: post_imp = ceil(impact * 255 / (k1 + 1)) + 1, clipped to 255.  A clipped impact
+ *    stands for 255 * fl((k1 + 1) / 255), which may be an ulp below k1 + 1; the thresholds the
+ *    kernels compare against are integers (floor(theta * scale * (1 - 1e-12)) in accumulator
+ *    units), so a bound that is short by a few ulps never prunes a doc that ties or beats theta.
+ *  - the accumulator weights of a query: w_t = ceil(idf_t * unit * 248 / sum), unit = (k1 + 1) /
+ *    255, sum = the sum of idf_t * unit over the query's (probed) terms, clamped to >= 1; they add
+ *    up to <= 256, so eight clipped impacts (255 * 256) fit a 16-bit slot.  A query whose idfs are
+ *    all 0.0 scores 0.0 everywhere and is never pruned.  248 / sum must be finite: the smallest
+ *    sum is one idf * unit, unit >= 1 / 255 for k1 >= 0, so idf >= 248 * 255 / DBL_MAX = 3.52e-304
+ *    suffices; the contract rounds that up to 1e-300 (bm25_idf yields >= 2.3e-10 for 2^31 docs).
+ *    Below it the weight would be (int)ceil(inf) and a 16-bit slot could spill into its neighbour.
+ * Nothing in these entry points reads idf back to check it (that would be a device round trip
+ * per call): the host layer does once, at index set-up (_native.bm25_check_params, called by
+ * GpuIndex.set_lexical), and refuses values outside the contract by name. */
 /* Index set-up: upper bounds for the WAND-style pruning of thr_bm25_topk, computed with the
  * scoring formula itself: term_ub[t] = max contribution of a posting of term t, block_ub[j] = max
  * contribution among postings [128 j, 128 j + 128) of the posting array

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -781,6 +782,29 @@ def bm25_check_batch(n_queries: int) -> None:
     if n_queries > THR_BM25_MAX_QUERIES:
         raise NativeError(f"bm25: {n_queries} queries in one call, the limit is {THR_BM25_MAX_QUERIES} "
                           "(THR_BM25_MAX_QUERIES): split the batch")
+
+
+BM25_IDF_MIN = 1e-300   # the smallest positive idf (thr_hip.h, a3: the input contract of the pruning bounds)
+
+
+def bm25_check_params(idf, avgdl: float, k1: float = 1.2, b: float = 0.75) -> None:
+    """What the BM25 pruning bounds assume of their inputs (thr_hip.h, a3): avgdl > 0, k1 >= 0,
+    0 <= b <= 1, every idf finite and 0 or >= BM25_IDF_MIN.  Outside it a quantised impact is no
+    upper bound (a negative idf times an impact rounded up) or the accumulator weights are not
+    finite, and a wrong top-k comes back without a flag.  ``idf``: a tensor on any device (read
+    back once: call it at index set-up, not per query); raises NativeError naming the value."""
+    for name, v, ok in (("avgdl", avgdl, lambda x: x > 0.0), ("k1", k1, lambda x: x >= 0.0),
+                        ("b", b, lambda x: 0.0 <= x <= 1.0)):
+        v = float(v)
+        if not (math.isfinite(v) and ok(v)):
+            raise NativeError(f"bm25: {name} = {v!r}; the scoring bounds need avgdl > 0, k1 >= 0, 0 <= b <= 1, all finite")
+    t = idf.detach() if isinstance(idf, torch.Tensor) else torch.tensor(idf, dtype=torch.float64)   # (a copy: numpy arrays may be read-only)
+    t = t.reshape(-1).to(torch.float64)
+    bad = ~torch.isfinite(t) | (t < 0) | ((t > 0) & (t < BM25_IDF_MIN))
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        raise NativeError(f"bm25: idf[{i}] = {float(t[i])!r}; every idf must be finite and either 0 or >= {BM25_IDF_MIN!r}"
+                          f" ({int(bad.sum())} of {t.numel()} are not)")
 
 
 def bm25_topk(rowptr, post_doc, post_tf, doclen, idf, avgdl: float, query_terms, k: int,

@@ -192,6 +192,7 @@ class GpuIndex(ScopedSearch, EntitySearch, MutableIndex):
         reused when they were computed for the same k1, b, avgdl and dense share."""
         if dense_share is None:
             dense_share = float(os.environ.get("THR_BM25_DENSE_SHARE", self.DENSE_SHARE))
+        N.bm25_check_params(idf, avgdl, k1, b)   # (the pruning bounds' input contract: thr_hip.h, a3)
         self.lex = dict(rowptr=self._t(rowptr, torch.int64), post_doc=self._t(post_doc, torch.int32),
                         post_tf=self._t(post_tf, torch.int32), doclen=self._t(doclen, torch.float32),
                         idf=self._t(idf, torch.float64), avgdl=float(avgdl), k1=float(k1), b=float(b),
