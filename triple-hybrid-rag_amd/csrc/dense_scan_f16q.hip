@@ -24,11 +24,19 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
     if (nseg_out) *nseg_out = nseg;
     if (n_blocks) *n_blocks = (int)grid.x;
     if (PROF && !stamps) return THR_OK;   // size query
-#define THR_QS_LAUNCH(DIM, SHAPE)                                                                 \
-    return launch_lds(dense_scan_f16qs<DIM, MODE, SHAPE>, grid, dim3(QS_NW * 64),                 \
+    // a batch without a collection filter (no collections in the index, or none asked for) runs the
+    // instantiation that has no gather and no test for one compiled in
+    const bool coll = doc_coll != nullptr && query_coll != nullptr;
+#define THR_QS_LAUNCH_(DIM, SHAPE, COLL)                                                          \
+    return launch_lds(dense_scan_f16qs<DIM, MODE, SHAPE, COLL>, grid, dim3(QS_NW * 64),           \
                       QStag<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,       \
                       n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,    \
                       sample, doc_coll, query_coll, n_queries);
+#define THR_QS_LAUNCH(DIM, SHAPE)                                                                 \
+    {                                                                                             \
+        if (coll) THR_QS_LAUNCH_(DIM, SHAPE, true)                                                \
+        THR_QS_LAUNCH_(DIM, SHAPE, false)                                                         \
+    }
     if (stag) {
         if (dim == 512 && shape == 32) THR_QS_LAUNCH(512, 32)
         if (dim == 512) THR_QS_LAUNCH(512, 16)
@@ -36,11 +44,17 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
         THR_QS_LAUNCH(768, 16)
     }
 #undef THR_QS_LAUNCH
-#define THR_Q_LAUNCH(DIM, SHAPE)                                                                  \
-    return launch_lds(dense_scan_f16q<DIM, MODE, PROF, SHAPE>, grid, dim3(Q_NW * 64),             \
+#undef THR_QS_LAUNCH_
+#define THR_Q_LAUNCH_(DIM, SHAPE, COLL)                                                           \
+    return launch_lds(dense_scan_f16q<DIM, MODE, PROF, SHAPE, COLL>, grid, dim3(Q_NW * 64),       \
                       QScan<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,       \
                       n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,    \
                       sample, doc_coll, query_coll, n_queries, stamps);
+#define THR_Q_LAUNCH(DIM, SHAPE)                                                                  \
+    {                                                                                             \
+        if (coll) THR_Q_LAUNCH_(DIM, SHAPE, true)                                                 \
+        THR_Q_LAUNCH_(DIM, SHAPE, false)                                                          \
+    }
     switch (dim) {
         case 512: if (shape == 16) THR_Q_LAUNCH(512, 16) THR_Q_LAUNCH(512, 32)
         case 768: if (shape == 16) THR_Q_LAUNCH(768, 16) THR_Q_LAUNCH(768, 32)
@@ -51,6 +65,7 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
         default: return THR_ERR_UNSUPPORTED;
     }
 #undef THR_Q_LAUNCH
+#undef THR_Q_LAUNCH_
 }
 
 int launch_pack_queries(int dim, const float* queries, int n_queries, int qpad,

@@ -274,13 +274,24 @@ __device__ __forceinline__ void qsx_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NB
 // the emit of one accumulator register (a struct member, not a lambda: its store is inline asm).
 // A lane's candidate segment is addressed as a 32-bit byte offset from `cand` (one SGPR pair for
 // the base instead of a 64-bit pointer per lane): slot = next free entry, end = one past the last.
-template <int SHAPE>
-struct QEmit {
+//
+// COLL: whether the batch carries a collection filter.  The COLL = false instantiation (what
+// launch_scan_f16q picks when the index or the batch has no collections) has no qc[], no doc_coll
+// pointer, no gather and no exec region for it: an unfiltered batch used to carry all that and
+// branch around it on every hit (53 us of the 2.74 ms headline step, profiles/dense_emit.md).
+template <int NQL, bool COLL>
+struct QColl {   // the collection filter of a lane's queries (-1: none)
+    const int32_t* doc_coll;
+    int qc[NQL];
+};
+template <int NQL>
+struct QColl<NQL, false> {};
+
+template <int SHAPE, bool COLL>
+struct QEmit : QColl<QAcc<SHAPE>::NQL, COLL> {
     static constexpr int NQL = QAcc<SHAPE>::NQL;
     const Cand* cand;
-    const int32_t* doc_coll;
     float tau[NQL];
-    int qc[NQL];
     uint32_t slot[NQL], end[NQL];
     template <int X>
     __device__ __forceinline__ void one(const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
@@ -288,8 +299,10 @@ struct QEmit {
         const float v = acc.template get<X>();
         if (v >= tau[qs]) {   // false for NaN
             const uint32_t row = row0 + (uint32_t)QAcc<SHAPE>::template row<X>(lane);
-            // (a filtered query pays a dependent gather here, and its wait drains the DMA queue)
-            if (qc[qs] != -1 && doc_coll[row] != qc[qs]) return;
+            if constexpr (COLL) {
+                // (a filtered query pays a dependent gather here, and its wait drains the DMA queue)
+                if (this->qc[qs] != -1 && this->doc_coll[row] != this->qc[qs]) return;
+            }
             if (slot[qs] < end[qs]) {
                 const uint64_t word = (uint64_t)__float_as_uint(v) | ((uint64_t)row << 32);
                 // (inline asm: a store hipcc can see would make it wait vmcnt(0) -- DMA included --
@@ -319,11 +332,10 @@ struct QEmit {
 // so the gather never leaves doc_coll).  That is a dependent load per finite score of a filtered
 // query, and its wait drains the DMA queue as the filter scan's gather does: paid by filtered batches
 // in the sample pass only (~1 % of the rows), and NOT measured -- no filtered batch was profiled.
-template <int SHAPE>
-struct QTop {
+// COLL = false (no collections in the index or the batch) compiles the gather and its test out.
+template <int SHAPE, bool COLL>
+struct QTop : QColl<QAcc<SHAPE>::NQL, COLL> {
     static constexpr int NQL = QAcc<SHAPE>::NQL;
-    const int32_t* doc_coll;
-    int qc[NQL];
     float t[NQL][SAMPLE_TOP];
     __device__ __forceinline__ void init() {
 #pragma unroll
@@ -336,9 +348,11 @@ struct QTop {
         constexpr int qs = QAcc<SHAPE>::template qsel<X>();
         float x = acc.template get<X>();
         x = x == x ? x : -INFINITY;
-        if (doc_coll && qc[qs] != -1 && x > -INFINITY) {
-            const uint32_t row = row0 + (uint32_t)QAcc<SHAPE>::template row<X>(lane);
-            if (doc_coll[row] != qc[qs]) x = -INFINITY;
+        if constexpr (COLL) {
+            if (this->doc_coll && this->qc[qs] != -1 && x > -INFINITY) {
+                const uint32_t row = row0 + (uint32_t)QAcc<SHAPE>::template row<X>(lane);
+                if (this->doc_coll[row] != this->qc[qs]) x = -INFINITY;
+            }
         }
 #pragma unroll
         for (int j = 0; j < SAMPLE_TOP; ++j) {   // t[qs] stays sorted; x carries the displaced value down
@@ -368,9 +382,9 @@ struct QTop {
 // tile.  Here the 16 accumulator registers of tile i - 1 are compared / stored one at a time
 // between the MFMAs of tile i (8 per half tile, evenly spaced): an MFMA occupies the pipe for
 // 16 cycles after it issues, which is what one register's compare-and-branch takes to issue.
-template <int S, int HS, int K0, int KS, int PER, int SHAPE, int HF, int RING, int NBQ, typename Issue>
+template <int S, int HS, int K0, int KS, int PER, int SHAPE, int HF, int RING, int NBQ, bool COLL, typename Issue>
 __device__ __forceinline__ void qsx_steps_pe(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
-                                             uint32_t abase, Issue& issue_piece, QEmit<SHAPE>& em,
+                                             uint32_t abase, Issue& issue_piece, QEmit<SHAPE, COLL>& em,
                                              const QAcc<SHAPE>& prv, uint32_t row_prv, int lane) {
     if constexpr (S < HS) {
         constexpr int left = HS - S - 1 < RING - 1 ? HS - S - 1 : RING - 1;
@@ -383,7 +397,7 @@ __device__ __forceinline__ void qsx_steps_pe(f32x4 (&a)[RING], const f32x4 (&bq)
         // step at which j = floor(S * NRH / HS) is about to change
         constexpr int NRH = QAcc<SHAPE>::NREG / 2, j = S * NRH / HS;
         if constexpr ((S + 1) * NRH / HS > j) em.template one<NRH * HF + j>(prv, row_prv, lane);
-        qsx_steps_pe<S + 1, HS, K0, KS, PER, SHAPE, HF, RING, NBQ>(a, bq, acc, abase, issue_piece, em, prv, row_prv, lane);
+        qsx_steps_pe<S + 1, HS, K0, KS, PER, SHAPE, HF, RING, NBQ, COLL>(a, bq, acc, abase, issue_piece, em, prv, row_prv, lane);
     }
 }
 #undef QS_RD
@@ -393,7 +407,8 @@ __device__ __forceinline__ void qsx_steps_pe(f32x4 (&a)[RING], const f32x4 (&bq)
 // pieces, 1: barrier, 2: ring fill, 3: k-loop (with the DMA issue), 4: emit, 5: half tiles,
 // 6: whole loop, 7: HW_ID}].  Each stamp drains the wave's LDS/SMEM queue, so the build is slower
 // than the real one; it only says where the time goes.
-template <int DIM, int MODE, bool PROF = false, int SHAPE = 32>
+// COLL: the batch carries a collection filter (QEmit / QTop).
+template <int DIM, int MODE, bool PROF = false, int SHAPE = 32, bool COLL = true>
 __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q(
     const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
     int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
@@ -422,11 +437,10 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
     // the lane's private candidate segments (MODE_FILTER): query q, segment SEGS * slice + seg(lane)
     const int nseg = A::SEGS * slot.nslices;
     const int my_seg = A::SEGS * slot.slice + A::seg(lane);
-    QEmit<SHAPE> em;
+    QEmit<SHAPE, COLL> em;
     em.cand = cand;
-    em.doc_coll = doc_coll;
-    QTop<SHAPE> top;   // MODE_ALL
-    top.doc_coll = doc_coll;
+    QTop<SHAPE, COLL> top;   // MODE_ALL
+    if constexpr (COLL) em.doc_coll = top.doc_coll = doc_coll;
     top.init();
     uint32_t start[NQL];
 #pragma unroll
@@ -435,7 +449,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
         em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
         // collection filter of this lane's query (-1: none): checked only for rows that pass tau
         // (MODE_ALL: for the sample rows with a finite score)
-        em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
+        if constexpr (COLL) em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
         start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
         em.slot[u] = start[u];
         em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
@@ -681,7 +695,7 @@ struct QStag {
     static_assert(HS % QS_NW == 0 && LDS_BYTES <= 160 * 1024, "dim 512 / 768 only");
 };
 
-template <int DIM, int MODE, int SHAPE = 32>
+template <int DIM, int MODE, int SHAPE = 32, bool COLL = true>
 __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
     int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
@@ -707,11 +721,10 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
         });
     const int nseg = A::SEGS * slot.nslices;
     const int my_seg = A::SEGS * slot.slice + A::seg(lane);
-    QEmit<SHAPE> em;
+    QEmit<SHAPE, COLL> em;
     em.cand = cand;
-    em.doc_coll = doc_coll;
-    QTop<SHAPE> top;   // MODE_ALL
-    top.doc_coll = doc_coll;
+    QTop<SHAPE, COLL> top;   // MODE_ALL
+    if constexpr (COLL) em.doc_coll = top.doc_coll = doc_coll;
     top.init();
     uint32_t start[NQL];
 #pragma unroll
@@ -720,7 +733,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
         em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
         // collection filter of this lane's query (-1: none): checked only for rows that pass tau
         // (MODE_ALL: for the sample rows with a finite score)
-        em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
+        if constexpr (COLL) em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
         start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
         em.slot[u] = start[u];
         em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
