@@ -316,8 +316,9 @@ int thr_csr_compact(const int64_t *rowptr, int64_t rows, int64_t nnz, const int3
 /* f4  scoped queries: which rows a query may see.  Every reference RPC carries p_org_id
  * (database/migrations/20260114_rag2_schema.sql:341-410), the RAG 2.0 ones p_collection, the RAG 1.0
  * ones p_category / p_source_document (src/voice_agent/retrieval/hybrid_search.py:227-231), all applied
- * in SQL BEFORE the LIMIT.  A scope is a conjunction of equalities over per-row int32 attribute
- * columns; a batch names n_preds distinct ones.  The dense, lexical and graph scorers all filter by
+ * in SQL BEFORE the LIMIT.  A scope is a conjunction over per-row int32 attribute columns -- of
+ * equalities here, of sets, ranges and negations too in thr_scope_resolve_clauses below -- and a
+ * batch names n_preds distinct ones.  The dense, lexical and graph scorers all filter by
  * the labels written here (doc_coll / query_coll; the graph channel: thr_graph_topk_scoped, a4).
  *   h_cols [n_cols]: a HOST array of device pointers, each column int32 [n_docs];
  *   preds int32 [n_preds, n_cols]: the value a row must hold per column, -1 = any value, a value
@@ -341,6 +342,33 @@ size_t thr_scope_resolve_workspace_bytes(int64_t n_docs, int n_preds);
 int thr_scope_resolve(const int32_t *const *h_cols, int n_cols, int64_t n_docs, const int32_t *preds,
                       int n_preds, int64_t *rowptr, int32_t *rows, int64_t cap, int32_t *labels,
                       int32_t *overlap, void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
+/* The general scope: per column a CLAUSE instead of a value -- set membership ("inside these
+ * documents"), ranges ("ingested since day d") and their negations, AND-ed over the columns as the
+ * equalities above are.  thr_scope_resolve's outputs, contract and kernel shape (three launches,
+ * no atomic, the same output every run, every destination checked against cap):
+ *   clauses int32 [n_preds, n_cols, 4], DEVICE memory: (kind, a, b, 0) per predicate and column --
+ *      kind 0  any value;                       kind 1  no row;
+ *      kind 2  a <= value <= b (an equality is a == b);
+ *      kind 3  value is one of set_values[a .. a + b): ascending, distinct, >= 0;
+ *      kind 6 / 7  kind 2 / 3 negated.
+ *      A row whose value is -1 (it has none) matches no clause of kind 2 .. 7, negated or not: SQL's
+ *      rule for NULL under =, IN, BETWEEN, <> and NOT IN; only kind 0 accepts it.
+ *   set_values int32 [n_set_values], DEVICE memory: the members of every set of the call, one after
+ *      another; NULL iff n_set_values == 0; at most THR_SCOPE_MAX_SET_VALUES.
+ * The host cannot read the table, so the kernels are safe for any: an unknown kind matches no row,
+ * and a set's window [a, a + b) is clamped into [0, n_set_values] before anything is read (callers
+ * validate the table while it is still on the host).  A set costs each row a binary search over its
+ * window.  ``workspace`` >= thr_scope_resolve_clauses_workspace_bytes(). */
+#define THR_SCOPE_MAX_SET_VALUES (1 << 22)   /* set members of one call, all clauses together */
+size_t thr_scope_resolve_clauses_workspace_bytes(int64_t n_docs, int n_preds);
+int thr_scope_resolve_clauses(const int32_t *const *h_cols, int n_cols, int64_t n_docs,
+                              const int32_t *clauses /* device [P, C, 4] */, int n_preds,
+                              const int32_t *set_values /* device; NULL iff n_set_values == 0 */,
+                              int64_t n_set_values,
+                              int64_t *rowptr, int32_t *rows, int64_t cap,
+                              int32_t *labels, int32_t *overlap,
+                              void *workspace, size_t workspace_bytes, thr_stream_t stream);
 
 /* Exact cosine top-k of every query over the ROW LIST of its scope (rowptr / rows of
  * thr_scope_resolve, or any lists of local row indices; query_scope int32 [nq] in [0, n_scopes), any

@@ -33,6 +33,9 @@ THR_TOPK_MAX = 128
 THR_SCOPE_MAX_COLS = 8
 THR_SCOPE_MAX_PREDS = 4096
 THR_SCOPE_MAX_QUERIES = 1 << 20
+THR_SCOPE_MAX_SET_VALUES = 1 << 22   # set members of one thr_scope_resolve_clauses call
+# clause kinds of thr_scope_resolve_clauses: (kind, a, b, 0); + SCOPE_NEGATED on a range or a set
+SCOPE_ANY, SCOPE_NONE, SCOPE_RANGE, SCOPE_SET, SCOPE_NEGATED = 0, 1, 2, 3, 4
 THR_ENTITY_MAX_NEEDLE = 128     # bytes of a keyword's lowered UTF-8 thr_entity_match takes
 THR_ENTITY_MAX_KEYWORDS = 5
 THR_ENTITY_MAX_QUERIES = 1 << 20
@@ -87,6 +90,8 @@ _SIGNATURES = {
     "thr_csr_compact": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "thr_scope_resolve_workspace_bytes": (_sz, [_i64, _i32]),
     "thr_scope_resolve": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "thr_scope_resolve_clauses_workspace_bytes": (_sz, [_i64, _i32]),
+    "thr_scope_resolve_clauses": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "thr_dense_topk_rows_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "thr_dense_topk_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -681,6 +686,78 @@ def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = Tr
                                     cap, labels.data_ptr() if want_labels else None,
                                     overlap.data_ptr() if want_labels else None, ws.data_ptr(), need, _stream()),
            "thr_scope_resolve")
+    return rowptr, rows, labels, overlap
+
+
+def scope_check_clauses(clauses, set_values, n_cols: int):
+    """The host validation of a clause table before its upload -> (int32 [P, C, 4], int32 [n_set]) numpy,
+    contiguous.  Refused: a kind outside any / none / range / set (+ negated), a range with a > b or
+    a < 0, a set whose window leaves set_values or is empty, or whose members are not ascending,
+    distinct and >= 0."""
+    import numpy as np
+    tab = np.ascontiguousarray(clauses, dtype=np.int32)
+    sv = np.ascontiguousarray(np.zeros(0, np.int32) if set_values is None else set_values, dtype=np.int32).reshape(-1)
+    if tab.ndim != 3 or tab.shape[1] != n_cols or tab.shape[2] != 4:
+        raise NativeError(f"scope_resolve_clauses: clauses must be [P, {n_cols}, 4]")
+    P = tab.shape[0]
+    if not 1 <= P <= THR_SCOPE_MAX_PREDS:
+        raise NativeError(f"scope_resolve_clauses: 1 .. {THR_SCOPE_MAX_PREDS} predicates per call, got {P}")
+    if sv.shape[0] > THR_SCOPE_MAX_SET_VALUES:
+        raise NativeError(f"scope_resolve_clauses: at most {THR_SCOPE_MAX_SET_VALUES} set values per call, got {sv.shape[0]}")
+    kind, a, b = tab[..., 0], tab[..., 1].astype(np.int64), tab[..., 2].astype(np.int64)
+    base = kind & ~SCOPE_NEGATED
+    known = (kind == SCOPE_ANY) | (kind == SCOPE_NONE) | (((base == SCOPE_RANGE) | (base == SCOPE_SET)) & (kind >= 0) & (kind < 8))
+    if not known.all():
+        raise NativeError(f"scope_resolve_clauses: unknown clause kind {int(kind[~known][0])}")
+    rng = base == SCOPE_RANGE
+    if (rng & ((a > b) | (a < 0))).any():
+        raise NativeError("scope_resolve_clauses: a range clause needs 0 <= a <= b")
+    sets = base == SCOPE_SET
+    if (sets & ((a < 0) | (b < 1) | (a + b > sv.shape[0]))).any():
+        raise NativeError(f"scope_resolve_clauses: a set clause's offset / length leaves the {sv.shape[0]} set values")
+    if sv.shape[0] and int(sv.min()) < 0:
+        raise NativeError("scope_resolve_clauses: set values are >= 0")
+    if sets.any() and sv.shape[0] > 1:
+        rising = np.concatenate([[0], np.cumsum(np.diff(sv) <= 0)])     # breaks of the ascent before each position
+        lo, hi = a[sets], a[sets] + b[sets] - 1
+        if (rising[hi] != rising[lo]).any():
+            raise NativeError("scope_resolve_clauses: the values of a set are ascending and distinct")
+    return tab, sv
+
+
+def scope_resolve_clauses(cols, clauses, set_values=None, cap: Optional[int] = None, want_labels: bool = True):
+    """thr_scope_resolve_clauses: scope_resolve over predicates of CLAUSES.  ``clauses`` int32 [P, C, 4]
+    and ``set_values`` int32 [n] are HOST numpy arrays: they are validated here (scope_check_clauses:
+    the device cannot be asked) and uploaded.  -> scope_resolve's (rowptr, rows, labels, overlap)."""
+    cols = list(cols)
+    if not 1 <= len(cols) <= THR_SCOPE_MAX_COLS:
+        raise NativeError(f"scope_resolve_clauses: 1 .. {THR_SCOPE_MAX_COLS} attribute columns, got {len(cols)}")
+    n = cols[0].shape[0]
+    if any(c.dim() != 1 or c.shape[0] != n for c in cols):
+        raise NativeError("scope_resolve_clauses: every column is 1-d of the same length")
+    if isinstance(clauses, torch.Tensor) or isinstance(set_values, torch.Tensor):
+        raise NativeError("scope_resolve_clauses: the clause table and the set values are host numpy arrays")
+    tab, sv = scope_check_clauses(clauses, set_values, len(cols))
+    P = tab.shape[0]
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+        raise NativeError("scope_resolve_clauses: cap is negative")
+    ptrs = (C.c_void_p * len(cols))(*[_dev(c, torch.int32, "column", 1) for c in cols])
+    dev = cols[0].device
+    dtab = torch.from_numpy(tab).to(dev)
+    dsv = torch.from_numpy(sv).to(dev) if sv.shape[0] else None
+    rowptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev) if want_labels else None
+    overlap = torch.empty(1, dtype=torch.int32, device=dev) if want_labels else None
+    need = int(load().thr_scope_resolve_clauses_workspace_bytes(n, P))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _check(load().thr_scope_resolve_clauses(ptrs, len(cols), n, dtab.data_ptr(), P,
+                                            dsv.data_ptr() if dsv is not None else None, sv.shape[0],
+                                            rowptr.data_ptr(), rows.data_ptr() if cap else None, cap,
+                                            labels.data_ptr() if want_labels else None,
+                                            overlap.data_ptr() if want_labels else None, ws.data_ptr(), need, _stream()),
+           "thr_scope_resolve_clauses")
     return rowptr, rows, labels, overlap
 
 

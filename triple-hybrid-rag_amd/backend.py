@@ -53,6 +53,7 @@ import torch
 
 from . import _native as N
 from .index import GpuIndex
+from .index_scope import In
 
 _TOKEN = re.compile(r"[\w]+", re.UNICODE)
 
@@ -464,10 +465,36 @@ class GpuIndexClient:
     def _scoped(self, org, collection=None, index=None) -> Optional[dict]:
         """The filter arguments of a one-query search: ``collections=`` as always, or, multi-tenant,
         ``scopes=`` the cached plan of (org, collection); None = answer no rows."""
+        if isinstance(collection, (list, tuple)):
+            return self._scoped_union(org, collection, index)
         if not self.multi_tenant:
             return {} if index is not None else {"collections": self._qcoll(collection)}
         plan = self._scope(org, collection, index)
         return None if plan is None else {"scopes": plan}
+
+    def _scoped_union(self, org, wanted, index=None) -> Optional[dict]:
+        """``p_collection`` as a list of names: rank inside their UNION -- an ``In`` clause on
+        "collection" (AND the org, multi-tenant) through the index's scopes, single-tenant clients
+        included.  Names no row carries are dropped; none left = answer no rows (None).  The plan
+        is kept per (org, sorted names) until the index changes, as _scope keeps its own."""
+        index = self.index if index is None else index
+        scope = {}
+        if self.multi_tenant:
+            code = self._org_code.get(org) if org is not None else None
+            if code is None:
+                return None
+            scope["org"] = code
+        if index.doc_coll is None:          # no collection column: the filter does nothing, as with one name
+            return self._scoped(org, None, None if index is self.index else index)
+        names = tuple(sorted({c for c in wanted if c in self._coll_id}))
+        if not names:
+            return None
+        key = (id(index), org if self.multi_tenant else None, names)
+        plan = self._plans.get(key)
+        if plan is None or not index.scope_plan_current(plan, 1):
+            scope["collection"] = In([self._coll_id[c] for c in names])
+            plan = self._plans[key] = index.scope_plan([scope], 1)
+        return {"scopes": plan}
 
     def _image(self, embedding, limit: int, org=None) -> List[Dict[str, Any]]:
         """Cosine top-``limit`` over the image vectors (exact; the SQL orders by ``<=>``)."""

@@ -1,11 +1,14 @@
 """Scoped queries: every query of a batch names the rows it may see.
 
-A SCOPE is a conjunction of equalities over per-row int32 attribute columns (org, collection,
-document, category, ...): what the reference's RPCs filter by in SQL before their LIMIT (p_org_id
+A SCOPE is a conjunction of clauses over per-row int32 attribute columns (org, collection,
+document, category, ...) -- an equality, a set (``In``, or any list of values), a range
+(``Between``, ``range``) or the negation of one (``Not``) per column: what the reference's RPCs
+filter by in SQL before their LIMIT (p_org_id
 and p_collection, database/migrations/20260114_rag2_schema.sql:341-410; p_category and
 p_source_document, src/voice_agent/retrieval/hybrid_search.py:227-231).  ``ScopedSearch`` is the part
 of ``GpuIndex`` that holds the columns (``set_attributes``), resolves the distinct scopes of a batch
-on the device (``scope_plan``: thr_scope_resolve) and routes every query:
+on the device (``scope_plan``: thr_scope_resolve; thr_scope_resolve_clauses once a clause of the batch
+is more than an equality) and routes every query:
 
     unscoped                     the search as it always was;
     at most scope_rows_max rows  thr_dense_topk_rows over the scope's row list: the cost of its rows;
@@ -33,6 +36,216 @@ from . import _native as N
 NO_ROW = -2      # a predicate value that matches no row: a name the store has never seen
 
 
+INT32_MAX = 2 ** 31 - 1
+GENERAL = -3     # in ScopePlan.preds: the column carries a clause that is no equality (see ScopePlan.clauses)
+SCOPE_MAX_GENERAL = 256   # distinct scopes of a batch that holds a set, a range or a negation
+
+
+class In:
+    """Clause: the row's value is one of ``values`` (what a plain list, tuple, set, frozenset, 1-d integer
+    array or tensor means too).  Negative members are dropped; an empty set matches no row."""
+    __slots__ = ("values",)
+
+    def __init__(self, values):
+        self.values = values
+
+    def __repr__(self):
+        return f"In({self.values!r})"
+
+
+class Between:
+    """Clause: ``lo <= value <= hi``, both ends inclusive; None = open.  The ends are clipped to
+    [0, 2^31 - 1]; ``lo > hi`` matches no row.  ``range(a, b)`` (step 1) means Between(a, b - 1)."""
+    __slots__ = ("lo", "hi")
+
+    def __init__(self, lo=None, hi=None):
+        self.lo, self.hi = lo, hi
+
+    def __repr__(self):
+        return f"Between({self.lo!r}, {self.hi!r})"
+
+
+class Not:
+    """Clause: the negation of an equality, an ``In`` or a ``Between``.  A row whose value is -1 (it has
+    none) still matches nothing: SQL's NULL under <> and NOT IN."""
+    __slots__ = ("clause",)
+
+    def __init__(self, clause):
+        self.clause = clause
+
+    def __repr__(self):
+        return f"Not({self.clause!r})"
+
+
+# Canonical clauses (hashable; what the distinct scopes of a batch are found by):
+#   None                      any value (the attribute is not named)
+#   ("none",)                 no row
+#   ("eq", v)                 value == v
+#   ("range", lo, hi, neg)    lo <= value <= hi, lo < hi or negated; neg: every OTHER value >= 0
+#   ("set", (v, ...), neg)    two or more members, ascending and distinct
+_NONE = ("none",)
+
+
+def _as_int(x, what: str) -> int:
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+        raise ValueError(f"scopes: {what} must be an integer, got {x!r}")
+    return int(x)
+
+
+def _members(values) -> np.ndarray:
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    if isinstance(values, np.ndarray):
+        if values.ndim != 1 or values.dtype == np.bool_ or not np.issubdtype(values.dtype, np.integer):
+            raise ValueError(f"scopes: a set of values is a 1-d integer array, got {values.dtype} {values.shape}")
+        v = values.astype(np.int64)
+    elif isinstance(values, (list, tuple, set, frozenset)):
+        v = np.array([_as_int(x, "a member of a set") for x in values], dtype=np.int64)
+    else:
+        raise ValueError(f"scopes: In() takes a list, tuple, set or 1-d integer array, got {values!r}")
+    return np.unique(v[(v >= 0) & (v <= INT32_MAX)])
+
+
+def canonical_clause(value):
+    """One clause as the caller writes it -> its canonical form (see above).  Equal predicates get
+    equal forms: {"org": [3]}, {"org": In([3, 3])}, {"org": Between(3, 3)} and {"org": 3} are one."""
+    if value is None:
+        return _NONE
+    if isinstance(value, Not):
+        inner = value.clause
+        if inner is None or isinstance(inner, Not):
+            raise ValueError(f"scopes: Not() takes an equality, In or Between, got {inner!r}")
+        c = canonical_clause(inner)
+        if c == _NONE:                       # Not(In([])): every row that has a value
+            return ("range", 0, INT32_MAX, False)
+        if c[0] == "eq":
+            return ("range", c[1], c[1], True)
+        return (c[0], *c[1:-1], True)
+    if isinstance(value, range):
+        if value.step != 1:
+            raise ValueError(f"scopes: a range clause has step 1, got step {value.step}")
+        value = Between(value.start, value.stop - 1)
+    if isinstance(value, Between):
+        lo = 0 if value.lo is None else _as_int(value.lo, "an end of Between")
+        hi = INT32_MAX if value.hi is None else _as_int(value.hi, "an end of Between")
+        if lo > hi or hi < 0 or lo > INT32_MAX:
+            return _NONE
+        lo, hi = max(lo, 0), min(hi, INT32_MAX)
+        return ("eq", lo) if lo == hi else ("range", lo, hi, False)
+    if isinstance(value, In) or isinstance(value, (list, tuple, set, frozenset, np.ndarray, torch.Tensor)):
+        v = _members(value.values if isinstance(value, In) else value)
+        if v.size == 0:
+            return _NONE
+        return ("eq", int(v[0])) if v.size == 1 else ("set", tuple(v.tolist()), False)
+    v = _as_int(value, "a scope value")
+    return ("eq", v) if 0 <= v <= INT32_MAX else _NONE
+
+
+def _general(c) -> bool:
+    return c is not None and c[0] in ("range", "set")
+
+
+def _clause_disjoint(a, b) -> bool:
+    """Provably no value satisfies both canonical clauses (neither is None)?  False = may overlap."""
+    if a == _NONE or b == _NONE:
+        return True
+    a = ("range", a[1], a[1], False) if a[0] == "eq" else a
+    b = ("range", b[1], b[1], False) if b[0] == "eq" else b
+    if a[-1] and b[-1]:
+        return False                                    # two negations: may overlap
+    if a[-1] or b[-1]:                                  # Not(X) against Y: disjoint iff Y lies inside X
+        x, y = (a, b) if a[-1] else (b, a)
+        if x[0] == "range":
+            lo, hi = (y[1], y[2]) if y[0] == "range" else (y[1][0], y[1][-1])
+            return x[1] <= lo and hi <= x[2]
+        xs = np.asarray(x[1], dtype=np.int64)
+        if y[0] == "set":
+            return bool(np.isin(np.asarray(y[1], dtype=np.int64), xs).all())
+        inside = np.searchsorted(xs, y[2], side="right") - np.searchsorted(xs, y[1], side="left")
+        return int(inside) == y[2] - y[1] + 1
+    if a[0] == "range" and b[0] == "range":
+        return a[2] < b[1] or b[2] < a[1]
+    if a[0] == "set" and b[0] == "set":
+        if a[1][-1] < b[1][0] or b[1][-1] < a[1][0]:
+            return True
+        return np.intersect1d(np.asarray(a[1], dtype=np.int64), np.asarray(b[1], dtype=np.int64)).size == 0
+    r, st = (a, b) if a[0] == "range" else (b, a)
+    xs = np.asarray(st[1], dtype=np.int64)
+    return int(np.searchsorted(xs, r[2], side="right") - np.searchsorted(xs, r[1], side="left")) == 0
+
+
+def scopes_disjoint(a, b) -> bool:
+    """Provably no row satisfies both canonical scopes (tuples of canonical clauses, one per column)?
+    True when one of them holds a clause that matches nothing, or when on some column both constrain
+    the clauses are disjoint: equalities of different values, ranges that do not intersect, sets
+    without a common member, a range and a set with no member inside it, Not(X) against a clause
+    contained in X.  Everything else counts as "may overlap": conservative -- a pass more, never a
+    wrong filter."""
+    if _NONE in a or _NONE in b:
+        return True
+    return any(x is not None and y is not None and _clause_disjoint(x, y) for x, y in zip(a, b))
+
+
+def clause_groups(keys) -> List[np.ndarray]:
+    """Greedy placement, pair by pair, of the distinct canonical scopes into groups whose members are
+    pairwise disjoint (scopes_disjoint) -> scope indices per group.  O(P^2) clause comparisons: what
+    SCOPE_MAX_GENERAL bounds."""
+    # (the members of a set as an array, once: the comparisons below are numpy's)
+    keys = [tuple(("set", np.asarray(c[1], dtype=np.int64), c[2]) if c is not None and c[0] == "set" else c for c in key)
+            for key in keys]
+    groups: List[List[int]] = []
+    for i, key in enumerate(keys):
+        for g in groups:
+            if all(scopes_disjoint(key, keys[j]) for j in g):
+                g.append(i)
+                break
+        else:
+            groups.append([i])
+    return [np.asarray(g, dtype=np.int64) for g in groups]
+
+
+def encode_clauses(keys, n_cols: int):
+    """Canonical scopes -> (int32 [P, C, 4] clause table, int32 set values) of thr_scope_resolve_clauses."""
+    tab = np.zeros((len(keys), n_cols, 4), dtype=np.int32)
+    sets, used = [], 0
+    for p, key in enumerate(keys):
+        for c, cl in enumerate(key):
+            if cl is None:
+                continue
+            if cl == _NONE:
+                tab[p, c] = (N.SCOPE_NONE, 0, 0, 0)
+            elif cl[0] == "eq":
+                tab[p, c] = (N.SCOPE_RANGE, cl[1], cl[1], 0)
+            elif cl[0] == "range":
+                tab[p, c] = (N.SCOPE_RANGE | (N.SCOPE_NEGATED if cl[3] else 0), cl[1], cl[2], 0)
+            else:
+                tab[p, c] = (N.SCOPE_SET | (N.SCOPE_NEGATED if cl[2] else 0), used, len(cl[1]), 0)
+                sets.append(np.asarray(cl[1], dtype=np.int32))
+                used += len(cl[1])
+    if used > N.THR_SCOPE_MAX_SET_VALUES:
+        raise ValueError(f"scopes: the sets of one batch hold at most {N.THR_SCOPE_MAX_SET_VALUES} values together, got {used}")
+    return tab, (np.concatenate(sets) if sets else np.zeros(0, np.int32))
+
+
+def decode_clauses(tab: np.ndarray, set_values: np.ndarray):
+    """encode_clauses' inverse: the canonical scopes a clause table holds."""
+    keys = []
+    for pred in np.asarray(tab):
+        key = []
+        for kind, a, b, _ in pred.tolist():
+            neg = bool(kind & N.SCOPE_NEGATED)
+            if kind == N.SCOPE_ANY:
+                key.append(None)
+            elif kind == N.SCOPE_NONE:
+                key.append(_NONE)
+            elif kind & ~N.SCOPE_NEGATED == N.SCOPE_RANGE:
+                key.append(("eq", a) if a == b and not neg else ("range", a, b, neg))
+            else:
+                key.append(("set", tuple(np.asarray(set_values[a:a + b]).tolist()), neg))
+        keys.append(tuple(key))
+    return keys
+
+
 @dataclass
 class ScopePlan:
     """The distinct scopes of a batch, resolved: what dense_search / bm25_search / retrieve_batch
@@ -49,6 +262,10 @@ class ScopePlan:
     n_docs: int = 0
     mutations: int = 0
     columns: tuple = ()              # data_ptr of every attribute column the plan was resolved over
+    # a batch with a set, a range or a negation (else None: the plan is an equality plan, as it always was):
+    # the table thr_scope_resolve_clauses took, and ``preds`` then holds GENERAL where a clause is no equality
+    clauses: Optional[np.ndarray] = None      # int32 [P, C, 4] (kind, a, b, 0), host
+    set_values: Optional[np.ndarray] = None   # int32: the members of every set clause, host
 
 
 def _may_overlap(a: np.ndarray, b: np.ndarray) -> bool:
@@ -172,8 +389,19 @@ class ScopedSearch:
 
     def scope_plan(self, scopes, n_queries: int) -> ScopePlan:
         """Resolve the distinct scopes of a batch on the device (thr_scope_resolve) -> ScopePlan.
-        ``scopes``: per query a dict {attribute: value} (None / {} = unscoped), or an int32 [nq, C]
-        table over attribute_names() (-1 = any value).  Host side: the distinct scopes are found
+        ``scopes``: per query a dict {attribute: clause} (None / {} = unscoped), or an int32 [nq, C]
+        table over attribute_names() (-1 = any value; equalities only).  A clause is an int >= 0
+        (equality), None or an int < 0 (no row), a list / tuple / set / 1-d integer array or ``In``
+        (one of the values), ``Between(lo, hi)`` or ``range(a, b)`` (inclusive range, None = open), or
+        ``Not`` of one of these; the clauses of a scope are AND-ed, and a row whose value is -1 (it has
+        none) matches no clause, negated or not -- only an attribute the scope does not name accepts it.
+        A batch of equalities alone takes the path it always took; one with a set, a range or a
+        negation resolves through thr_scope_resolve_clauses, may name at most SCOPE_MAX_GENERAL
+        distinct scopes, and its scopes are grouped pair by pair (scopes_disjoint).  Scopes that may
+        share a row land in different groups, and BM25 and the graph channel run ONE PASS PER GROUP
+        (labels carry one scope per row): overlapping per-user document lists, for instance, cost a
+        pass each -- as {"org": 3} beside {"org": 3, "collection": 1} always did.
+        Host side: the distinct scopes are found
         with numpy (a table given as a DEVICE tensor is copied to the host for that: pass host data)
         and split into groups of disjoint ones (disjoint_groups: near-linear in P).  ONE small
         read-back from the device: the P + 1 row pointers (how many rows each distinct scope holds
@@ -185,6 +413,15 @@ class ScopedSearch:
                 raise ValueError("scopes: this ScopePlan was made for another batch size, another index, or before "
                                  "the index or its attribute columns changed")
             return scopes
+        if not isinstance(scopes, (torch.Tensor, np.ndarray)):
+            scopes = list(scopes)
+        keys = self._scope_keys(scopes, n_queries)
+        if keys is not None:
+            if any(_general(c) for key in keys for c in key):
+                return self._clause_plan(keys, n_queries)
+            # equalities after all ({"org": [3]}): the same predicates as values, the path they always took
+            names = self.attribute_names()
+            scopes = [{n: (None if c == _NONE else c[1]) for n, c in zip(names, key) if c is not None} for key in keys]
         names, tab = self._scope_table(scopes, n_queries)
         scoped = np.any(tab != -1, axis=1)
         qscope = np.full(n_queries, -1, dtype=np.int32)
@@ -218,6 +455,69 @@ class ScopedSearch:
             for g in plan.groups:
                 _, _, lab, _ = N.scope_resolve(cols, dpreds[torch.from_numpy(g).to(self.device)].contiguous(), cap=0)
                 plan.labels.append(lab)
+        return plan
+
+    def _scope_keys(self, scopes, nq: int):
+        """The canonical scope of every query (a tuple of canonical clauses over attribute_names()), or
+        None when ``scopes`` is a table or names nothing but plain ints and None: the batch the
+        equality path has always taken, which it then takes as it is."""
+        if isinstance(scopes, (torch.Tensor, np.ndarray)):
+            return None
+        plain = (int, np.integer)
+        if all(v is None or (isinstance(v, plain) and not isinstance(v, (bool, np.bool_)))
+               for sc in scopes for v in (sc or {}).values()):
+            return None
+        if len(scopes) != nq:
+            raise ValueError(f"scopes: one per query ({nq}), got {len(scopes)}")
+        names = self.attribute_names()
+        keys = []
+        for sc in scopes:
+            key = [None] * max(len(names), 1)
+            for name, value in (sc or {}).items():
+                if name not in names:
+                    raise ValueError(f"unknown attribute {name!r}: this index has {names}")
+                key[names.index(name)] = canonical_clause(value)
+            keys.append(tuple(key))
+        return keys
+
+    def _clause_plan(self, keys, n_queries: int) -> ScopePlan:
+        """scope_plan for a batch that holds a set, a range or a negation: the distinct canonical scopes
+        in order of first appearance, grouped pair by pair, resolved by thr_scope_resolve_clauses."""
+        names = self.attribute_names()
+        qscope = np.full(n_queries, -1, dtype=np.int32)
+        index: Dict[tuple, int] = {}
+        for i, key in enumerate(keys):
+            if any(c is not None for c in key):
+                qscope[i] = index.setdefault(key, len(index))
+        distinct = list(index)
+        if len(distinct) > SCOPE_MAX_GENERAL:
+            raise ValueError(f"scopes: a batch with a set, a range or a negation names at most {SCOPE_MAX_GENERAL} "
+                             f"distinct scopes, got {len(distinct)}")
+        tab, sv = encode_clauses(distinct, len(names))
+        preds = np.full((len(distinct), len(names)), -1, dtype=np.int32)
+        for p, key in enumerate(distinct):
+            for c, cl in enumerate(key):
+                if cl is not None:
+                    preds[p, c] = NO_ROW if cl == _NONE else cl[1] if cl[0] == "eq" else GENERAL
+        groups = clause_groups(distinct)
+        plan = ScopePlan(names, preds, qscope, np.zeros(0, np.int64), None, None, groups, n_docs=self.n_docs,
+                         mutations=getattr(self, "_mutations", 0), columns=self._column_key(), clauses=tab, set_values=sv)
+        plan.local = np.zeros((len(distinct), 2), dtype=np.int32)
+        for gi, g in enumerate(groups):
+            plan.local[g, 0] = gi
+            plan.local[g, 1] = np.arange(len(g), dtype=np.int32)
+        cols = [self.attribute(n) for n in names]
+        rowptr, rows, labels, _ = N.scope_resolve_clauses(cols, tab, sv, cap=self.n_docs, want_labels=len(groups) == 1)
+        h = rowptr.cpu().numpy()                    # the one read-back
+        if h[-1] > rows.shape[0]:                   # overlapping scopes: more list entries than rows
+            rowptr, rows, _, _ = N.scope_resolve_clauses(cols, tab, sv, cap=int(h[-1]), want_labels=False)
+        plan.rowptr, plan.rows, plan.counts = rowptr, rows, np.diff(h)
+        if len(groups) == 1:
+            plan.labels = [labels]
+        else:
+            for g in groups:
+                sub, sub_sv = encode_clauses([distinct[j] for j in g], len(names))
+                plan.labels.append(N.scope_resolve_clauses(cols, sub, sub_sv, cap=0)[2])
         return plan
 
     # ------------------------------------------------------------ routes
