@@ -53,6 +53,7 @@ enum {
 #define THR_BM25_MAX_QUERIES (1 << 20) /* queries of one thr_bm25_topk call (the caller splits a larger batch) */
 #define THR_GRAPH_MAX_SEEDS 16
 #define THR_RRF_MAX_PER_CHANNEL 128
+#define THR_RRF_MAX_TOP_K 512  /* rows of one fused list: top_k of thr_rrf_fuse*, n of thr_fuse_post / thr_rerank_order */
 #define THR_TOPK_MAX 128      /* bm25 / graph k upper bound */
 
 int thr_abi_version(void);
@@ -593,7 +594,10 @@ int thr_entity_match(const uint8_t *name_bytes, const int64_t *name_ptr, int64_t
  * float64 arithmetic and stable ordering of RAG2Retriever._retrieve_candidates
  * / _fuse_rrf, src/voice_agent/rag2/retrieval.py:203-271, 358-376.
  * Channel inputs are ranked id lists [nq, n_*] (negative id = end of list);
- * a null pointer or n_* == 0 disables the channel. */
+ * a null pointer or n_* == 0 disables the channel.  out_ranks: the id's LAST 1-based position
+ * in each channel, 0 = absent; rows past out_counts[q] are (-1, -inf, ranks 0).  Refused with
+ * THR_ERR_INVALID: top_k outside 1 .. THR_RRF_MAX_TOP_K, n_* above THR_RRF_MAX_PER_CHANNEL, and
+ * rrf_k outside 0 .. INT_MAX - THR_RRF_MAX_PER_CHANNEL (k + rank is formed in int). */
 int thr_rrf_fuse(const int64_t *lex_ids, int n_lex, const int64_t *sem_ids, int n_sem,
                  const int64_t *graph_ids, int n_graph, int n_queries, double w_lex, double w_sem,
                  double w_graph, int rrf_k, int top_k, int64_t *out_ids /* [nq,top_k] */,
@@ -672,8 +676,12 @@ int thr_maxsim_pack(const uint16_t *dtok, int64_t n_docs, int d_tokens, int tok_
  * (elements); list_stride = 0 means n_queries * k_in, i.e. the [n_lists, n_queries, k_in]
  * layout an all-gather of each rank's [n_queries, k_in] block produces -- a larger stride lets
  * scores and ids be read in place from one gathered [n_lists, 2, n_queries, k_in] tile.
- * Entries with score -inf or a negative id are padding.  Ids must be distinct across lists
- * (disjoint shards).  Lists that arrive ranked (the normal case) are merged without a sort. */
+ * Entries with a score of -inf or NaN or a negative id are padding; +inf is a score, and
+ * -0.0 == +0.0 (the id decides).  The result is the top k_out of the MULTISET of entries: the
+ * same (score, id) pair in two lists comes out twice, the copy of the lower-numbered list
+ * first (disjoint shards never produce one; no (-inf, -1) hole is left inside
+ * out_counts[q] either way).  Lists that arrive ranked (the normal case) are merged without
+ * a sort.  k_out is at most 512; rows past out_counts[q] are (-inf, -1). */
 int thr_merge_topk(const double *in_scores, const int64_t *in_ids, int n_queries, int n_lists,
                    int k_in, int64_t list_stride, int k_out, double *out_scores, int64_t *out_ids,
                    int32_t *out_counts, thr_stream_t stream);

@@ -708,12 +708,13 @@ def test_rrf_fuse_matches_reference_python(T, golden):
             c = dev(gra) if use[2] else None
             ids, sc, rk, cnt = T._native.rrf_fuse(a, dev(sem), c, 10, w["lexical"], w["semantic"],
                                                   w["graph"], 60, want_ranks=True)
-            ids, sc, cnt = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
+            ids, sc, rk, cnt = ids.cpu().numpy(), sc.cpu().numpy(), rk.cpu().numpy(), cnt.cpu().numpy()
             for q in range(nq):
                 cut = lambda l: [int(x) for x in l[q][: list(l[q] < 0).index(True) if (l[q] < 0).any() else None]]
-                ei, es = O.fused_topk_ids(cut(lex) if use[0] else None, cut(sem),
-                                          cut(gra) if use[2] else None, 10, w)
+                ei, es, er = O.fused_topk_ranks(cut(lex) if use[0] else None, cut(sem),
+                                                cut(gra) if use[2] else None, 10, w)
                 assert list(ids[q, :cnt[q]]) == ei and list(sc[q, :cnt[q]]) == es
+                assert rk[q, :cnt[q]].tolist() == [list(r) for r in er] and not rk[q, cnt[q]:].any()
     # the reference's own _fuse_rrf outputs (tests/golden/rrf_fuse.json): single-candidate lists
     for c in golden("rrf_fuse.json"):
         if len(c["ids"]) != 1 or c["ranks"][0] == [None, None, None]:

@@ -29,6 +29,7 @@ THR_BM25_MAX_TERMS = 32
 THR_BM25_MAX_QUERIES = 1 << 20
 THR_GRAPH_MAX_SEEDS = 16
 THR_RRF_MAX_PER_CHANNEL = 128
+THR_RRF_MAX_TOP_K = 512          # rows of one fused list (thr_rrf_fuse*, thr_fuse_post, thr_rerank_order)
 THR_TOPK_MAX = 128
 THR_SCOPE_MAX_COLS = 8
 THR_SCOPE_MAX_PREDS = 4096
@@ -1061,8 +1062,17 @@ def graph_transpose_mentions(men_rowptr, men_chunk, men_conf, chunk_base: int, n
 
 
 # ----------------------------------------------------------------- a5 + a6
+def rrf_check_top_k(what: str, top_k: int) -> None:
+    """The top_k thr_rrf_fuse / thr_rrf_fuse_standalone take, refused here with the limit in the
+    message (the library answers anything else with THR_ERR_INVALID)."""
+    if not 1 <= int(top_k) <= THR_RRF_MAX_TOP_K:
+        raise NativeError(f"{what}: top_k must be in 1 .. {THR_RRF_MAX_TOP_K} (the rows of one fused list), "
+                          f"got {top_k}")
+
+
 def rrf_fuse(lex_ids, sem_ids, graph_ids, top_k: int, w_lex: float = 0.7, w_sem: float = 0.8,
              w_graph: float = 1.0, rrf_k: int = 60, want_ranks: bool = False):
+    rrf_check_top_k("rrf_fuse", top_k)
     chans = [lex_ids, sem_ids, graph_ids]
     ref = next(c for c in chans if c is not None)
     nq = ref.shape[0]
@@ -1092,6 +1102,7 @@ def rrf_fuse_standalone(lex_ids, sem_ids, graph_ids, top_k: int, w_lex: float = 
                         w_graph: float = 1.0, two_channels: bool = False, want_ranks: bool = True):
     """The standalone package's RRFFusion.fuse / fuse_two_channels on id lists [nq, n_c] (-1
     padded) -> (ids i64 [nq, top_k], scores f64, ranks i32 [nq, top_k, 3] or None, counts)."""
+    rrf_check_top_k("rrf_fuse_standalone", top_k)
     chans = [lex_ids, sem_ids, graph_ids]
     ref = next(c for c in chans if c is not None)
     nq = ref.shape[0]
@@ -1229,7 +1240,10 @@ def rerank_order(scores: torch.Tensor, ids: torch.Tensor, counts: Optional[torch
 def merge_topk(in_scores: torch.Tensor, in_ids: torch.Tensor, k_out: int):
     """in_* are [n_lists, n_queries, k_in] (the layout an all-gather of each rank's
     [n_queries, k_in] block produces); they may be strided views of one gathered
-    [n_lists, 2, n_queries, k_in] tile (same list stride, contiguous [n_queries, k_in] blocks)."""
+    [n_lists, 2, n_queries, k_in] tile (same list stride, contiguous [n_queries, k_in] blocks).
+    Top k_out of the multiset of entries under (score desc, id asc): the same (score, id) pair in
+    two lists comes out twice (disjoint shards never produce one).  -inf / NaN scores and negative
+    ids are padding."""
     if in_scores.shape != in_ids.shape or in_scores.dim() != 3:
         raise NativeError("merge: shape mismatch")
     if in_scores.dtype != torch.float64 or in_ids.dtype != torch.int64 or not in_scores.is_cuda:

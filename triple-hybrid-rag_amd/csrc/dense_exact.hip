@@ -147,10 +147,13 @@ __global__ __launch_bounds__(256) void merge_lists(const double* __restrict__ in
 }
 
 // Merge of at most EX_CAP candidates per query held entirely in LDS: the per-shard lists of the
-// multi-GPU path (8 x <= 128).  The lists arrive ranked under (score desc, id asc) with disjoint
-// ids, so an entry's place in the merged order is its own position plus, per other list, the
-// number of entries ahead of it there (one binary search each) -- no sort.  A list that is NOT
-// ranked makes the block fall back to a bitonic sort of everything (same result, slower).
+// multi-GPU path (8 x <= 128).  The lists arrive ranked under (score desc, id asc), so an entry's
+// place in the merged order is its own position plus, per other list, the number of entries ahead
+// of it there (one binary search each) -- no sort.  "Ahead" is the total order extended by the list
+// index: against a LOWER-numbered list an equal (score, id) pair counts as ahead, against a
+// higher-numbered one it does not, so copies of one pair in several lists (shards that are not
+// disjoint) take consecutive places instead of one place and a hole.  A list that is NOT ranked
+// makes the block fall back to a bitonic sort of everything (same result, slower).
 __global__ __launch_bounds__(256) void merge_ranked_lists(const double* __restrict__ in_s,
                                                           const int64_t* __restrict__ in_id,
                                                           int64_t q_stride, int64_t list_stride,
@@ -200,7 +203,11 @@ __global__ __launch_bounds__(256) void merge_ranked_lists(const double* __restri
                 int lo = 0, hi = k_in;  // first position of list b that is not ahead of (ms, mi)
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    if (better(b_s[b * k_in + mid], b_id[b * k_in + mid], ms, mi)) lo = mid + 1;
+                    const double os = b_s[b * k_in + mid];
+                    const int64_t oi = b_id[b * k_in + mid];
+                    // b < a: not worse than mine; b > a: strictly better
+                    const bool ahead = b < a ? !better(ms, mi, os, oi) : better(os, oi, ms, mi);
+                    if (ahead) lo = mid + 1;
                     else hi = mid;
                 }
                 rank += lo;

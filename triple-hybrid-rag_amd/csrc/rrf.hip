@@ -16,7 +16,7 @@ namespace thr {
 
 constexpr int RRF_THREADS = 128;
 constexpr int RRF_MAXC = THR_RRF_MAX_PER_CHANNEL;  // per channel
-constexpr int RRF_SLOTS = 512;                      // >= 3 * RRF_MAXC, power of two
+constexpr int RRF_SLOTS = THR_RRF_MAX_TOP_K;         // >= 3 * RRF_MAXC, power of two
 
 // last 1-based position of id in l[0..n), 0 if absent
 __device__ __forceinline__ int last_rank(const int64_t* l, int n, int64_t id) {
@@ -254,6 +254,7 @@ __global__ __launch_bounds__(RRF_THREADS) void fuse_post_kernel(
     __shared__ int64_t s_id[2][RRF_SLOTS];
     __shared__ int wave_cnt[2];
     __shared__ double red[2][2];
+    __shared__ int red_at[2];
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int cnt = counts ? counts[q] : n;
     cnt = cnt < n ? cnt : n;
@@ -318,23 +319,28 @@ __global__ __launch_bounds__(RRF_THREADS) void fuse_post_kernel(
     if (top_k > 0 && m > top_k) m = top_k;
     double lo = 0.0, hi = 0.0;
     if (normalize && m > 0) {
+        // Python's min() answers the FIRST of equal minima, and -0.0 == +0.0: which zero is
+        // subtracted decides the sign of a normalised zero, so the minimum carries its row
         double mn = INFINITY, mx = -INFINITY;
+        int at = INT_MAX;
         for (int i = t; i < m; i += RRF_THREADS) {
             const double v = s_s[cur][i];
-            mn = v < mn ? v : mn;
+            if (v < mn) mn = v, at = i;
             mx = v > mx ? v : mx;
         }
         for (int o = 32; o > 0; o >>= 1) {
             const double a = __shfl_xor(mn, o, WAVE), b2 = __shfl_xor(mx, o, WAVE);
-            mn = a < mn ? a : mn;
+            const int a_at = __shfl_xor(at, o, WAVE);
+            if (a < mn || (a == mn && a_at < at)) mn = a, at = a_at;
             mx = b2 > mx ? b2 : mx;
         }
         if (lane == 0) {
             red[0][wave] = mn;
             red[1][wave] = mx;
+            red_at[wave] = at;
         }
         __syncthreads();
-        lo = red[0][0] < red[0][1] ? red[0][0] : red[0][1];
+        lo = (red[0][1] < red[0][0] || (red[0][1] == red[0][0] && red_at[1] < red_at[0])) ? red[0][1] : red[0][0];
         hi = red[1][0] > red[1][1] ? red[1][0] : red[1][1];
     }
     for (int i = t; i < n; i += RRF_THREADS) {
@@ -375,6 +381,8 @@ extern "C" int thr_rrf_fuse(const int64_t* lex_ids, int n_lex, const int64_t* se
     clear_status();
     THR_RETURN_IF(!out_ids || !out_scores || !out_counts, THR_ERR_INVALID);
     THR_RETURN_IF(n_queries <= 0 || top_k <= 0 || top_k > RRF_SLOTS || rrf_k < 0, THR_ERR_INVALID);
+    // the kernel forms rrf_k + rank (rank <= RRF_MAXC) in int
+    THR_RETURN_IF(rrf_k > INT_MAX - RRF_MAXC, THR_ERR_INVALID);
     THR_RETURN_IF(n_lex < 0 || n_sem < 0 || n_graph < 0 || n_lex > RRF_MAXC || n_sem > RRF_MAXC ||
                       n_graph > RRF_MAXC,
                   THR_ERR_INVALID);

@@ -75,6 +75,10 @@ __device__ __forceinline__ uint64_t dkey(double d) {
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
+// top 32 bits of the key, with -0.0 keyed as +0.0: under better() the two zeros are EQUAL (the id
+// decides), so a select by key prefix must not tell them apart (x + 0.0 is x but for -0.0 -> +0.0)
+__device__ __forceinline__ uint32_t dkey_hi(double d) { return (uint32_t)(dkey(d + 0.0) >> 32); }
+
 __device__ __forceinline__ double dkey_inv(uint64_t k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
@@ -226,7 +230,7 @@ struct BlockTopK {
             if (threadIdx.x < 256) hist[threadIdx.x] = 0;
             __syncthreads();
             for (int i = threadIdx.x; i < c; i += blockDim.x) {
-                const uint32_t key = (uint32_t)(dkey(s[i]) >> 32);
+                const uint32_t key = dkey_hi(s[i]);
                 if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8)))
                     atomicAdd(&hist[(key >> shift) & 255u], 1);
             }
@@ -270,7 +274,7 @@ struct BlockTopK {
             if (i < c) {
                 rs[u] = s[i];
                 ri[u] = id[i];
-                keep[u] = (uint32_t)(dkey(rs[u]) >> 32) >= prefix;
+                keep[u] = dkey_hi(rs[u]) >= prefix;
             }
         }
         if (threadIdx.x == 0) kept = 0;
