@@ -314,6 +314,47 @@ int thr_csr_compact(const int64_t *rowptr, int64_t rows, int64_t nnz, const int3
                     void *pay_out /* or NULL */, int64_t out_capacity, int64_t *nnz_out,
                     void *workspace, size_t workspace_bytes, thr_stream_t stream);
 
+/* f2  graph ingest: row-wise stable merge of two CSRs over one row space.  The reference's entity
+ * extraction runs behind the chunk inserts of a document and upserts rag_entities, inserts
+ * rag_relations and inserts rag_entity_mentions for chunks that are already stored
+ * (src/voice_agent/rag2/entity_extraction.py:449-554): a new relation may join two old entities and
+ * land anywhere inside a sorted row or be there already, a new mention of an old chunk lands in the
+ * middle of its entity's chunk-ascending row -- a merge, not thr_csr_append's concatenation.
+ *   A: rowptr_a [rows_a + 1], ids_a int32 [nnz_a], pay_a [nnz_a] an opaque 4-byte companion or NULL;
+ *   B: the same with rows_b >= rows_a (the entity set may have grown: rows >= rows_a are empty in A);
+ *      within a row ids are non-decreasing in both (drop_present: strictly ascending);
+ *   out: rowptr_out [rows_b + 1], ids_out / pay_out with room for out_capacity elements, *nnz_out,
+ *      *status_out (all device memory, buffers of their own).  Row t of the result is the merge of
+ *      A's and B's row t by id; on equal ids A's entries come first and each side keeps its order
+ *      (what a stable sort gives a fresh build that lists the old rows before the new ones).
+ *   drop_present = 1 (relations: set union): a B entry whose id is already in A's row is dropped,
+ *      *nnz_out <= nnz_a + nnz_b and rowptr_out counts kept entries only;
+ *   drop_present = 0 (mentions: multiset merge): nothing is dropped, *nnz_out = nnz_a + nnz_b.
+ * *status_out is 0 or a sum of THR_CSR_MERGE_UNSORTED_A / _B (the input breaks the ordering its mode
+ * needs: the result is then undefined, though inside its buffers, and must not be used) and
+ * THR_CSR_MERGE_OVERFLOW (*nnz_out > out_capacity: only positions below out_capacity were written).
+ * Of ids_out / pay_out the first min(*nnz_out, out_capacity) elements are written, nothing behind.
+ * Work is cut in slices of THR_CSR_MERGE_SLICE positions, not by row; three launches (count, scan,
+ * scatter), no workgroup waits for another, stream-ordered, no host round trip inside; ``workspace``
+ * (8-byte aligned) >= thr_csr_merge_workspace_bytes().  The kernels check every source index
+ * against nnz_a / nnz_b and every destination against out_capacity.  THR_ERR_INVALID before any
+ * launch: a null pointer with a non-zero size, rows_b < rows_a, a negative size, drop_present other
+ * than 0 / 1, a payload on one side only, a destination that is one of the sources.  rows_a == 0
+ * (rowptr_a may be NULL) merges into an empty graph. */
+#define THR_CSR_MERGE_SLICE 1024
+#define THR_CSR_MERGE_UNSORTED_A 1
+#define THR_CSR_MERGE_UNSORTED_B 2
+#define THR_CSR_MERGE_OVERFLOW 4
+int thr_csr_merge_slice(void);    /* THR_CSR_MERGE_SLICE as the library was built */
+size_t thr_csr_merge_workspace_bytes(int64_t rows_b, int64_t nnz_a, int64_t nnz_b);
+int thr_csr_merge(const int64_t *rowptr_a, int64_t rows_a, int64_t nnz_a, const int32_t *ids_a,
+                  const void *pay_a /* or NULL */, const int64_t *rowptr_b, int64_t rows_b,
+                  int64_t nnz_b, const int32_t *ids_b, const void *pay_b /* or NULL */,
+                  int drop_present, int64_t *rowptr_out, int32_t *ids_out,
+                  void *pay_out /* or NULL */, int64_t out_capacity, int64_t *nnz_out,
+                  int32_t *status_out, void *workspace, size_t workspace_bytes,
+                  thr_stream_t stream);
+
 /* f4  scoped queries: which rows a query may see.  Every reference RPC carries p_org_id
  * (database/migrations/20260114_rag2_schema.sql:341-410), the RAG 2.0 ones p_collection, the RAG 1.0
  * ones p_category / p_source_document (src/voice_agent/retrieval/hybrid_search.py:227-231), all applied

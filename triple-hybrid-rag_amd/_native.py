@@ -41,6 +41,9 @@ THR_ENTITY_MAX_NEEDLE = 128     # bytes of a keyword's lowered UTF-8 thr_entity_
 THR_ENTITY_MAX_KEYWORDS = 5
 THR_ENTITY_MAX_QUERIES = 1 << 20
 THR_ENTITY_SLICE_BYTES = 8192   # name bytes a workgroup of thr_entity_match stages at a time
+THR_CSR_MERGE_SLICE = 1024      # positions a workgroup of thr_csr_merge owns
+# bits of thr_csr_merge's status word: an input breaks its mode's ordering; the result exceeds out_capacity
+THR_CSR_MERGE_UNSORTED_A, THR_CSR_MERGE_UNSORTED_B, THR_CSR_MERGE_OVERFLOW = 1, 2, 4
 # token dims thr_maxsim has a kernel for (csrc/maxsim.hip THR_MS_KSTEPS, times 16)
 MAXSIM_TOK_DIMS = (16, 32, 64, 96, 128, 192, 256)
 ABI_VERSION = 9
@@ -89,6 +92,10 @@ _SIGNATURES = {
     "thr_csr_append": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "thr_csr_compact_workspace_bytes": (_sz, [_i64, _i64]),
     "thr_csr_compact": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "thr_csr_merge_slice": (_i32, []),
+    "thr_csr_merge_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "thr_csr_merge": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                             _vp, _sz, _vp]),
     "thr_scope_resolve_workspace_bytes": (_sz, [_i64, _i32]),
     "thr_scope_resolve": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "thr_scope_resolve_clauses_workspace_bytes": (_sz, [_i64, _i32]),
@@ -646,6 +653,85 @@ def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out
                                   _dev(pay_out, pay.dtype, "pay_out", 1) if nnz and pay is not None else None,
                                   cap, kept.data_ptr(), ws.data_ptr(), need, _stream()), "thr_csr_compact")
     return rowptr_out, ids_out, (pay_out if pay is not None else None), int(kept.item())
+
+
+def csr_merge_status_message(status: int) -> Optional[str]:
+    """What a non-zero status word of thr_csr_merge says, or None."""
+    if not status:
+        return None
+    said = []
+    if status & (THR_CSR_MERGE_UNSORTED_A | THR_CSR_MERGE_UNSORTED_B):
+        who = " and ".join(n for n, b in (("A (the index's rows)", THR_CSR_MERGE_UNSORTED_A),
+                                          ("B (the batch)", THR_CSR_MERGE_UNSORTED_B)) if status & b)
+        said.append(f"{who} not in build_graph's canonical form (ids ascending within a row; "
+                    "for relations strictly: no duplicate edge)")
+    if status & THR_CSR_MERGE_OVERFLOW:
+        said.append("the result does not fit the destination (out_capacity)")
+    return "; ".join(said)
+
+
+def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool, ids_out=None, pay_out=None,
+              workspace=None, check: bool = True):
+    """Row-wise stable merge of two CSRs over one row space (thr_csr_merge): row t of the result is
+    the merge of A's and B's row t by id, A first on equal ids.  ``rowptr_a`` int64 [rows_a + 1] or
+    None (an empty A), ``rowptr_b`` int64 [rows_b + 1], rows_b >= rows_a; ``ids_*`` int32 [nnz],
+    ``pay_*`` 4-byte tensors [nnz] of one dtype, on both sides or on neither.  ``drop_present``: the
+    set union (a B entry whose id is in A's row is dropped; both sides strictly ascending within a
+    row), else the multiset merge.  ``ids_out`` / ``pay_out``: capacity-reserved 1-d destinations
+    (allocated for nnz_a + nnz_b when None); ``workspace``: uint8, reused when large enough.  One
+    host read-back at the end (the count and the status word).  ``check``: raise NativeError on a
+    non-zero status (inputs not in canonical form, destination too small) instead of returning it.
+    -> (rowptr_out, ids_out, pay_out or None, nnz_out, status)."""
+    rows_a = 0 if rowptr_a is None else rowptr_a.shape[0] - 1
+    rows_b = rowptr_b.shape[0] - 1
+    if rows_b < rows_a or rows_b < 0:
+        raise NativeError(f"csr_merge: B has {rows_b} rows, A has {rows_a} (rows only grow)")
+    nnz_a = 0 if ids_a is None else ids_a.shape[0]
+    nnz_b = 0 if ids_b is None else ids_b.shape[0]
+    if (pay_a is not None and ids_a is None) or (pay_b is not None and ids_b is None):
+        raise NativeError("csr_merge: a payload without ids")
+    if (ids_a is not None and ids_b is not None and (pay_a is None) != (pay_b is None)) or \
+            (pay_out is not None and pay_a is None and pay_b is None):
+        raise NativeError("csr_merge: a payload travels on both sides or on neither")
+    pay_like = pay_a if pay_a is not None else pay_b
+    for pay, n, name in ((pay_a, nnz_a, "pay_a"), (pay_b, nnz_b, "pay_b")):
+        if pay is not None and (pay.dtype.itemsize != 4 or pay.dim() != 1 or pay.shape[0] != n or
+                                pay.dtype != pay_like.dtype):
+            raise NativeError(f"csr_merge: {name} is a 1-d array of 4-byte elements of one dtype, one per id")
+    for out, like, name in ((ids_out, torch.int32, "ids_out"),
+                            (pay_out, None if pay_like is None else pay_like.dtype, "pay_out")):
+        if out is not None and (out.dtype != like or out.dim() != 1):
+            raise NativeError(f"csr_merge: {name} is a 1-d array of the source's dtype")
+    pra = _dev(rowptr_a, torch.int64, "rowptr_a", 1)
+    prb = _dev(rowptr_b, torch.int64, "rowptr_b", 1)
+    pia = _dev(ids_a, torch.int32, "ids_a", 1)
+    pib = _dev(ids_b, torch.int32, "ids_b", 1)
+    dev = rowptr_b.device
+    if ids_out is None:
+        ids_out = torch.empty(nnz_a + nnz_b, dtype=torch.int32, device=dev)
+    if pay_out is None and pay_like is not None:
+        pay_out = torch.empty(nnz_a + nnz_b, dtype=pay_like.dtype, device=dev)
+    rowptr_out = torch.empty(rows_b + 1, dtype=torch.int64, device=dev)
+    tail = torch.zeros(2, dtype=torch.int64, device=dev)      # *nnz_out, *status_out
+    need = int(load().thr_csr_merge_workspace_bytes(rows_b, nnz_a, nnz_b))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    cap = ids_out.shape[0] if pay_like is None else min(ids_out.shape[0], pay_out.shape[0])
+    has = pay_like is not None
+    _check(load().thr_csr_merge(pra if rows_a else None, rows_a, nnz_a, pia if nnz_a else None,
+                                _dev(pay_a, pay_like.dtype, "pay_a", 1) if nnz_a and has else None,
+                                prb, rows_b, nnz_b, pib if nnz_b else None,
+                                _dev(pay_b, pay_like.dtype, "pay_b", 1) if nnz_b and has else None,
+                                1 if drop_present else 0, rowptr_out.data_ptr(),
+                                _dev(ids_out, torch.int32, "ids_out", 1) if cap else None,
+                                _dev(pay_out, pay_like.dtype, "pay_out", 1) if has and cap else None,
+                                cap, tail.data_ptr(), tail.data_ptr() + 8, _dev(workspace, torch.uint8, "workspace", 1),
+                                workspace.numel(), _stream()), "thr_csr_merge")
+    nnz_out, status = (int(v) for v in tail.tolist())
+    status &= 0xFFFFFFFF
+    if check and status:
+        raise NativeError("csr_merge: " + csr_merge_status_message(status))
+    return rowptr_out, ids_out, (pay_out if has else None), nnz_out, status
 
 
 # --------------------------------------------------------------------- f4

@@ -79,10 +79,73 @@ class CorpusStore:
     doc_base: int = 0
     content_hashes: Optional[List[Optional[str]]] = None            # the dedup key of the ingest (nullable)
     org_ids: Optional[List[Optional[str]]] = None                   # per-row tenant (rows' ``org_id``): one store, many orgs
+    # rag_entities.id / .canonical_name, parallel to entity_names.  None (older saved indexes, synth):
+    # the integer index is the id and the name the canonical name
+    entity_ids: Optional[List[Any]] = None
+    entity_canonical: Optional[List[Optional[str]]] = None
 
     def __post_init__(self):
         self._row_of = {cid: i for i, cid in enumerate(self.child_ids)}
         self._hashes = {h for h in (self.content_hashes or ()) if h is not None}
+        self._ent_of: Optional[Dict[Any, int]] = None       # entity id -> index, built on first use
+        self._canon_of: Optional[Dict[str, int]] = None     # canonical name -> first index
+
+    # ---- entities (rag_entities): index e of the graph is row e of these columns
+    def entity_index(self, entity_id: Any) -> Optional[int]:
+        """Index of the entity with this id, or None.  Without an id column the integer index is the id."""
+        if self.entity_ids is None:
+            ok = isinstance(entity_id, (int, np.integer)) and not isinstance(entity_id, bool)
+            return int(entity_id) if ok and 0 <= int(entity_id) < len(self.entity_names) else None
+        if self._ent_of is None:
+            self._ent_of = {}
+            for i, e in enumerate(self.entity_ids):
+                self._ent_of.setdefault(e, i)
+                self._ent_of.setdefault(str(e), i)     # (a saved column comes back as strings)
+        i = self._ent_of.get(entity_id)
+        return self._ent_of.get(str(entity_id)) if i is None else i
+
+    def entity_row(self, i: int) -> Dict[str, Any]:
+        canon = None if self.entity_canonical is None else self.entity_canonical[i]
+        return {"id": i if self.entity_ids is None else self.entity_ids[i], "name": self.entity_names[i],
+                "canonical_name": self.entity_names[i] if canon is None else canon}
+
+    def entity_by_canonical(self, canonical: str) -> Optional[int]:
+        """Index of the first entity with this canonical name, or None."""
+        if self._canon_of is None:
+            self._canon_of = {}
+            for i in range(len(self.entity_names)):
+                self._canon_of.setdefault(self.entity_row(i)["canonical_name"], i)
+        return self._canon_of.get(canonical)
+
+    def check_new_entities(self, rows: Sequence[Dict[str, Any]]) -> None:
+        """The unique constraint on rag_entities.id, before anything is changed."""
+        seen = set()
+        for r in rows:
+            if self.entity_index(r["id"]) is not None or r["id"] in seen:
+                raise ValueError(f"duplicate key value violates unique constraint on rag_entities (id {r['id']!r})")
+            seen.add(r["id"])
+
+    def append_entities(self, rows: Sequence[Dict[str, Any]]) -> range:
+        """Append rag_entities rows (id, name, canonical_name) -> the range of their indices.  The id
+        and canonical-name columns come into being here, the old entities keeping their defaults."""
+        rows = list(rows)
+        self.check_new_entities(rows)
+        n0 = len(self.entity_names)
+        if not rows:
+            return range(n0, n0)
+        for name in ("entity_names", "entity_ids", "entity_canonical"):
+            if getattr(self, name) is not None and not isinstance(getattr(self, name), list):
+                setattr(self, name, list(getattr(self, name)))
+        if self.entity_ids is None:
+            self.entity_ids = list(range(n0))
+        if self.entity_canonical is None:
+            self.entity_canonical = [None] * n0
+        for r in rows:
+            self.entity_ids.append(r["id"])
+            self.entity_names.append(r.get("name") or "")
+            self.entity_canonical.append(r.get("canonical_name"))
+        self._ent_of = self._canon_of = None
+        return range(n0, n0 + len(rows))
 
     def has_hash(self, content_hash: Optional[str]) -> bool:
         return content_hash is not None and content_hash in self._hashes
@@ -264,9 +327,11 @@ class LazyRows(collections.abc.Sequence):
 
 
 class _TableQuery:
-    def __init__(self, fetch, by_hash=None, insert=None, org_id=None, delete=None, tenants=False):
+    def __init__(self, fetch, by_hash=None, insert=None, org_id=None, delete=None, tenants=False, by_eq=None):
         self._fetch = fetch
         self._by_hash = by_hash       # content_hash lookup (rag_child_chunks only)
+        self._by_eq = by_eq           # equality lookup {column: value} -> rows (rag_entities.canonical_name)
+        self._eqs: Dict[str, Any] = {}
         self._insert = insert         # row writer (the two chunk tables)
         self._delete = delete         # row remover: [(column, values), ...] -> the deleted rows
         self._filters: Optional[List[Any]] = None   # delete(): the filters so far (AND)
@@ -285,6 +350,8 @@ class _TableQuery:
     def eq(self, *a, **_kw):
         if len(a) == 2 and a[0] == "org_id" and self._org_id is not None and a[1] not in (None, self._org_id):
             self._foreign = True
+        if self._by_eq is not None and len(a) == 2 and a[0] != "org_id":
+            self._eqs[a[0]] = a[1]
         if self._tenants and len(a) == 2 and a[0] == "org_id":
             self._org_eq = [a[1]]
             if self._filters is not None:
@@ -336,6 +403,8 @@ class _TableQuery:
         org = {} if self._org_eq is None else {"org": self._org_eq[0]}
         if self._hashes is not None:
             rows = [] if self._foreign else self._by_hash(self._hashes, **org)
+        elif self._by_eq is not None and self._ids is None:
+            rows = [] if self._foreign else self._by_eq(dict(self._eqs), **org)
         else:
             rows = self._fetch(self._ids or [], **org)
         return _Reply(rows[: self._limit] if self._limit is not None else rows)
@@ -791,6 +860,78 @@ class GpuIndexClient:
             del self._by_text
         return [{"id": p["id"]} for p in rows]
 
+    # -------------------------------------------------------------- graph ingest
+    # What the reference's entity extraction writes behind a document's chunk inserts
+    # (rag2/entity_extraction.py:449-554): rag_entities upserts, rag_relations and rag_entity_mentions
+    # inserts.  Index first, store second, as insert_children: a refused call leaves both as they were.
+    def _check_foreign_org(self, rows: Sequence[Dict[str, Any]]) -> None:
+        """rag_entity_mentions rows carry no org_id in the reference (a mention's tenant is its
+        chunk's): only rows that name ANOTHER org than this client's are refused."""
+        if self.org_id is not None and any(r.get("org_id") not in (None, self.org_id) for r in rows):
+            raise ValueError("insert refused: the rows belong to another org_id than this index "
+                             "(data isolation, as rpc() answers another tenant with no rows)")
+
+    def insert_entities(self, rows: Sequence[Dict[str, Any]]):
+        """``table("rag_entities").insert(rows)``: the entities get the next entity ids of the live
+        index (``GpuIndex.append_graph``), their lower-cased names join the device name store, and
+        the rows (id, name, canonical_name) the store -> [{"id": ...}, ...].  A duplicate id is the
+        unique-constraint ValueError, raised before anything is changed."""
+        rows = list(rows)
+        self._check_org(rows)
+        if not rows:
+            return []
+        st, idx = self.store, self.index
+        st.check_new_entities(rows)
+        names = [r.get("name") or "" for r in rows]
+        if idx.entities is None and len(st.entity_names) > 0:
+            # the names of this store were not uploaded yet (find_entities_batch does it on first use,
+            # from all of store.entity_names): only the rows grow now
+            idx.append_graph(n_new_entities=len(rows))
+        else:
+            idx.append_graph(entity_names=names)
+        st.append_entities(rows)
+        self._tri = None       # (the trigram index of find_entities is over the old names)
+        return [{"id": r["id"]} for r in rows]
+
+    def insert_relations(self, rows: Sequence[Dict[str, Any]]):
+        """``table("rag_relations").insert(rows)``: subject_entity_id / object_entity_id become entity
+        indices; a row naming an unknown entity is skipped, as ``index_build.build_graph`` skips it;
+        the rest go through ``GpuIndex.append_graph(relations=)`` (both directions, self-loops and
+        edges the index already holds dropped).  Relation types and confidences are not stored: the
+        walk does not read them."""
+        rows = list(rows)
+        self._check_org(rows)
+        st = self.store
+        pairs = [(st.entity_index(r.get("subject_entity_id")), st.entity_index(r.get("object_entity_id"))) for r in rows]
+        pairs = [(a, b) for a, b in pairs if a is not None and b is not None]
+        if pairs:
+            self.index.append_graph(relations=(np.asarray([a for a, _ in pairs], dtype=np.int64),
+                                               np.asarray([b for _, b in pairs], dtype=np.int64)))
+            self._tri = None
+        return [{"id": r.get("id")} for r in rows]
+
+    def insert_mentions(self, rows: Sequence[Dict[str, Any]]):
+        """``table("rag_entity_mentions").insert(rows)``: entity_id / child_chunk_id become an entity
+        index and a chunk of the live index; a row naming an unknown entity or chunk is skipped, as
+        ``build_graph`` skips it; ``confidence`` defaults to 1.0; the rest go through
+        ``GpuIndex.append_mentions``."""
+        rows = list(rows)
+        self._check_foreign_org(rows)
+        st = self.store
+        me, mc, mw = [], [], []
+        for r in rows:
+            e, c = st.entity_index(r.get("entity_id")), st.row_index(r.get("child_chunk_id"))
+            if e is None or c is None:
+                continue
+            me.append(e)
+            mc.append(c)
+            mw.append(1.0 if r.get("confidence") is None else float(r["confidence"]))
+        if me:
+            self.index.append_mentions(np.asarray(me, dtype=np.int64), np.asarray(mc, dtype=np.int64),
+                                       np.asarray(mw, dtype=np.float32))
+            self._tri = None
+        return [{"id": r.get("id")} for r in rows]
+
     # -------------------------------------------------------------- delete
     def _child_rows_where(self, filters, columns=("id", "document_id", "parent_id")) -> List[int]:
         """Row indices of the child chunks that match every (column, values) filter; a multi-tenant
@@ -946,6 +1087,28 @@ class GpuIndexClient:
                 return [dict(st.parents[p]) for p in ids if p in st.parents and (own is None or p in own)]
             return _TableQuery(parents, insert=self.insert_parents, org_id=self.org_id,
                                delete=self._delete_parents_where, tenants=self.multi_tenant)
+        # the graph tables of the entity extraction (rag2/entity_extraction.py:449-554).  Entities carry
+        # no org in the store: eq("org_id", x) does not narrow a multi-tenant lookup
+        if name == "rag_entities":
+            def entities(ids, **_within):
+                st = self.store
+                return [st.entity_row(i) for i in (st.entity_index(e) for e in ids) if i is not None]
+
+            def by_eq(eqs, **_within):
+                unknown = set(eqs) - {"canonical_name"}
+                if unknown or not eqs:
+                    raise ValueError("rag_entities rows are looked up by id or canonical_name, not "
+                                     f"{sorted(unknown) or 'without a filter'}")
+                i = self.store.entity_by_canonical(eqs["canonical_name"])
+                return [] if i is None else [self.store.entity_row(i)]
+            return _TableQuery(entities, by_eq=by_eq, insert=self.insert_entities, org_id=self.org_id,
+                               tenants=self.multi_tenant)
+        if name == "rag_relations":
+            return _TableQuery(lambda _ids, **_w: [], insert=self.insert_relations, org_id=self.org_id,
+                               tenants=self.multi_tenant)
+        if name == "rag_entity_mentions":
+            return _TableQuery(lambda _ids, **_w: [], insert=self.insert_mentions, org_id=self.org_id,
+                               tenants=self.multi_tenant)
         # tenant discovery of the tool layer (tools/crm_knowledge.py:89-101 in the reference)
         if name in ("rag_documents", "organizations") and self.multi_tenant:
             key = "org_id" if name == "rag_documents" else "id"

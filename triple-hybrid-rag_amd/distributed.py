@@ -170,6 +170,18 @@ class ShardedIndex:
         raise N.NativeError("delete_rows is not supported on a ShardedIndex: rebuild the shards "
                             "(deletes from a document-sharded index are out of scope)")
 
+    def append_graph(self, *_a, **_kw):
+        """Not supported: every rank holds the whole entity CSR and its own chunks' mentions, so a
+        graph ingest would be a collective with a rule for which rank takes a mention (DESIGN.md,
+        Graph ingest)."""
+        raise N.NativeError("append_graph is not supported on a ShardedIndex: rebuild the shards "
+                            "(graph ingest into a document-sharded index is out of scope)")
+
+    def append_mentions(self, *_a, **_kw):
+        """Not supported, as append_graph."""
+        raise N.NativeError("append_mentions is not supported on a ShardedIndex: rebuild the shards "
+                            "(graph ingest into a document-sharded index is out of scope)")
+
     def _floor_exchange(self):
         if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline", "f16-anydim"):
             return None

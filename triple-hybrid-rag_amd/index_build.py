@@ -237,7 +237,10 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
         vocab=vocab, entity_names=[e.get("name", "") for e in entity_rows], doc_base=doc_base,
         content_hashes=[r.get("content_hash") for r in child_rows]
         if any(r.get("content_hash") is not None for r in child_rows) else None,
-        org_ids=[r.get("org_id") for r in child_rows] if any("org_id" in r for r in child_rows) else None)
+        org_ids=[r.get("org_id") for r in child_rows] if any("org_id" in r for r in child_rows) else None,
+        entity_ids=[e["id"] for e in entity_rows] if entity_rows else None,
+        entity_canonical=[e.get("canonical_name") for e in entity_rows]
+        if any(e.get("canonical_name") is not None for e in entity_rows) else None)
     hi = HostIndex(docs=docs, rowptr=rowptr, post_doc=pd, post_tf=ptf, doclen=dl, idf=idf,
                    avgdl=avgdl, store=store)
     if entity_rows:
@@ -252,7 +255,7 @@ _ARRAYS = ("docs", "rowptr", "post_doc", "post_tf", "doclen", "idf", "ent_rowptr
 _DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf")
 _DERIVED_SCALARS = ("doc_rel_err", "f16_layout", "lexical_tag", "dense_stride")
 _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modalities", "collections",
-                   "entity_names", "content_hashes", "org_ids")
+                   "entity_names", "content_hashes", "org_ids", "entity_ids", "entity_canonical")
 _NO_PAGE = np.iinfo(np.int32).min   # store_pages.npy: the SQL column is nullable (page INT)
 
 
@@ -270,10 +273,11 @@ def _mutated_since_sync(hi: HostIndex, gpu_index) -> bool:
 
 def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
     """After ``GpuIndex.append_rows`` (the ingest seam, rag2/ingest.py:361-470) or
-    ``GpuIndex.delete_rows`` the device holds other rows than the HostIndex: pull the source arrays
-    back, in place, so that ``hi`` -- and a ``save`` of it -- equals a build from the rows the index
-    holds now.  The store is appended to and deleted from by the client (``CorpusStore.append`` /
-    ``.delete``) and is not touched here."""
+    ``GpuIndex.delete_rows`` -- or a graph ingest, ``append_graph`` / ``append_mentions`` -- the
+    device holds other rows than the HostIndex: pull the source arrays back, in place, so that
+    ``hi`` -- and a ``save`` of it -- equals a build from the rows the index holds now.  The store
+    is appended to and deleted from by the client (``CorpusStore.append`` / ``.delete`` /
+    ``.append_entities``) and is not touched here."""
     g = gpu_index
     if g.docs is not None:
         hi.docs = g.docs.cpu().numpy()
@@ -283,6 +287,7 @@ def refresh_from_gpu(hi: HostIndex, gpu_index) -> HostIndex:
         hi.doclen, hi.idf, hi.avgdl = L["doclen"].cpu().numpy(), L["idf"].cpu().numpy(), float(L["avgdl"])
     if g.graph is not None:
         G = g.graph
+        hi.ent_rowptr, hi.ent_col = G["ent_rowptr"].cpu().numpy(), G["ent_col"].cpu().numpy()   # (append_graph)
         hi.men_rowptr, hi.men_chunk, hi.men_conf = (G[k].cpu().numpy() for k in ("men_rowptr", "men_chunk", "men_conf"))
     if hi.tokens is not None:
         stale = len(hi.tokens) != g.n_docs
@@ -390,6 +395,7 @@ def load(path: str, mmap: bool = True) -> HostIndex:
                                 collections=cols.get("collections"), vocab=vocab,
                                 entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"],
                                 content_hashes=cols.get("content_hashes"),
-                                org_ids=cols.get("org_ids"))    # (None: a directory saved without the column)
+                                org_ids=cols.get("org_ids"),    # (None: a directory saved without the column)
+                                entity_ids=cols.get("entity_ids"), entity_canonical=cols.get("entity_canonical"))
     attributes = {name: arr(f"attr_{i}") for i, name in enumerate(meta.get("attributes", []))} or None
     return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, attributes=attributes, **arrays)

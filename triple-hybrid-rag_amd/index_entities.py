@@ -90,9 +90,11 @@ class EntitySearch:
 
     def set_entity_names(self, names: Sequence[str]) -> "EntitySearch":
         """The device copy of the entity names ``find_entities`` matches against (index set-up, not
-        the query path): entity e is names[e].  Built once: append_rows / delete_rows never change the
-        entity set (mentions name existing entities only), so mutations leave it alone.  After
-        set_graph the count must be the entity CSR's, and a later set_graph must bring as many entities."""
+        the query path): entity e is names[e].  append_rows / delete_rows never change the entity set
+        (their mentions name existing entities only) and leave it alone; append_graph(entity_names=)
+        extends it on the device -- the old bytes, the new names, the padding moved to the new end --
+        to what this call would build from all the names.  After set_graph the count must be the
+        entity CSR's, and a later set_graph must bring as many entities."""
         names = list(names)
         G = getattr(self, "graph", None)
         if G is not None and len(names) != G["ent_rowptr"].shape[0] - 1:

@@ -99,6 +99,7 @@ class _NewState:
     csr: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = field(default_factory=dict)    # CSR payload -> (buffer, view)
     lex: Optional[dict] = None       # the new ``lex`` dict + "df"
     graph: Optional[dict] = None
+    entities: Optional[dict] = None  # the new name store (append_graph with names)
     shortlist: Optional[str] = None  # dense channel: the flavour and the float16 error bound afterwards
     doc_rel_err: float = 0.0
 
@@ -236,6 +237,8 @@ class MutableIndex:
             self.lex = new.lex
         if new.graph is not None:
             self.graph = new.graph
+        if new.entities is not None:
+            self.entities = new.entities
         self._install_rows(new.rows)
         if self.docs is not None:
             self.shortlist, self.doc_rel_err = new.shortlist, new.doc_rel_err
@@ -381,7 +384,7 @@ class MutableIndex:
         if e.shape[0]:
             if int(e.min()) < 0 or int(e.max()) >= n_ent:
                 raise E(f"append_rows: mention entity ids must be existing entities, 0 .. {n_ent - 1} "
-                        "(new entities need set_graph)")
+                        "(append_graph adds entities)")
             if int(c.min()) < 0 or int(c.max()) >= m:
                 raise E(f"append_rows: mention chunk ids are local to the batch, 0 .. {m - 1}")
         return e, c, w
@@ -519,6 +522,177 @@ class MutableIndex:
         mc_b = (c[order] + (self.doc_base + n_old)).to(torch.int32).contiguous()
         mw_b = w[order].contiguous()
         new.graph = self._graph_with(*self._csr_append(new, G, self.GRAPH_CSR, rp_b, mc_b, mw_b))
+
+    # ------------------------------------------------------------ graph ingest
+    # New entities, relations and mentions of chunks that are already stored (DESIGN.md "Graph
+    # ingest"): what the reference's entity extraction writes behind a document's chunk inserts
+    # (rag2/entity_extraction.py:449-554).  Afterwards every graph array and the name store are what
+    # index_build.build_graph over the old rows followed by the new ones, set_graph and
+    # set_entity_names would hold: thr_csr_merge is that build's stable sort, row by row.
+    CANONICAL = ("the index's graph is not in index_build.build_graph's canonical form (relations sorted by "
+                 "(src, dst) without duplicates, mentions chunk-ascending within an entity): it came through "
+                 "set_graph from other arrays and cannot be merged into -- rebuild it with build_graph")
+
+    def _graph_or_refuse(self, who: str) -> dict:
+        if self.graph is None:
+            raise N.NativeError(f"{who}: this index has no graph channel (set_graph)")
+        return self.graph
+
+    def _merge_or_refuse(self, who: str, *a, **kw):
+        """thr_csr_merge; a status word that names an input is an error, not a graph to commit."""
+        rowptr, ids, pay, nnz, status = N.csr_merge(*a, check=False, **kw)
+        if status & N.THR_CSR_MERGE_UNSORTED_A:
+            raise N.NativeError(f"{who}: {self.CANONICAL}")
+        if status:
+            raise N.NativeError(f"{who}: thr_csr_merge: {N.csr_merge_status_message(status)}")
+        return rowptr, ids, pay, nnz
+
+    def _validate_append_graph(self, entity_names, n_new_entities, relations):
+        """What append_graph refuses before any device work -> (m, names or None, subject, object)."""
+        E, who = N.NativeError, "append_graph"
+        G = self._graph_or_refuse(who)
+        n_ent = int(G["men_rowptr"].shape[0]) - 1
+        names = None if entity_names is None else [str(nm) for nm in entity_names]
+        if names is not None and n_new_entities is not None and int(n_new_entities) != len(names):
+            raise E(f"{who}: n_new_entities differs from the number of entity names")
+        m = len(names) if names is not None else int(n_new_entities or 0)
+        if m < 0 or n_ent + m > (1 << 31) - 2:
+            raise E(f"{who}: entity count out of range")
+        if self.entities is not None and names is None and m > 0:
+            raise E(f"{who}: this index holds entity names (set_entity_names): entity_names for the "
+                    f"{m} new entities are required")
+        if self.entities is None and names and n_ent > 0:
+            raise E(f"{who}: entity_names given, but the index holds no names for its {n_ent} entities "
+                    "(set_entity_names first, or pass n_new_entities)")
+        s = o = None
+        if relations is not None and len(relations) != 2:
+            raise E(f"{who}: relations is (subject, object)")
+        if relations is not None and (self._size(relations[0]) or self._size(relations[1])):
+            s = self._host_or_device(relations[0], "relation subject", True, who).reshape(-1)
+            o = self._host_or_device(relations[1], "relation object", True, who).reshape(-1)
+            if s.shape != o.shape:
+                raise E(f"{who}: relation subject / object are 1-d arrays of one length")
+            if s.shape[0] and (min(int(s.min()), int(o.min())) < 0 or max(int(s.max()), int(o.max())) >= n_ent + m):
+                raise ValueError(f"{who}: relation endpoints are entity ids, 0 .. {n_ent + m - 1} "
+                                 f"({n_ent} existing + {m} new)")
+        return m, names, s, o
+
+    @staticmethod
+    def _size(a) -> int:
+        return int(a.numel()) if isinstance(a, torch.Tensor) else int(np.asarray(a).size)
+
+    def _names_with(self, names: List[str]) -> dict:
+        """The name store after ``names`` were added: byte for byte pack_entity_names(all names) -- the
+        old bytes up to name_ptr[E], the new names lower-cased with one 0xFF each, the padding at the
+        new end -- without the old names coming back to the host."""
+        from .index_entities import pack_entity_names
+        blob, ptr = pack_entity_names(names)
+        Ent = self.entities
+        if Ent is None:
+            return dict(name_bytes=self._t(blob, torch.uint8), name_ptr=self._t(ptr, torch.int64), n=len(names))
+        used = int(Ent["name_bytes"].shape[0]) - N.THR_ENTITY_MAX_NEEDLE      # = name_ptr[E]
+        return dict(name_bytes=torch.cat([Ent["name_bytes"][:used], self._t(blob, torch.uint8)]),
+                    name_ptr=torch.cat([Ent["name_ptr"], self._t(ptr[1:] + used, torch.int64)]),
+                    n=Ent["n"] + len(names))
+
+    @staticmethod
+    def _rows_grown(rowptr: torch.Tensor, m: int) -> torch.Tensor:
+        """``rowptr`` with m empty rows behind the last."""
+        return rowptr if m == 0 else torch.cat([rowptr, rowptr[-1:].expand(m)])
+
+    @_refuse_when_unusable
+    def append_graph(self, entity_names=None, n_new_entities: Optional[int] = None, relations=None) -> range:
+        """New entities and relations into the live index -> the range of the new entity ids.
+          entity_names    names of the m new entities: they get the ids E .. E+m-1.  Required when the
+                          index holds entity names (set_entity_names): the device name store becomes,
+                          byte for byte, pack_entity_names(all names).  An index with a graph but
+                          without names takes ``n_new_entities`` = m instead;
+          relations       (subject, object): int arrays of entity ids, old or new.  As build_graph
+                          treats them: both directions, self-loops dropped, duplicates -- inside the
+                          batch or of an edge the index holds -- dropped.
+        Afterwards ent_rowptr / ent_col / men_rowptr (and the name store) are, to the bit, what
+        build_graph over the old rows followed by the new ones, set_graph and set_entity_names would
+        hold; the new entities' rows are empty until relations or mentions arrive (append_mentions,
+        append_rows(mentions=)).  The mentions are carried over.  Everything is validated before the
+        first change and swapped in last (_commit): a refused call -- an endpoint outside the entity
+        ids (ValueError), a graph that is not in build_graph's canonical form -- leaves the index
+        answering over the old graph.  One host read of the merged edge count.  Synchronises the
+        main and the side stream (not a query-path call).  Nothing to add: a no-op."""
+        who = "append_graph"
+        m, names, s, o = self._validate_append_graph(entity_names, n_new_entities, relations)
+        G = self.graph
+        n_ent = int(G["men_rowptr"].shape[0]) - 1
+        if m == 0 and s is None:
+            return range(n_ent, n_ent)
+        n_all = n_ent + m
+        self._sync_streams()
+        new = _NewState(self.n_docs, shortlist=self.shortlist, doc_rel_err=self.doc_rel_err)
+        ent_rowptr, ent_col = self._rows_grown(G["ent_rowptr"], m), G["ent_col"]
+        if s is not None:
+            s, o = self._t(s, torch.int64), self._t(o, torch.int64)
+            real = s != o
+            s, o = s[real], o[real]
+            # both directions, unique and sorted by (src, dst): build_graph's np.unique over the pairs
+            key = torch.unique(torch.cat([s * n_all + o, o * n_all + s]))
+            src, dst = key // n_all, (key % n_all).to(torch.int32).contiguous()
+            rp_b = torch.zeros(n_all + 1, dtype=torch.int64, device=self.device)
+            rp_b[1:] = torch.cumsum(torch.bincount(src, minlength=n_all), 0)
+            dest = self._store.destination("ent_col", ent_col, int(ent_col.shape[0] + dst.shape[0]), grow=True)
+            ent_rowptr, out, _, nnz = self._merge_or_refuse(who, G["ent_rowptr"], ent_col, None, rp_b, dst, None,
+                                                            True, ids_out=dest)
+            new.csr["ent_col"] = (out, out[:nnz])
+            ent_col = new.csr["ent_col"][1]
+        new.graph = dict(ent_rowptr=ent_rowptr, ent_col=ent_col, men_rowptr=self._rows_grown(G["men_rowptr"], m),
+                         men_chunk=G["men_chunk"], men_conf=G["men_conf"])
+        if names:
+            new.entities = self._names_with(names)
+        self._commit(new)
+        return range(n_ent, n_all)
+
+    @_refuse_when_unusable
+    def append_mentions(self, entity, chunk, conf=None) -> None:
+        """Mentions of chunks the index already holds.  ``entity``: ids of existing entities (those of
+        an earlier append_graph included), ``chunk``: LOCAL doc ids 0 .. n_docs-1 (stored as
+        + doc_base), ``conf``: float per mention, 1.0 when None; any order, repeats are kept.  The
+        batch is sorted by (entity, chunk), stably, and merged into the entity-major mention CSR with
+        thr_csr_merge: afterwards men_rowptr / men_chunk / men_conf are, to the bit, what build_graph
+        over the old mention rows followed by these would hold.  Validated before the first change,
+        swapped in last; a refused call leaves the index answering over the old graph.  Synchronises
+        the main and the side stream (not a query-path call)."""
+        E, who = N.NativeError, "append_mentions"
+        G = self._graph_or_refuse(who)
+        if not (self._size(entity) or self._size(chunk) or (conf is not None and self._size(conf))):
+            return
+        e = self._host_or_device(entity, "entity", True, who).reshape(-1)
+        c = self._host_or_device(chunk, "chunk", True, who).reshape(-1)
+        w = None if conf is None else self._host_or_device(conf, "conf", who=who).reshape(-1)
+        if c.shape != e.shape or (w is not None and w.shape != e.shape):
+            raise E(f"{who}: entity / chunk / conf are 1-d arrays of one length")
+        if not e.shape[0]:
+            return
+        n_ent = int(G["men_rowptr"].shape[0]) - 1
+        if int(e.min()) < 0 or int(e.max()) >= n_ent:
+            raise ValueError(f"{who}: entity ids are existing entities, 0 .. {n_ent - 1} (append_graph adds entities)")
+        if int(c.min()) < 0 or int(c.max()) >= self.n_docs:
+            raise ValueError(f"{who}: chunk ids are local doc ids of stored chunks, 0 .. {self.n_docs - 1}")
+        self._sync_streams()
+        e, c = self._t(e, torch.int64), self._t(c, torch.int64)
+        w = torch.ones(e.shape[0], dtype=torch.float32, device=self.device) if w is None else self._t(w, torch.float32)
+        order = torch.sort(c, stable=True).indices
+        order = order[torch.sort(e[order], stable=True).indices]
+        rp_b = torch.zeros(n_ent + 1, dtype=torch.int64, device=self.device)
+        rp_b[1:] = torch.cumsum(torch.bincount(e, minlength=n_ent), 0)
+        mc_b = (c[order] + self.doc_base).to(torch.int32).contiguous()
+        mw_b = w[order].contiguous()
+        new = _NewState(self.n_docs, shortlist=self.shortlist, doc_rel_err=self.doc_rel_err)
+        nnz = int(G["men_chunk"].shape[0] + mc_b.shape[0])
+        d0, d1 = (self._store.destination(k, G[k], nnz, grow=True) for k in ("men_chunk", "men_conf"))
+        rowptr, out0, out1, nnz = self._merge_or_refuse(who, G["men_rowptr"], G["men_chunk"], G["men_conf"], rp_b,
+                                                        mc_b, mw_b, False, ids_out=d0, pay_out=d1)
+        new.csr["men_chunk"], new.csr["men_conf"] = (out0, out0[:nnz]), (out1, out1[:nnz])
+        # (a fresh dict: the chunk-major copy cached in the old one is keyed on n_docs, which stays)
+        new.graph = self._graph_with(rowptr, new.csr["men_chunk"][1], new.csr["men_conf"][1])
+        self._commit(new)
 
     # ------------------------------------------------------------ delete
     # Delete in place (DESIGN.md "Delete in place"): after delete_rows every device array is what a

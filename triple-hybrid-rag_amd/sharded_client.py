@@ -102,6 +102,15 @@ class _ShardEndpoint(GpuIndexClient):
         raise N.NativeError("insert is not supported through a sharded index client: rebuild the shards "
                             "(appends to a document-sharded index are out of scope)")
 
+    def _refuse_graph_ingest(self, *_a, **_kw):
+        """Not supported: every rank holds the whole entity CSR and its own chunks' mentions, so an
+        insert into rag_entities / rag_relations / rag_entity_mentions would be a collective with a
+        rule for which rank takes a mention (Graph ingest)."""
+        raise N.NativeError("graph ingest is not supported through a sharded index client: rebuild the shards "
+                            "(graph ingest into a document-sharded index is out of scope)")
+
+    insert_entities = insert_relations = insert_mentions = _refuse_graph_ingest
+
     def _refuse_delete(self, *_a, **_kw):
         """Not supported: a delete from a document-sharded index needs the same collective df /
         length all-reduce as an append, and the front's store holds the WHOLE corpus' rows while
