@@ -631,6 +631,102 @@ int thr_entity_match(const uint8_t *name_bytes, const int64_t *name_ptr, int64_t
                      int32_t *seeds /* [nq, THR_GRAPH_MAX_SEEDS] */, int32_t *counts /* [nq] */,
                      void *workspace, size_t workspace_bytes, thr_stream_t stream);
 
+/* a9  text to BM25 term ids, for a batch.  Stands where rag2_lexical_search hands p_query to
+ * plainto_tsquery (rag2_schema.sql:365) for queries and where ingest.py inserts a child chunk's text
+ * column (the database tokenises it) for rows; the host restatement is backend.tokenize (\w+ over
+ * text.lower()), a lookup in store.vocab and GpuIndexClient._query_terms.
+ *
+ * THE ANALYSIS IS A TABLE: uint32 [65536], one entry per BMP code point: bits 0..15 the lowered code
+ * point, bit 16 (THR_TEXT_WORD) the lowered character is a word character, bit 17 (THR_TEXT_EXC) the
+ * code point is exceptional (its lowering is not one BMP code point or depends on context).  Every
+ * surrogate's entry carries bit 17.  A text that holds an exceptional code point, a code point above
+ * U+FFFF, a surrogate (three-byte generalised UTF-8) or malformed UTF-8 (a stray continuation byte, a
+ * character cut off by the end of its text, an overlong form, 0xC0, 0xC1, 0xF5 ..) gets
+ * THR_TEXT_EXCEPTIONAL in its flags: the caller redoes it on the host.
+ *
+ * THE VOCABULARY is an open-addressing table of ``capacity`` (a power of two, THR_VOCAB_MIN_SLOTS ..
+ * THR_VOCAB_MAX_SLOTS) 16-byte slots { uint64 hash; int32 term_id; int32 pad } on a 16-byte boundary,
+ * all zero when empty, beside the key store: term_bytes uint8 = the keys' UTF-8 as they stand (tokens
+ * are lowered before they are compared, keys never), term_ptr int64 [n_vocab + 1], key t =
+ * [term_ptr[t], term_ptr[t + 1]).  hash(key) = 64-bit FNV-1a over the key's bytes (h =
+ * 0xCBF29CE484222325; per byte h = (h ^ byte) * 0x100000001B3 mod 2^64), a result of 0 replaced by 1
+ * (hash 0 = an empty slot).  Home slot = (uint32)(hash ^ (hash >> 32)) & (capacity - 1); linear
+ * probing, wrapping at the end; a lookup ends at the first empty slot.  A slot whose hash equals a
+ * token's is taken only when the key's bytes equal the lowered token's: otherwise it is passed over.
+ *
+ * thr_vocab_insert puts keys first_id .. first_id + count - 1 of the key store into the table (each
+ * claims the first free slot from its home by a 64-bit compare-and-swap on the hash word): the initial
+ * build (first_id 0 into a zeroed table) and growth.  Equal keys in the store are the caller's error.
+ * Refused (THR_ERR_INVALID): null pointers, capacity not such a power of two, slots not 16-byte or
+ * term_ptr not 8-byte aligned, first_id < 0, count < 1, first_id + count > capacity / 2 (the load
+ * stays at or below 1/2: the caller reallocates and inserts everything again).
+ * thr_vocab_table_bytes: 16 * capacity, 0 for a capacity thr_vocab_insert refuses.
+ *
+ * thr_text_tokens: text_bytes uint8, 16-byte aligned + text_ptr int64 [n_texts + 1], text_ptr[0] = 0,
+ * ascending, text_ptr[n_texts] = n_bytes: text d is [text_ptr[d], text_ptr[d + 1]).  REQUIRED PADDING:
+ * the allocation holds at least 4 readable bytes behind n_bytes; nothing outside [0, n_bytes + 4) is
+ * read, whatever the bytes are.
+ * A token starts at the lead byte of a word character that is the first byte of its text or whose
+ * previous character is not a word character, and runs to the last word character in front of the next
+ * other character or the end of its text: no token crosses a text_ptr boundary.  Its term: each
+ * character lowered through the table, the lowered characters' UTF-8 hashed as above, the table
+ * probed, a hit verified byte for byte against the key store (the lowering can change a character's
+ * encoded length; nothing is written anywhere in lowered form).
+ *   tok_doc, tok_term int32 [token_capacity]: per token in text order its text and its term id, -1
+ *      for a token outside the vocabulary (it still counts); n_tokens int32 [n_texts];
+ *   flags int32 [n_texts]: THR_TEXT_EXCEPTIONAL.  The rows of a flagged text may hold anything; they
+ *      are n_tokens[d] in number and in their place;
+ *   n_total int32 [1]: all tokens.  Rows at or behind token_capacity are not written: a caller that
+ *      reads n_total > token_capacity calls again with more room ((n_bytes + n_texts + 1) / 2 always
+ *      suffices);
+ *   unknown_off int64 / unknown_len int32 [token_capacity], n_unknown int32 [1]: byte offset and byte
+ *      length of the tokens with term -1, in text order.
+ * Count, scan, scatter over slices of THR_TEXT_SLICE_BYTES bytes staged in LDS with a halo; no
+ * workgroup waits for another, nothing is read back, the same bits every run.
+ * Refused before any launch: n_texts outside 1 .. THR_TEXT_MAX_TEXTS, n_bytes outside 0 ..
+ * THR_TEXT_MAX_BYTES, token_capacity outside 1 .. THR_TEXT_MAX_BYTES (THR_ERR_UNSUPPORTED; the size
+ * query returns 0); null pointers, a capacity thr_vocab_insert refuses, n_vocab outside 0 ..
+ * capacity / 2, text_bytes or slots not 16-byte, text_ptr / term_ptr / unknown_off / workspace not
+ * 8-byte, table not 4-byte aligned (THR_ERR_INVALID); ``workspace`` <
+ * thr_text_tokens_workspace_bytes() (THR_ERR_WORKSPACE).
+ *
+ * thr_query_terms: GpuIndexClient._query_terms for a batch, from the rows of a thr_text_tokens call
+ * whose texts are the queries (tok_term, n_tokens, flags, n_total, token_capacity as there): one wave
+ * per query over its tokens, 64 at a time.
+ *   out_terms int32 [n_queries, THR_BM25_MAX_TERMS]: the distinct known term ids in order of first
+ *      appearance, padded with -1 (the query_terms table of thr_bm25_topk);
+ *   n_distinct int32 [n_queries]: their number, clamped at THR_BM25_MAX_TERMS + 1;
+ *   out_flags int32 [n_queries]: THR_TEXT_EXCEPTIONAL (copied), THR_TEXT_UNKNOWN (a token outside the
+ *      vocabulary occurred), THR_TEXT_TOO_MANY (more than THR_BM25_MAX_TERMS distinct terms).
+ * Refused: n_queries outside 1 .. THR_TEXT_MAX_TEXTS, token_capacity outside 1 .. THR_TEXT_MAX_BYTES
+ * (THR_ERR_UNSUPPORTED; the size query returns 0), null pointers, workspace not 4-byte aligned
+ * (THR_ERR_INVALID), ``workspace`` < thr_query_terms_workspace_bytes() (THR_ERR_WORKSPACE). */
+#define THR_TEXT_SLICE_BYTES 8192
+#define THR_TEXT_MAX_TEXTS (1 << 20)
+#define THR_TEXT_MAX_BYTES 0x7FFFFFFF
+#define THR_TEXT_WORD (1 << 16)
+#define THR_TEXT_EXC (1 << 17)
+#define THR_TEXT_EXCEPTIONAL 1
+#define THR_TEXT_UNKNOWN 2
+#define THR_TEXT_TOO_MANY 4
+#define THR_VOCAB_MIN_SLOTS 16
+#define THR_VOCAB_MAX_SLOTS (1 << 30)
+size_t thr_vocab_table_bytes(int64_t capacity);
+int thr_vocab_insert(void *slots, int64_t capacity, const uint8_t *term_bytes, const int64_t *term_ptr,
+                     int64_t first_id, int64_t count, thr_stream_t stream);
+size_t thr_text_tokens_workspace_bytes(int64_t n_texts, int64_t n_bytes, int64_t token_capacity);
+int thr_text_tokens(const uint8_t *text_bytes, const int64_t *text_ptr, int64_t n_texts, int64_t n_bytes,
+                    const uint32_t *table /* [65536] */, const void *slots, int64_t capacity,
+                    const uint8_t *term_bytes, const int64_t *term_ptr, int64_t n_vocab,
+                    int64_t token_capacity, int32_t *tok_doc, int32_t *tok_term, int32_t *n_tokens,
+                    int32_t *flags, int32_t *n_total, int64_t *unknown_off, int32_t *unknown_len,
+                    int32_t *n_unknown, void *workspace, size_t workspace_bytes, thr_stream_t stream);
+size_t thr_query_terms_workspace_bytes(int n_queries);
+int thr_query_terms(const int32_t *tok_term, const int32_t *n_tokens, const int32_t *text_flags,
+                    const int32_t *n_total, int64_t token_capacity, int n_queries,
+                    int32_t *out_terms /* [nq, THR_BM25_MAX_TERMS] */, int32_t *n_distinct,
+                    int32_t *out_flags, void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
 /* a5+a6  candidate merge + weighted Reciprocal Rank Fusion, bit-for-bit the
  * float64 arithmetic and stable ordering of RAG2Retriever._retrieve_candidates
  * / _fuse_rrf, src/voice_agent/rag2/retrieval.py:203-271, 358-376.

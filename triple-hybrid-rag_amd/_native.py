@@ -41,6 +41,13 @@ THR_ENTITY_MAX_NEEDLE = 128     # bytes of a keyword's lowered UTF-8 thr_entity_
 THR_ENTITY_MAX_KEYWORDS = 5
 THR_ENTITY_MAX_QUERIES = 1 << 20
 THR_ENTITY_SLICE_BYTES = 8192   # name bytes a workgroup of thr_entity_match stages at a time
+THR_TEXT_SLICE_BYTES = 8192     # text bytes a workgroup of thr_text_tokens stages at a time
+THR_TEXT_MAX_TEXTS = 1 << 20    # texts of one thr_text_tokens / thr_query_terms call
+THR_TEXT_MAX_BYTES = 0x7FFFFFFF   # bytes of one thr_text_tokens call
+THR_TEXT_WORD, THR_TEXT_EXC = 1 << 16, 1 << 17   # bits of a TextTable entry above the lowered code point
+# bits of the text flags: redo on the host; (thr_query_terms) an unknown token occurred; more than 32 distinct terms
+THR_TEXT_EXCEPTIONAL, THR_TEXT_UNKNOWN, THR_TEXT_TOO_MANY = 1, 2, 4
+THR_VOCAB_MIN_SLOTS, THR_VOCAB_MAX_SLOTS = 16, 1 << 30
 THR_CSR_MERGE_SLICE = 1024      # positions a workgroup of thr_csr_merge owns
 # bits of thr_csr_merge's status word: an input breaks its mode's ordering; the result exceeds out_capacity
 THR_CSR_MERGE_UNSORTED_A, THR_CSR_MERGE_UNSORTED_B, THR_CSR_MERGE_OVERFLOW = 1, 2, 4
@@ -117,6 +124,13 @@ _SIGNATURES = {
                                      _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_entity_match_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "thr_entity_match": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "thr_vocab_table_bytes": (_sz, [_i64]),
+    "thr_vocab_insert": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp]),
+    "thr_text_tokens_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "thr_text_tokens": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _sz, _vp]),
+    "thr_query_terms_workspace_bytes": (_sz, [_i32]),
+    "thr_query_terms": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_rrf_fuse": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
                             _vp, _vp, _vp, _vp, _vp]),
     "thr_rrf_fuse_standalone": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
@@ -1128,6 +1142,85 @@ def entity_match(name_bytes, name_ptr, needles, needle_len, query_needles, query
     _check(load().thr_entity_match(pb, pp, n_ent, pn, pl, M, pq, pr, nq, seeds.data_ptr(), counts.data_ptr(),
                                    ws.data_ptr(), ws.numel(), _stream()), "thr_entity_match")
     return seeds, counts
+
+
+def vocab_insert(slots, term_bytes, term_ptr, first_id: int, count: int) -> None:
+    """thr_vocab_insert: keys first_id .. first_id + count - 1 of the key store (term_bytes u8, term_ptr i64
+    [V + 1]) into the open-addressing table ``slots`` (int64 [capacity, 2]: a slot's hash word and its
+    (term_id, pad) pair; zero = empty)."""
+    ps = _dev(slots, torch.int64, "slots", 2)
+    if slots.shape[1] != 2:
+        raise NativeError("vocab_insert: slots is int64 [capacity, 2]")
+    pb = _dev(term_bytes, torch.uint8, "term_bytes", 1)
+    pp = _dev(term_ptr, torch.int64, "term_ptr", 1)
+    if first_id < 0 or count < 1 or first_id + count > term_ptr.shape[0] - 1:
+        raise NativeError(f"vocab_insert: keys {first_id} .. {first_id + count - 1} of {term_ptr.shape[0] - 1}")
+    _check(load().thr_vocab_insert(ps, slots.shape[0], pb, pp, first_id, count, _stream()), "thr_vocab_insert")
+
+
+def text_token_capacity(n_texts: int, n_bytes: int) -> int:
+    """Token rows that always suffice: a token takes a byte and two tokens of a text a byte between them."""
+    return max((n_bytes + n_texts + 1) // 2, 1)
+
+
+def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, term_ptr, workspace=None,
+                token_capacity: Optional[int] = None):
+    """thr_text_tokens -> dict(doc i32 [cap], term i32 [cap], n_tokens i32 [n], flags i32 [n], n_total i32 [1],
+    unknown_off i64 [cap], unknown_len i32 [cap], n_unknown i32 [1], capacity), all on the device: the first
+    n_total rows (n_unknown entries) are valid.  text_bytes u8 holds n_bytes bytes of texts and at least 4
+    more; text_ptr i64 [n + 1]; table u32-as-int32 [65536]; the vocabulary as vocab_insert takes it.  No host
+    read-back."""
+    pb = _dev(text_bytes, torch.uint8, "text_bytes", 1)
+    pp = _dev(text_ptr, torch.int64, "text_ptr", 1)
+    n = text_ptr.shape[0] - 1
+    pt = _dev(table, torch.int32, "table", 1)
+    ps = _dev(slots, torch.int64, "slots", 2)
+    pk = _dev(term_bytes, torch.uint8, "term_bytes", 1)
+    pkp = _dev(term_ptr, torch.int64, "term_ptr", 1)
+    if table.shape[0] != 65536 or slots.shape[1] != 2:
+        raise NativeError("text_tokens: table is [65536], slots int64 [capacity, 2]")
+    if not 1 <= n <= THR_TEXT_MAX_TEXTS:
+        raise NativeError(f"text_tokens: 1 .. {THR_TEXT_MAX_TEXTS} texts per call, got {n}")
+    if not 0 <= n_bytes <= THR_TEXT_MAX_BYTES or text_bytes.shape[0] < n_bytes + 4:
+        raise NativeError(f"text_tokens: {n_bytes} bytes (at most {THR_TEXT_MAX_BYTES}) and 4 of padding behind them, "
+                          f"the array holds {text_bytes.shape[0]}")
+    cap = text_token_capacity(n, n_bytes) if token_capacity is None else int(token_capacity)
+    need = int(load().thr_text_tokens_workspace_bytes(n, n_bytes, cap))
+    ws = workspace
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=text_bytes.device)
+    dev = text_bytes.device
+    out = dict(doc=torch.empty(cap, dtype=torch.int32, device=dev), term=torch.empty(cap, dtype=torch.int32, device=dev),
+               n_tokens=torch.empty(n, dtype=torch.int32, device=dev), flags=torch.empty(n, dtype=torch.int32, device=dev),
+               n_total=torch.empty(1, dtype=torch.int32, device=dev),
+               unknown_off=torch.empty(cap, dtype=torch.int64, device=dev),
+               unknown_len=torch.empty(cap, dtype=torch.int32, device=dev),
+               n_unknown=torch.empty(1, dtype=torch.int32, device=dev), capacity=cap)
+    _check(load().thr_text_tokens(pb, pp, n, n_bytes, pt, ps, slots.shape[0], pk, pkp, term_ptr.shape[0] - 1, cap,
+                                  out["doc"].data_ptr(), out["term"].data_ptr(), out["n_tokens"].data_ptr(),
+                                  out["flags"].data_ptr(), out["n_total"].data_ptr(), out["unknown_off"].data_ptr(),
+                                  out["unknown_len"].data_ptr(), out["n_unknown"].data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream()), "thr_text_tokens")
+    return out
+
+
+def query_terms(rows: dict, workspace=None):
+    """thr_query_terms over the rows text_tokens returned for a batch of queries -> (terms i32
+    [nq, THR_BM25_MAX_TERMS] padded with -1, n_distinct i32 [nq], flags i32 [nq]).  No host read-back."""
+    nq = rows["n_tokens"].shape[0]
+    dev = rows["term"].device
+    need = int(load().thr_query_terms_workspace_bytes(nq))
+    ws = workspace
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    terms = torch.empty((nq, THR_BM25_MAX_TERMS), dtype=torch.int32, device=dev)
+    nd = torch.empty(nq, dtype=torch.int32, device=dev)
+    fl = torch.empty(nq, dtype=torch.int32, device=dev)
+    _check(load().thr_query_terms(_dev(rows["term"], torch.int32, "term", 1), _dev(rows["n_tokens"], torch.int32, "n_tokens", 1),
+                                  _dev(rows["flags"], torch.int32, "flags", 1), _dev(rows["n_total"], torch.int32, "n_total", 1),
+                                  rows["capacity"], nq, terms.data_ptr(), nd.data_ptr(), fl.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream()), "thr_query_terms")
+    return terms, nd, fl
 
 
 def graph_transpose_mentions(men_rowptr, men_chunk, men_conf, chunk_base: int, n_chunks: int):

@@ -54,6 +54,7 @@ import torch
 from . import _native as N
 from .index import GpuIndex
 from .index_scope import In
+from .index_text import TextTable, is_table_tokenizer
 
 _TOKEN = re.compile(r"[\w]+", re.UNICODE)
 
@@ -420,7 +421,8 @@ class GpuIndexClient:
     def __init__(self, index: GpuIndex, store: CorpusStore, org_id: Optional[str] = None,
                  token_embedder: Any = None, lexical_and: bool = False,
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
-                 collection_names: Optional[Sequence[str]] = None):
+                 collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
+                 tokenizer: Any = None):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's
         ``plainto_tsquery`` does (rag2_schema.sql:365); default is BM25's OR form, the
         north star's and the oracle's.
@@ -437,7 +439,12 @@ class GpuIndexClient:
         distinct names; one it already has is checked against the store's column), each RPC and
         ``graph_chunks`` rank inside {"org": p_org_id} (+ "collection") through the index's scopes,
         a missing or unknown org gets no rows, ``table().eq("org_id", x)`` filters rows, and an
-        insert needs ``org_id`` on every row."""
+        insert needs ``org_id`` on every row.
+        tokenizer: what the index's vocabulary was built with (default ``tokenize``, from_rows' default).
+        device_text: query and chunk text become term ids on the device (GpuIndex.set_vocabulary from
+        ``store.vocab`` -- derived state, rebuilt here, never saved): ``_lexical`` and ``insert_children``
+        take that route and ``query_terms_batch`` serves batches.  Needs ``tokenize`` or a TextTable's
+        ``.tokenize`` as the tokenizer; any other is refused by name."""
         self.lexical_and = bool(lexical_and)
         self.image_index = image_index
         self.image_rows = None if image_rows is None else [int(r) for r in image_rows]
@@ -447,7 +454,8 @@ class GpuIndexClient:
         self.store = store
         self.org_id = org_id
         self.token_embedder = token_embedder
-        self.tokenizer = tokenize     # what the index's vocabulary was built with (from_rows' default)
+        self.tokenizer = tokenizer or tokenize
+        self.device_text = False
         self._pin: Dict[Any, list] = {}   # reusable pinned staging buffers (one query per call)
         # collection names -> ids; the filter itself runs on the device, before the ranking
         self._coll_id: Dict[str, int] = {}
@@ -480,6 +488,45 @@ class GpuIndexClient:
                 if ix is not None and "org" not in ix.attribute_names():
                     orgs = store.org_ids if rows is None else [store.org_ids[r] for r in rows]
                     ix.set_attributes({"org": np.array([self._org_code.get(o, -1) for o in orgs], dtype=np.int32)})
+        if device_text:
+            self._text_table()          # (refuses a custom tokenizer before anything is uploaded)
+            self.device_text = True
+            self._sync_vocabulary()
+
+    # -------------------------------------------------------------- text on the device
+    def _text_table(self) -> TextTable:
+        """The analysis table of this client's tokenizer; a tokenizer that is no table is refused."""
+        if self.tokenizer is tokenize:
+            return TextTable.default()
+        table = is_table_tokenizer(self.tokenizer)
+        if table is None:
+            name = getattr(self.tokenizer, "__qualname__", None) or repr(self.tokenizer)
+            raise ValueError(f"device_text=True needs backend.tokenize or a TextTable's .tokenize as the tokenizer, "
+                             f"not {name}: the device restates a table, not a function")
+        return table
+
+    def _sync_vocabulary(self) -> None:
+        """The index's device vocabulary is store.vocab's (built on first use, rebuilt when another writer
+        grew the store's)."""
+        idx, vocab = self.index, self.store.vocab
+        table = self._text_table()
+        X = idx.text
+        if X is None or X["table"] is not table or len(X["ids"]) != len(vocab):
+            terms = [None] * len(vocab)
+            for tok, t in vocab.items():
+                terms[t] = tok
+            if any(t is None for t in terms):
+                raise ValueError("device_text: store.vocab's ids are not 0 .. len - 1")
+            idx.set_vocabulary(terms, table)
+
+    def query_terms_batch(self, queries: Sequence[str]):
+        """``_query_terms`` for a batch of query texts, on the device (GpuIndex.query_terms) -> the int32
+        [nq, THR_BM25_MAX_TERMS] device table ``index.retrieve_batch(query_terms=)`` / ``bm25_search`` take;
+        under ``lexical_and`` a query nothing can match is an all -1 row."""
+        if not self.device_text:
+            raise ValueError("query_terms_batch: the client was made without device_text=True")
+        self._sync_vocabulary()
+        return self.index.query_terms(list(queries), conjunctive=self.lexical_and)[0]
 
     def _scope(self, org, collection=None, index=None):
         """Multi-tenant: the ScopePlan of a one-query call inside ``org`` (and ``collection``), made
@@ -716,14 +763,20 @@ class GpuIndexClient:
                 pending.materialize()   # read it back before the kernels of this one are enqueued
             except Exception:           # (its own caller sees that failure when it looks at the rows)
                 pass
-        terms = self._query_terms(query)
-        if terms is None:
-            return []
+        if self.device_text and getattr(self.index, "lex", None) is not None:
+            terms = None
+        else:
+            terms = self._query_terms(query)
+            if terms is None:
+                return []
         within = self._scoped(org, collection)
         if within is None:
             return []
-        # (fixed width: one pinned buffer, one workspace size, whatever the number of terms)
-        qt = self._upload(terms + [-1] * (N.THR_BM25_MAX_TERMS - len(terms)), torch.int32, self.index.device)
+        if terms is None:
+            qt = self.query_terms_batch([query])    # (a query nothing can match: an all -1 row, no rows)
+        else:
+            # (fixed width: one pinned buffer, one workspace size, whatever the number of terms)
+            qt = self._upload(terms + [-1] * (N.THR_BM25_MAX_TERMS - len(terms)), torch.int32, self.index.device)
         k = min(N.THR_TOPK_MAX, limit)
         if not defer or self.index.device.type != "cuda":
             S, I, _ = self.index.bm25_search(qt, k, conjunctive=self.lexical_and, **within)
@@ -795,7 +848,19 @@ class GpuIndexClient:
         else:
             parts.update(docs=None, n_rows=m)
         vocab = st.vocab
-        if getattr(idx, "lex", None) is not None:
+        text_rows = None
+        if getattr(idx, "lex", None) is not None and self.device_text:
+            # the same on the device: the unknown tokens come back as strings and are numbered here, in
+            # order of first appearance across the batch, exactly as the loop below numbers them
+            self._sync_vocabulary()
+            text_rows = idx.text_rows([r.get("text", "") for r in rows])
+            grown = {tok: len(vocab) + i for i, tok in enumerate(text_rows.unknown)}
+            t_dev = text_rows.term
+            if len(text_rows.unknown_which):
+                t_dev = t_dev.clone()
+                t_dev[t_dev < 0] = torch.from_numpy((len(vocab) + text_rows.unknown_which).astype(np.int32)).to(idx.device)
+            parts["lex"] = (text_rows.doc, t_dev, None, max(len(vocab) + len(grown), 1))
+        elif getattr(idx, "lex", None) is not None:
             # term ids of the store's vocabulary; unseen terms get the next ids (committed to the
             # store only after the index took the rows)
             grown: Dict[str, int] = {}
@@ -838,7 +903,13 @@ class GpuIndexClient:
             parts["mentions"] = (np.asarray(me, dtype=np.int64), np.asarray(mc, dtype=np.int64),
                                  np.asarray(mw, dtype=np.float32))
         idx.append_rows(**parts)
-        st.append(rows, tokenizer=self.tokenizer if getattr(idx, "lex", None) is not None else None)
+        if text_rows is not None:       # index before store: the device vocabulary, then the rows, then the terms
+            if text_rows.unknown:
+                idx.grow_vocabulary(text_rows.unknown)
+            st.append(rows, tokenizer=None)
+            st.vocab.update(grown)
+        else:
+            st.append(rows, tokenizer=self.tokenizer if getattr(idx, "lex", None) is not None else None)
         if self.multi_tenant:
             self._org_code = org_code
             self._settle_deferred()   # (a deferred search may still read the plans' labels)

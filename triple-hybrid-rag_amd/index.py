@@ -38,6 +38,7 @@ import torch
 from . import _native as N
 from .index_mutate import MutableIndex, _refuse_when_unusable, _Storage
 from .index_entities import EntitySearch
+from .index_text import TextSearch
 from .index_scope import ScopedSearch, ScopePlan
 
 log = logging.getLogger(__name__)
@@ -62,7 +63,7 @@ class BatchResult:
     rescued: object = 0
 
 
-class GpuIndex(ScopedSearch, EntitySearch, MutableIndex):
+class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
     # what an index has before anything sets it (also: one made without __init__, as the host tests do)
     _side = None                # the second HIP stream of side_channels, made on first use
     _shortlist_of = None        # what the candidate lists in the dense workspace belong to (dense_shortlist)

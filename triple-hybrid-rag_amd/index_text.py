@@ -1,0 +1,334 @@
+"""Query and chunk text to BM25 term ids, for a whole batch on the device.
+
+The lexical channel takes term ids; the reference hands text to PostgreSQL (``plainto_tsquery(p_query)`` in
+rag2_lexical_search, the text column of ingest.py's child-chunk insert) and the host restatement is
+``backend.tokenize`` (``\\w+`` over ``text.lower()``), a lookup in ``store.vocab`` and
+``GpuIndexClient._query_terms``.  ``TextSearch`` is the part of ``GpuIndex`` that holds a device copy of the
+vocabulary (``set_vocabulary`` / ``grow_vocabulary``: an open-addressing hash table beside the keys' bytes)
+and turns the texts of a batch into token rows (``text_rows``: thr_text_tokens) or into the int32 [nq, 32]
+table ``bm25_search`` / ``retrieve_batch(query_terms=)`` take (``query_terms``: + thr_query_terms).
+
+The analysis is DATA: a ``TextTable`` holds, per BMP code point, the lowered code point, whether the lowered
+character is a word character and whether the code point is EXCEPTIONAL -- the per-character model does not
+hold for it.  ``TextTable.default()`` is built from Python itself (``chr(cp).lower()``, ``re.fullmatch(r"\\w",
+...)``), so the device equals ``backend.tokenize`` by construction and not by a copied Unicode database; the
+exceptional code points are derived, never listed: those whose lowering is not one BMP code point, and those
+for which the per-character restatement disagrees with the tokenizer in one of ``CONTEXTS``.  A text that
+holds an exceptional code point, a code point above U+FFFF or a surrogate is EXCEPTIONAL: the device flags
+it, the wrappers here find it on the host beforehand (one regular-expression search per text) and answer it
+with the table's host tokenizer, so the answer is always the host's.
+
+What stays on the host: the UTF-8 encoding (("utf-8", "surrogatepass"), as index_entities), the exceptional
+texts, and the strings of unknown tokens (an ingest numbers them: GpuIndexClient.insert_children).
+"""
+from __future__ import annotations
+
+import functools
+import re
+import unicodedata
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+_TOKEN = re.compile(r"[\w]+", re.UNICODE)       # backend.tokenize's
+_WORD = re.compile(r"\w", re.UNICODE)
+CONTEXTS = ("a{}a", " {} ", "a{}", "{}a")       # between letters, between spaces, letter-left, letter-right
+
+
+def _lower_words(text: str) -> List[str]:
+    return _TOKEN.findall(text.lower())
+
+
+def fold_accents(c: str) -> str:
+    """The shipped example of a character map: accent folding on top of lowering -- NFD of the lowered
+    character with the combining marks (Mn) stripped, kept only where that leaves one code point."""
+    low = c.lower()
+    bare = "".join(ch for ch in unicodedata.normalize("NFD", low) if unicodedata.category(ch) != "Mn")
+    return bare if len(bare) == 1 else low
+
+
+class TextTable:
+    """uint32 [65536]: bits 0..15 the lowered code point, THR_TEXT_WORD, THR_TEXT_EXC (thr_hip.h, a9)."""
+
+    def __init__(self, entries: np.ndarray, host: Callable[[str], List[str]]):
+        entries = np.ascontiguousarray(entries, dtype=np.uint32)
+        if entries.shape != (65536,):
+            raise ValueError("a TextTable has one entry per BMP code point")
+        self.entries = entries
+        self._host = host        # the tokenizer the table restates: the answer for exceptional texts
+        low = entries & 0xFFFF
+        word = (entries & N.THR_TEXT_WORD) != 0
+        # str.translate over a 65536-character string: a word character becomes its lowering, any other a space
+        self._map = "".join(chr(int(c)) if w else " " for c, w in zip(low.tolist(), word.tolist()))
+        self._exc_re: Optional[re.Pattern] = None
+
+    # ------------------------------------------------------------ the host twin
+    def restate(self, text: str) -> List[str]:
+        """The per-character model, in plain Python: what the device computes for a text that is not
+        exceptional (each character replaced by its entry, maximal runs of word characters)."""
+        return text.translate(self._map).split()
+
+    def is_exceptional(self, text: str) -> bool:
+        if self._exc_re is None:
+            exc = np.flatnonzero(self.entries & N.THR_TEXT_EXC)
+            cls = "".join(re.escape(chr(int(c))) for c in exc)
+            self._exc_re = re.compile("[" + cls + "\U00010000-\U0010FFFF]")
+        return self._exc_re.search(text) is not None
+
+    def exceptional_among(self, texts: Sequence[str]) -> List[int]:
+        """The indices of the exceptional texts (one search over the joined batch settles the usual case)."""
+        if not self.is_exceptional("\n".join(texts)):
+            return []
+        return [d for d, t in enumerate(texts) if self.is_exceptional(t)]
+
+    def tokenize(self, text: str) -> List[str]:
+        """The host tokenizer of this table (hand it to from_rows / GpuIndexClient): the restatement, and
+        for an exceptional text the tokenizer the table was built from."""
+        return self._host(text) if self.is_exceptional(text) else self.restate(text)
+
+    # ------------------------------------------------------------ builders
+    @staticmethod
+    @functools.lru_cache(maxsize=1)
+    def default() -> "TextTable":
+        """backend.tokenize as a table, built from this Python's own str.lower() and \\w."""
+        entries = np.zeros(65536, dtype=np.uint32)
+        for cp in range(65536):
+            low = chr(cp).lower()
+            if len(low) != 1 or ord(low) > 0xFFFF or 0xD800 <= cp <= 0xDFFF:
+                entries[cp] = cp | N.THR_TEXT_EXC
+                continue
+            entries[cp] = ord(low) | (N.THR_TEXT_WORD if _WORD.fullmatch(low) else 0)
+        table = TextTable(entries, _lower_words)
+        # context-dependent lowerings cannot be seen per character: a code point for which the restatement
+        # disagrees with the tokenizer in some context is exceptional too
+        for cp in range(65536):
+            if entries[cp] & N.THR_TEXT_EXC:
+                continue
+            c = chr(cp)
+            if any(table.restate(ctx.format(c)) != _lower_words(ctx.format(c)) for ctx in CONTEXTS):
+                entries[cp] |= N.THR_TEXT_EXC
+        return TextTable(entries, _lower_words)
+
+    @staticmethod
+    def from_char_map(fn: Callable[[str], str]) -> "TextTable":
+        """The analyzer hook: ``fn`` maps one character to one character (``fold_accents``); the tokenizer
+        is "map each character, then \\w+".  A code point ``fn`` does not map to one BMP code point is
+        exceptional (its texts are answered by that definition on the host)."""
+        entries = np.zeros(65536, dtype=np.uint32)
+        for cp in range(65536):
+            m = fn(chr(cp))
+            if len(m) != 1 or ord(m) > 0xFFFF or 0xD800 <= cp <= 0xDFFF:
+                entries[cp] = cp | N.THR_TEXT_EXC
+                continue
+            entries[cp] = ord(m) | (N.THR_TEXT_WORD if _WORD.fullmatch(m) else 0)
+        return TextTable(entries, lambda text: _TOKEN.findall("".join(map(fn, text))))
+
+
+def is_table_tokenizer(tokenizer) -> Optional[TextTable]:
+    """The TextTable whose ``.tokenize`` this is, or None."""
+    owner = getattr(tokenizer, "__self__", None)
+    return owner if isinstance(owner, TextTable) and getattr(tokenizer, "__func__", None) is TextTable.tokenize else None
+
+
+def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+    """The text store of thr_text_tokens -> (bytes uint8 with 16 zero bytes of padding behind the last text,
+    ptr int64 [n + 1]); text d is bytes[ptr[d] : ptr[d + 1]]."""
+    enc = [t.encode("utf-8", "surrogatepass") for t in texts]
+    ptr = np.zeros(len(enc) + 1, dtype=np.int64)
+    if enc:
+        np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc)), out=ptr[1:])
+    return np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8), ptr
+
+
+def vocab_capacity(n_terms: int) -> int:
+    """Slots of the device table: the smallest power of two that keeps the load at or below 1/2."""
+    cap = N.THR_VOCAB_MIN_SLOTS
+    while cap < 2 * n_terms:
+        cap *= 2
+    return cap
+
+
+def host_query_row(tokens: Sequence[str], ids: Dict[str, int]) -> Tuple[List[int], int, int]:
+    """_query_terms' table row from a token list -> (the first THR_BM25_MAX_TERMS distinct known ids in order
+    of first appearance, their number clamped at THR_BM25_MAX_TERMS + 1, THR_TEXT_UNKNOWN | THR_TEXT_TOO_MANY)."""
+    seen: Dict[int, None] = {}
+    flags = 0
+    for tok in tokens:
+        t = ids.get(tok)
+        if t is None:
+            flags |= N.THR_TEXT_UNKNOWN
+        else:
+            seen.setdefault(t, None)
+    if len(seen) > N.THR_BM25_MAX_TERMS:
+        flags |= N.THR_TEXT_TOO_MANY
+    return list(seen)[:N.THR_BM25_MAX_TERMS], min(len(seen), N.THR_BM25_MAX_TERMS + 1), flags
+
+
+class TextRows(NamedTuple):
+    doc: torch.Tensor            # int32 [T] on the device: the text of each token, ascending
+    term: torch.Tensor           # int32 [T] on the device: its term id, -1 for a token outside the vocabulary
+    unknown: List[str]           # the distinct unknown tokens (lowered) in order of first appearance
+    unknown_which: np.ndarray    # int64 [number of -1 rows]: per -1 row, in row order, its index in ``unknown``
+
+
+class TextSearch:
+    text: Optional[dict] = None                 # table, its device copy, the vocabulary's host and device halves
+    _ws_text: Optional[torch.Tensor] = None     # thr_text_tokens' workspace, grown on demand and kept
+    _ws_qterms: Optional[torch.Tensor] = None
+
+    # ------------------------------------------------------------ the vocabulary
+    def set_vocabulary(self, terms: Sequence[str], table: Optional[TextTable] = None) -> "TextSearch":
+        """The device vocabulary ``query_terms`` / ``text_rows`` look tokens up in (index set-up): terms[i] is
+        the string of term id i, as the tokenizer produces it (lowered).  ``table``: the analysis, default
+        ``TextTable.default()``.  Derived state: nothing of it is saved with the index.  Duplicates are
+        refused; after set_lexical the count must be the lexical index's vocabulary size."""
+        terms = list(terms)
+        ids = {t: i for i, t in enumerate(terms)}
+        if len(ids) != len(terms):
+            raise ValueError("set_vocabulary: the terms hold duplicates")
+        L = getattr(self, "lex", None)
+        if L is not None and max(len(terms), 1) != L["rowptr"].shape[0] - 1:
+            raise ValueError(f"set_vocabulary: {len(terms)} terms for the {L['rowptr'].shape[0] - 1} terms of the "
+                             "lexical index (set_lexical)")
+        table = table or TextTable.default()
+        self.text = dict(table=table, table_dev=self._t(table.entries.view(np.int32), torch.int32), ids=ids,
+                         term_bytes=torch.zeros(16, dtype=torch.uint8, device=self.device),
+                         term_ptr=torch.zeros(1, dtype=torch.int64, device=self.device), n_bytes=0, slots=None)
+        self._extend_vocabulary(terms)
+        return self
+
+    def grow_vocabulary(self, new_terms: Sequence[str]) -> "TextSearch":
+        """Append terms: they get the next ids (thr_vocab_insert; above 1/2 load the table is reallocated and
+        everything inserted again).  A term the vocabulary holds, or one repeated in the call, is refused."""
+        if self.text is None:
+            raise N.NativeError("grow_vocabulary: the index has no vocabulary (set_vocabulary)")
+        new_terms = list(new_terms)
+        ids = self.text["ids"]
+        if len(set(new_terms)) != len(new_terms) or any(t in ids for t in new_terms):
+            raise ValueError("grow_vocabulary: a term is in the vocabulary already or repeated")
+        v0 = len(ids)
+        self._extend_vocabulary(new_terms)
+        for i, t in enumerate(new_terms):
+            ids[t] = v0 + i
+        return self
+
+    def _extend_vocabulary(self, terms: Sequence[str]) -> None:
+        X = self.text
+        v0 = X["term_ptr"].shape[0] - 1
+        v1 = v0 + len(terms)
+        if terms:
+            enc = [t.encode("utf-8", "surrogatepass") for t in terms]
+            ptr = X["n_bytes"] + np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc)))
+            blob = np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8)
+            X["term_bytes"] = torch.cat([X["term_bytes"][:X["n_bytes"]], self._t(blob, torch.uint8)])
+            X["term_ptr"] = torch.cat([X["term_ptr"], self._t(ptr, torch.int64)])
+            X["n_bytes"] = int(ptr[-1])
+        cap = vocab_capacity(v1)
+        if X["slots"] is None or X["slots"].shape[0] != cap:
+            X["slots"] = torch.zeros((cap, 2), dtype=torch.int64, device=self.device)
+            v0 = 0
+        if v1 > v0:
+            N.vocab_insert(X["slots"], X["term_bytes"], X["term_ptr"], v0, v1 - v0)
+
+    # ------------------------------------------------------------ texts
+    def _text_tokens(self, texts: Sequence[str]) -> dict:
+        X = self.text
+        blob, ptr = pack_texts(texts)
+        n_bytes = int(ptr[-1])
+        cap = N.text_token_capacity(len(texts), n_bytes)
+        need = int(N.load().thr_text_tokens_workspace_bytes(len(texts), n_bytes, cap))
+        rows = N.text_tokens(self._t(blob, torch.uint8), self._t(ptr, torch.int64), n_bytes, X["table_dev"], X["slots"],
+                             X["term_bytes"], X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)))
+        rows["blob"], rows["ptr"] = blob, ptr
+        return rows
+
+    def query_terms(self, texts: Sequence[str], conjunctive: bool = False):
+        """The BM25 term table of a batch of query texts -> (terms int32 [nq, THR_BM25_MAX_TERMS] padded with
+        -1, flags int32 [nq]), both on the device: per query GpuIndexClient._query_terms' answer -- the distinct
+        known term ids in order of first appearance.  flags: THR_TEXT_EXCEPTIONAL (the row was computed on
+        the host through the table's tokenizer and patched in), THR_TEXT_UNKNOWN, THR_TEXT_TOO_MANY.
+        ``conjunctive``: a row with an unknown token or more than 32 distinct terms becomes all -1 (no chunk
+        can hold every term: _query_terms' None; thr_bm25_topk answers an all -1 row with no rows in both
+        forms).  The device path reads nothing back."""
+        if self.text is None:
+            raise N.NativeError("query_terms: the index has no vocabulary (set_vocabulary)")
+        texts = list(texts)
+        nq = len(texts)
+        if nq == 0:
+            return (torch.empty((0, N.THR_BM25_MAX_TERMS), dtype=torch.int32, device=self.device),
+                    torch.empty(0, dtype=torch.int32, device=self.device))
+        X = self.text
+        rows = self._text_tokens(texts)
+        need = int(N.load().thr_query_terms_workspace_bytes(nq))
+        terms, _, flags = N.query_terms(rows, workspace=self._scratch("_ws_qterms", max(need, 8)))
+        redo = X["table"].exceptional_among(texts)
+        if redo:
+            host = np.full((len(redo), N.THR_BM25_MAX_TERMS), -1, dtype=np.int32)
+            hflags = np.zeros(len(redo), dtype=np.int32)
+            for i, q in enumerate(redo):
+                row, _, f = host_query_row(X["table"].tokenize(texts[q]), X["ids"])
+                host[i, :len(row)] = row
+                hflags[i] = f | N.THR_TEXT_EXCEPTIONAL
+            at = self._t(np.asarray(redo, dtype=np.int64), torch.int64)
+            terms[at] = self._t(host, torch.int32)
+            flags[at] = self._t(hflags, torch.int32)
+        if conjunctive:
+            void = (flags & (N.THR_TEXT_UNKNOWN | N.THR_TEXT_TOO_MANY)) != 0
+            terms.masked_fill_(void[:, None], -1)
+        return terms, flags
+
+    def text_rows(self, texts: Sequence[str]) -> TextRows:
+        """The token rows of a batch of chunk texts -> TextRows(doc, term, unknown, unknown_which): what
+        ``append_rows(lex=(doc, term, None, n_vocab))`` takes once the -1 entries are numbered.  The
+        exceptional texts are tokenised on the host and their rows merged in, in document order.  One host
+        read-back (the counts and the unknown tokens' places)."""
+        if self.text is None:
+            raise N.NativeError("text_rows: the index has no vocabulary (set_vocabulary)")
+        texts = list(texts)
+        X = self.text
+        table, ids = X["table"], X["ids"]
+        redo = table.exceptional_among(texts)
+        keep = texts
+        if redo:
+            gone = set(redo)
+            kept_idx = [d for d in range(len(texts)) if d not in gone]
+            keep = [texts[d] for d in kept_idx]
+        unknown_seq: List[Tuple[int, str]] = []      # (text, token) of every unknown token, in row order
+        if keep:
+            rows = self._text_tokens(keep)
+            n_total, n_unknown = int(rows["n_total"].item()), int(rows["n_unknown"].item())
+            assert n_total <= rows["capacity"]
+            doc, term = rows["doc"][:n_total], rows["term"][:n_total]
+            off = rows["unknown_off"][:n_unknown].cpu().numpy()
+            ln = rows["unknown_len"][:n_unknown].cpu().numpy()
+            of_text = np.searchsorted(rows["ptr"], off, side="right") - 1
+            raw = rows["blob"].tobytes()
+            for d, o, l in zip(of_text.tolist(), off.tolist(), ln.tolist()):
+                piece = raw[o:o + l].decode("utf-8", "surrogatepass")
+                unknown_seq.append((kept_idx[d] if redo else d, table.restate(piece)[0]))
+            if redo:
+                doc = self._t(np.asarray(kept_idx, dtype=np.int32), torch.int32)[doc.long()]
+        else:
+            doc = torch.empty(0, dtype=torch.int32, device=self.device)
+            term = torch.empty(0, dtype=torch.int32, device=self.device)
+        if redo:
+            hd, ht = [], []
+            for d in redo:
+                for tok in table.tokenize(texts[d]):
+                    t = ids.get(tok, -1)
+                    hd.append(d)
+                    ht.append(t)
+                    if t < 0:
+                        unknown_seq.append((d, tok))
+            doc = torch.cat([doc, self._t(np.asarray(hd, dtype=np.int32), torch.int32)])
+            term = torch.cat([term, self._t(np.asarray(ht, dtype=np.int32), torch.int32)])
+            order = torch.sort(doc, stable=True).indices       # a text's rows are all from one side
+            doc, term = doc[order].contiguous(), term[order].contiguous()
+            unknown_seq.sort(key=lambda e: e[0])                # (stable: a text's tokens keep their order)
+        first: Dict[str, int] = {}
+        which = np.fromiter((first.setdefault(tok, len(first)) for _, tok in unknown_seq), dtype=np.int64,
+                            count=len(unknown_seq))
+        return TextRows(doc.contiguous(), term.contiguous(), list(first), which)
