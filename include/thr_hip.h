@@ -727,7 +727,59 @@ int thr_query_terms(const int32_t *tok_term, const int32_t *n_tokens, const int3
                     int32_t *out_terms /* [nq, THR_BM25_MAX_TERMS] */, int32_t *n_distinct,
                     int32_t *out_flags, void *workspace, size_t workspace_bytes, thr_stream_t stream);
 
-/* a5+a6  candidate merge + weighted Reciprocal Rank Fusion, bit-for-bit the
+/* a9  numbering the new terms of a batch: the ingest step behind thr_text_tokens.  The host restatement is
+ * the loop of GpuIndexClient.insert_children / TextSearch.text_rows / index_build.lexical_rows: a token the
+ * vocabulary does not hold gets the next id at its first sighting, in text order.
+ *
+ * thr_vocab_grow takes the batch (text_bytes, text_ptr, n_texts, n_bytes, table: as thr_text_tokens took
+ * them, the padding included), the per-text flags and the unknown list (unknown_off, unknown_len,
+ * n_unknown) exactly as that call left them, unknown_capacity (the entries the three list arrays hold),
+ * n_vocab (the first free id) and hash_mask (below).  All of it is device memory; *n_unknown is read on
+ * the device and clamped to 0 .. unknown_capacity, every offset and length is clamped against n_bytes and
+ * the end of its text: nothing outside [0, n_bytes + 4) of text_bytes is read, whatever the lists hold.
+ *   unknown_term int32 [unknown_capacity]: per occurrence in list order n_vocab + r, r the rank of its
+ *      (lowered) token among the distinct new tokens of the batch in order of first appearance in the list.
+ *      An occurrence whose text carries THR_TEXT_EXCEPTIONAL gets -1 and is not numbered (its bytes reach
+ *      no key).  Entries at or behind *n_unknown are not written;
+ *   new_bytes uint8 [new_bytes_capacity], new_ptr int64 [unknown_capacity + 1]: the new keys in id order,
+ *      LOWERED (each character through the table, re-encoded: the lowering can change the encoded length);
+ *      key r = [new_ptr[r], new_ptr[r + 1]), new_ptr[0] = 0; entries 0 .. n_new are written;
+ *   n_new int32 [1], n_new_bytes int64 [1]: the distinct new tokens and their bytes;
+ *   status int32 [1]: THR_VOCAB_GROW_COLLISION (two different tokens under one masked hash were merged:
+ *      the numbering is not to be used; the caller answers the batch on the host), THR_VOCAB_GROW_OVERFLOW
+ *      (new_bytes_capacity < n_new_bytes: n_new / n_new_bytes / new_ptr / unknown_term are right, no byte
+ *      at or behind the capacity is written; call again with the room);
+ *   tok_term (may be null; then n_total and token_capacity are not looked at): the tok_term of the
+ *      thr_text_tokens call with its n_total and token_capacity.  Its entries < 0 are, in row order, the
+ *      list: each is replaced by its unknown_term (an entry whose unknown_term is -1 stays -1).
+ * The vocabulary table is not touched: committing is thr_vocab_insert over the key store extended by
+ * new_bytes / new_ptr.
+ * hash_mask: the 64-bit FNV-1a hash of a lowered token (as above) is ANDed with it before the dedupe (a
+ * result of 0 replaced by 1).  Production passes all ones; a smaller mask makes collisions reachable for a
+ * test.  It concerns the scratch table only, never the keys.
+ * Claim (compare-and-swap on the hash word of a zeroed scratch table of 16-byte slots, the smallest power of
+ * two >= 2 * unknown_capacity of them, at least 16; the lowest occurrence of a slot kept by an integer
+ * max), verify against the slot's first occurrence, scan, emit, patch: commuting integer atomics and
+ * kernel boundaries only, no workgroup waits for another, nothing is read back, the same bits every run.
+ * Refused before any launch: n_texts / n_bytes outside thr_text_tokens' limits, unknown_capacity outside
+ * 1 .. THR_TEXT_MAX_BYTES, with tok_term a token_capacity outside 1 .. THR_TEXT_MAX_BYTES
+ * (THR_ERR_UNSUPPORTED; the size query returns 0); null pointers (tok_term alone may be null; with it
+ * n_total may not), n_vocab < 0, n_vocab + unknown_capacity > INT32_MAX, hash_mask 0, new_bytes_capacity
+ * < 0, text_bytes or workspace not 16-byte, text_ptr / unknown_off / new_ptr / n_new_bytes not 8-byte,
+ * table not 4-byte aligned (THR_ERR_INVALID); ``workspace`` < thr_vocab_grow_workspace_bytes()
+ * (THR_ERR_WORKSPACE). */
+#define THR_VOCAB_GROW_COLLISION 1
+#define THR_VOCAB_GROW_OVERFLOW 2
+size_t thr_vocab_grow_workspace_bytes(int64_t unknown_capacity);
+int thr_vocab_grow(const uint8_t *text_bytes, const int64_t *text_ptr, int64_t n_texts, int64_t n_bytes,
+                   const uint32_t *table /* [65536] */, const int32_t *flags, const int64_t *unknown_off,
+                   const int32_t *unknown_len, const int32_t *n_unknown, int64_t unknown_capacity,
+                   int64_t n_vocab, uint64_t hash_mask, int32_t *tok_term, const int32_t *n_total,
+                   int64_t token_capacity, int32_t *unknown_term, uint8_t *new_bytes,
+                   int64_t new_bytes_capacity, int64_t *new_ptr, int32_t *n_new, int64_t *n_new_bytes,
+                   int32_t *status, void *workspace, size_t workspace_bytes, thr_stream_t stream);
+
+/* a5+a6 candidate merge + weighted Reciprocal Rank Fusion, bit-for-bit the
  * float64 arithmetic and stable ordering of RAG2Retriever._retrieve_candidates
  * / _fuse_rrf, src/voice_agent/rag2/retrieval.py:203-271, 358-376.
  * Channel inputs are ranked id lists [nq, n_*] (negative id = end of list);

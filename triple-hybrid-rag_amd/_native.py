@@ -48,6 +48,8 @@ THR_TEXT_WORD, THR_TEXT_EXC = 1 << 16, 1 << 17   # bits of a TextTable entry abo
 # bits of the text flags: redo on the host; (thr_query_terms) an unknown token occurred; more than 32 distinct terms
 THR_TEXT_EXCEPTIONAL, THR_TEXT_UNKNOWN, THR_TEXT_TOO_MANY = 1, 2, 4
 THR_VOCAB_MIN_SLOTS, THR_VOCAB_MAX_SLOTS = 16, 1 << 30
+# bits of thr_vocab_grow's status word: two tokens under one masked hash; new_bytes_capacity below n_new_bytes
+THR_VOCAB_GROW_COLLISION, THR_VOCAB_GROW_OVERFLOW = 1, 2
 THR_CSR_MERGE_SLICE = 1024      # positions a workgroup of thr_csr_merge owns
 # bits of thr_csr_merge's status word: an input breaks its mode's ordering; the result exceeds out_capacity
 THR_CSR_MERGE_UNSORTED_A, THR_CSR_MERGE_UNSORTED_B, THR_CSR_MERGE_OVERFLOW = 1, 2, 4
@@ -131,6 +133,9 @@ _SIGNATURES = {
                                _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_query_terms_workspace_bytes": (_sz, [_i32]),
     "thr_query_terms": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "thr_vocab_grow_workspace_bytes": (_sz, [_i64]),
+    "thr_vocab_grow": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_uint64, _vp, _vp, _i64,
+                              _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "thr_rrf_fuse": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
                             _vp, _vp, _vp, _vp, _vp]),
     "thr_rrf_fuse_standalone": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _dbl, _dbl, _dbl, _i32, _i32,
@@ -1221,6 +1226,59 @@ def query_terms(rows: dict, workspace=None):
                                   rows["capacity"], nq, terms.data_ptr(), nd.data_ptr(), fl.data_ptr(), ws.data_ptr(),
                                   ws.numel(), _stream()), "thr_query_terms")
     return terms, nd, fl
+
+
+def vocab_grow(text_bytes, text_ptr, n_bytes: int, table, rows: dict, n_unknown: int, n_vocab: int,
+               new_bytes_capacity: Optional[int] = None, hash_mask: int = (1 << 64) - 1, term=None,
+               workspace=None):
+    """thr_vocab_grow over what ``text_tokens`` returned for the batch (``rows``: flags, unknown_off,
+    unknown_len, n_unknown) -> dict(unknown_term i32 [n_unknown], new_bytes u8 [new_bytes_capacity + 16],
+    new_ptr i64 [n_unknown + 1], n_new i32 [1], n_new_bytes i64 [1], status i32 [1]), all on the device.
+    ``n_unknown`` (>= 1) is the host's copy of rows["n_unknown"]: it sizes the list and the workspace.
+    ``term``: the first n_total rows of rows["term"] (a contiguous int32 tensor), patched in place.
+    new_bytes_capacity: room for the lowered keys (default 16 bytes per occurrence); THR_VOCAB_GROW_OVERFLOW
+    in status asks for n_new_bytes.  new_bytes carries 16 bytes of padding behind the capacity (the key store's).
+    No host read-back."""
+    pb = _dev(text_bytes, torch.uint8, "text_bytes", 1)
+    pp = _dev(text_ptr, torch.int64, "text_ptr", 1)
+    pt = _dev(table, torch.int32, "table", 1)
+    n = text_ptr.shape[0] - 1
+    pf = _dev(rows["flags"], torch.int32, "flags", 1)
+    po = _dev(rows["unknown_off"], torch.int64, "unknown_off", 1)
+    pl = _dev(rows["unknown_len"], torch.int32, "unknown_len", 1)
+    pn = _dev(rows["n_unknown"], torch.int32, "n_unknown", 1)
+    if table.shape[0] != 65536 or rows["flags"].shape[0] != n:
+        raise NativeError("vocab_grow: table is [65536], flags one per text")
+    if not 1 <= n_unknown <= min(rows["unknown_off"].shape[0], rows["unknown_len"].shape[0]):
+        raise NativeError(f"vocab_grow: n_unknown {n_unknown} outside 1 .. the unknown list's {rows['unknown_off'].shape[0]}")
+    if not 0 <= n_bytes <= THR_TEXT_MAX_BYTES or text_bytes.shape[0] < n_bytes + 4:
+        raise NativeError(f"vocab_grow: {n_bytes} bytes and 4 of padding behind them, the array holds {text_bytes.shape[0]}")
+    if not 0 < hash_mask < 1 << 64:
+        raise NativeError("vocab_grow: hash_mask is a non-zero 64-bit mask")
+    dev = text_bytes.device
+    cap_b = max(int(new_bytes_capacity if new_bytes_capacity is not None else 16 * n_unknown), 0)
+    need = int(load().thr_vocab_grow_workspace_bytes(n_unknown))
+    ws = workspace
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    ptk = pnt = None
+    tcap = 0
+    if term is not None:
+        ptk = _dev(term, torch.int32, "term", 1)
+        pnt = _dev(rows["n_total"], torch.int32, "n_total", 1)
+        tcap = term.shape[0]
+        if tcap < 1:
+            raise NativeError("vocab_grow: an empty term array cannot hold unknown tokens")
+    out = dict(unknown_term=torch.empty(n_unknown, dtype=torch.int32, device=dev),
+               new_bytes=torch.zeros(cap_b + 16, dtype=torch.uint8, device=dev),
+               new_ptr=torch.empty(n_unknown + 1, dtype=torch.int64, device=dev),
+               n_new=torch.empty(1, dtype=torch.int32, device=dev), n_new_bytes=torch.empty(1, dtype=torch.int64, device=dev),
+               status=torch.empty(1, dtype=torch.int32, device=dev), capacity=cap_b)
+    _check(load().thr_vocab_grow(pb, pp, n, n_bytes, pt, pf, po, pl, pn, n_unknown, n_vocab, hash_mask, ptk, pnt, tcap,
+                                 out["unknown_term"].data_ptr(), out["new_bytes"].data_ptr(), cap_b,
+                                 out["new_ptr"].data_ptr(), out["n_new"].data_ptr(), out["n_new_bytes"].data_ptr(),
+                                 out["status"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "thr_vocab_grow")
+    return out
 
 
 def graph_transpose_mentions(men_rowptr, men_chunk, men_conf, chunk_base: int, n_chunks: int):

@@ -422,7 +422,7 @@ class GpuIndexClient:
                  token_embedder: Any = None, lexical_and: bool = False,
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
                  collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
-                 tokenizer: Any = None):
+                 tokenizer: Any = None, number_on_device: bool = False):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's
         ``plainto_tsquery`` does (rag2_schema.sql:365); default is BM25's OR form, the
         north star's and the oracle's.
@@ -444,7 +444,15 @@ class GpuIndexClient:
         device_text: query and chunk text become term ids on the device (GpuIndex.set_vocabulary from
         ``store.vocab`` -- derived state, rebuilt here, never saved): ``_lexical`` and ``insert_children``
         take that route and ``query_terms_batch`` serves batches.  Needs ``tokenize`` or a TextTable's
-        ``.tokenize`` as the tokenizer; any other is refused by name."""
+        ``.tokenize`` as the tokenizer; any other is refused by name.
+        number_on_device: (with device_text) ``insert_children`` also numbers the batch's new terms on the
+        device (GpuIndex.number_text_rows / commit_vocabulary): the unknown tokens are not decoded one
+        occurrence at a time, the new keys stay on the device, and the store's vocabulary gets one string per
+        distinct new term.  The ids are the host loop's.  Without device_text it is refused by name."""
+        if number_on_device and not device_text:
+            raise ValueError("number_on_device=True needs device_text=True: the terms are numbered behind "
+                             "the device tokenizer")
+        self.number_on_device = bool(number_on_device)
         self.lexical_and = bool(lexical_and)
         self.image_index = image_index
         self.image_rows = None if image_rows is None else [int(r) for r in image_rows]
@@ -848,8 +856,14 @@ class GpuIndexClient:
         else:
             parts.update(docs=None, n_rows=m)
         vocab = st.vocab
-        text_rows = None
-        if getattr(idx, "lex", None) is not None and self.device_text:
+        text_rows = numbered = None
+        if getattr(idx, "lex", None) is not None and self.device_text and self.number_on_device:
+            # tokenised AND numbered on the device: the rows come with their final ids, the new keys stay
+            # there until the index has taken the rows (commit_vocabulary below)
+            self._sync_vocabulary()
+            numbered = idx.number_text_rows([r.get("text", "") for r in rows])
+            parts["lex"] = (numbered.doc, numbered.term, None, max(len(vocab) + numbered.pending.n_new, 1))
+        elif getattr(idx, "lex", None) is not None and self.device_text:
             # the same on the device: the unknown tokens come back as strings and are numbered here, in
             # order of first appearance across the batch, exactly as the loop below numbers them
             self._sync_vocabulary()
@@ -903,7 +917,11 @@ class GpuIndexClient:
             parts["mentions"] = (np.asarray(me, dtype=np.int64), np.asarray(mc, dtype=np.int64),
                                  np.asarray(mw, dtype=np.float32))
         idx.append_rows(**parts)
-        if text_rows is not None:       # index before store: the device vocabulary, then the rows, then the terms
+        if numbered is not None:        # index, device vocabulary, store rows, store vocabulary: in that order
+            idx.commit_vocabulary(numbered.pending)
+            st.append(rows, tokenizer=None)
+            st.vocab.update((tok, numbered.n_before + i) for i, tok in enumerate(numbered.pending.terms))
+        elif text_rows is not None:       # index before store: the device vocabulary, then the rows, then the terms
             if text_rows.unknown:
                 idx.grow_vocabulary(text_rows.unknown)
             st.append(rows, tokenizer=None)

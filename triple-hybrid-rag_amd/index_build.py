@@ -122,6 +122,51 @@ def lexical_rows(texts: Sequence[str], tokenizer: Callable[[str], List[str]] = t
     return vocab, doc, term
 
 
+def lexical_rows_device(texts: Sequence[str], tokenizer: Callable[[str], List[str]] = tokenize,
+                        batch_bytes: int = 64 << 20):
+    """``lexical_rows`` for a fresh vocabulary with the text itself on the device -> (vocab, doc int32
+    [n_tokens], term int32 [n_tokens]), the two arrays DEVICE tensors.  The texts go through
+    ``GpuIndex.number_text_rows`` / ``commit_vocabulary`` in batches of at most ``batch_bytes`` of UTF-8 (a
+    longer text is a batch of its own), from an empty vocabulary: every token is new at its first sighting
+    and gets the next id there, the numbering of ``lexical_rows`` / ``build_lexical``.  A batch with an
+    exceptional text is answered on the host (number_text_rows says when).  The vocabulary's strings are
+    decoded once, from the final key store."""
+    import torch
+    from .index import GpuIndex
+    from .index_text import TextTable, decode_keys, is_table_tokenizer
+    table = TextTable.default() if tokenizer is tokenize else is_table_tokenizer(tokenizer)
+    if table is None:
+        name = getattr(tokenizer, "__qualname__", None) or repr(tokenizer)
+        raise ValueError(f"from_rows(device=\"text\") needs backend.tokenize or a TextTable's .tokenize as the "
+                         f"tokenizer, not {name}: the device restates a table, not a function")
+    if batch_bytes < 1:
+        raise ValueError("from_rows(device=\"text\"): batch_bytes is at least 1")
+    idx = GpuIndex().set_vocabulary([], table)
+    enc = [t.encode("utf-8", "surrogatepass") for t in texts]
+    docs, terms = [], []
+    a = 0
+    while a < len(enc):
+        b, size = a + 1, len(enc[a])
+        while b < len(enc) and size + len(enc[b]) <= batch_bytes:
+            size += len(enc[b])
+            b += 1
+        ptr = np.zeros(b - a + 1, dtype=np.int64)
+        np.cumsum(np.fromiter(map(len, enc[a:b]), dtype=np.int64, count=b - a), out=ptr[1:])
+        packed = (np.frombuffer(b"".join(enc[a:b]) + bytes(16), dtype=np.uint8), ptr)
+        rows = idx.number_text_rows(texts[a:b], packed=packed)
+        idx.commit_vocabulary(rows.pending, mirror=False)
+        docs.append(rows.doc + a if a else rows.doc)
+        terms.append(rows.term)
+        a = b
+    X = idx.text
+    n_vocab = X["term_ptr"].shape[0] - 1
+    vocab = {t: i for i, t in enumerate(decode_keys(X["term_bytes"][:X["n_bytes"]], X["term_ptr"]))} if n_vocab else {}
+    if len(vocab) != n_vocab:
+        raise RuntimeError("lexical_rows_device: the key store holds a key twice")
+    empty = torch.empty(0, dtype=torch.int32, device=idx.device)
+    return vocab, (torch.cat(docs) if docs else empty), (torch.cat(terms) if terms else empty.clone())
+
+
 def build_lexical(texts: Sequence[str], tokenizer: Callable[[str], List[str]] = tokenize,
                   vocab: Optional[Dict[str, int]] = None, n_docs_global: Optional[int] = None,
                   df_global: Optional[np.ndarray] = None, sum_dl_global: Optional[float] = None):
@@ -201,11 +246,14 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
               entity_rows: Sequence[Dict[str, Any]] = (), relation_rows: Sequence[Dict[str, Any]] = (),
               mention_rows: Sequence[Dict[str, Any]] = (), embedding_key: str = "embedding_1024",
               tokenizer: Callable[[str], List[str]] = tokenize, doc_base: int = 0,
-              device: bool = False) -> HostIndex:
+              device: Any = False, batch_bytes: int = 64 << 20) -> HostIndex:
     """Reference table rows -> HostIndex (+ CorpusStore).  Rows without an embedding keep a
     zero vector, i.e. are excluded from the dense channel (``embedding_1024 IS NOT NULL``).
     device=True builds the inverted index on the GPU (``lexical_rows`` + thr_lexical_build) and
-    brings the arrays back for ``save``; the result equals the host route's."""
+    brings the arrays back for ``save``; the result equals the host route's.
+    device="text" takes the chunk TEXTS to the device as well (``lexical_rows_device``): tokens, case
+    folding and the numbering of the vocabulary, in batches of at most ``batch_bytes`` of UTF-8; the
+    tokenizer must be ``backend.tokenize`` or a TextTable's ``.tokenize``, any other is refused by name."""
     n = len(child_rows)
     dim = next((len(r[embedding_key]) for r in child_rows if r.get(embedding_key) is not None), 0)
     docs = np.zeros((n, dim), dtype=np.float32)
@@ -213,7 +261,17 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
         if r.get(embedding_key) is not None:
             docs[i] = np.asarray(r[embedding_key], dtype=np.float32)
     texts = [r.get("text", "") for r in child_rows]
-    if device:
+    if isinstance(device, str) and device != "text":
+        raise ValueError(f"from_rows: device is False, True or \"text\", not {device!r}")
+    if device == "text":
+        from . import _native as N
+        vocab, d_dev, t_dev = lexical_rows_device(texts, tokenizer, batch_bytes)
+        rowptr, pd, ptf, dl, df = (a.cpu().numpy() for a in N.lexical_build(d_dev, t_dev, None, n, max(len(vocab), 1)))
+        rowptr, df = rowptr[:len(vocab) + 1], df[:len(vocab)]      # (no token at all: build_lexical's empty CSR)
+        dfh = df.astype(np.float64)
+        idf = np.log(1.0 + (float(n) - dfh + 0.5) / (dfh + 0.5))
+        avgdl = float(dl.astype(np.float64).sum()) / max(n, 1) or 1.0
+    elif device:
         from . import _native as N
         import torch
         vocab, d_tok, t_tok = lexical_rows(texts, tokenizer)

@@ -20,6 +20,12 @@ with the table's host tokenizer, so the answer is always the host's.
 
 What stays on the host: the UTF-8 encoding (("utf-8", "surrogatepass"), as index_entities), the exceptional
 texts, and the strings of unknown tokens (an ingest numbers them: GpuIndexClient.insert_children).
+
+``number_text_rows`` / ``commit_vocabulary`` number the new terms of a batch ON THE DEVICE instead
+(thr_vocab_grow: the next id at a token's first sighting, the numbering of that host loop): the rows come back
+without a -1, the new keys stay on the device as a ``PendingVocabulary`` until the commit appends them to the key
+store and inserts them, and their strings are decoded once per distinct term when the store's vocabulary wants
+them.  A batch with an exceptional text, or two new tokens under one hash, takes the host route above.
 """
 from __future__ import annotations
 
@@ -174,10 +180,46 @@ class TextRows(NamedTuple):
     unknown_which: np.ndarray    # int64 [number of -1 rows]: per -1 row, in row order, its index in ``unknown``
 
 
+class PendingVocabulary:
+    """The new terms of a numbered batch, not yet in the vocabulary (``commit_vocabulary`` puts them there):
+    ids ``n_before .. n_before + n_new - 1`` in order of first appearance.  From the device route the keys
+    are device memory -- ``key_bytes`` uint8 (lowered UTF-8), ``key_ptr`` int64 [n_new + 1] relative to 0 --
+    and ``terms`` decodes their strings on first use from ONE read-back of the blob: one decode per distinct
+    new term.  From the host route (a batch with an exceptional text, a hash collision) the strings are
+    there and the device halves are None."""
+
+    def __init__(self, n_before: int, n_new: int, n_key_bytes: int = 0, key_bytes: Optional[torch.Tensor] = None,
+                 key_ptr: Optional[torch.Tensor] = None, terms: Optional[List[str]] = None):
+        self.n_before, self.n_new, self.n_key_bytes = int(n_before), int(n_new), int(n_key_bytes)
+        self.key_bytes, self.key_ptr = key_bytes, key_ptr
+        self._terms = terms if terms is not None else ([] if n_new == 0 else None)
+
+    @property
+    def terms(self) -> List[str]:
+        if self._terms is None:
+            self._terms = decode_keys(self.key_bytes[:self.n_key_bytes], self.key_ptr[:self.n_new + 1])
+        return self._terms
+
+
+def decode_keys(key_bytes: torch.Tensor, key_ptr: torch.Tensor) -> List[str]:
+    """A key store as strings: one read-back of the blob, one decode per key."""
+    blob = key_bytes.cpu().numpy().tobytes()
+    ptr = key_ptr.cpu().tolist()
+    return [blob[a:b].decode("utf-8", "surrogatepass") for a, b in zip(ptr, ptr[1:])]
+
+
+class NumberedRows(NamedTuple):
+    doc: torch.Tensor            # int32 [T] on the device: the text of each token, ascending
+    term: torch.Tensor           # int32 [T] on the device: its term id; a new term has its id already, no -1
+    n_before: int                # the vocabulary's size the numbering started from
+    pending: PendingVocabulary   # the new terms, for commit_vocabulary
+
+
 class TextSearch:
     text: Optional[dict] = None                 # table, its device copy, the vocabulary's host and device halves
     _ws_text: Optional[torch.Tensor] = None     # thr_text_tokens' workspace, grown on demand and kept
     _ws_qterms: Optional[torch.Tensor] = None
+    _ws_grow: Optional[torch.Tensor] = None     # thr_vocab_grow's
 
     # ------------------------------------------------------------ the vocabulary
     def set_vocabulary(self, terms: Sequence[str], table: Optional[TextTable] = None) -> "TextSearch":
@@ -206,7 +248,7 @@ class TextSearch:
         if self.text is None:
             raise N.NativeError("grow_vocabulary: the index has no vocabulary (set_vocabulary)")
         new_terms = list(new_terms)
-        ids = self.text["ids"]
+        ids = self._mirror()
         if len(set(new_terms)) != len(new_terms) or any(t in ids for t in new_terms):
             raise ValueError("grow_vocabulary: a term is in the vocabulary already or repeated")
         v0 = len(ids)
@@ -226,6 +268,11 @@ class TextSearch:
             X["term_bytes"] = torch.cat([X["term_bytes"][:X["n_bytes"]], self._t(blob, torch.uint8)])
             X["term_ptr"] = torch.cat([X["term_ptr"], self._t(ptr, torch.int64)])
             X["n_bytes"] = int(ptr[-1])
+        self._insert_keys(v0, v1)
+
+    def _insert_keys(self, v0: int, v1: int) -> None:
+        """Keys v0 .. v1 - 1 of the key store into the table; above 1/2 load a new table and every key again."""
+        X = self.text
         cap = vocab_capacity(v1)
         if X["slots"] is None or X["slots"].shape[0] != cap:
             X["slots"] = torch.zeros((cap, 2), dtype=torch.int64, device=self.device)
@@ -233,16 +280,113 @@ class TextSearch:
         if v1 > v0:
             N.vocab_insert(X["slots"], X["term_bytes"], X["term_ptr"], v0, v1 - v0)
 
-    # ------------------------------------------------------------ texts
-    def _text_tokens(self, texts: Sequence[str]) -> dict:
+    def _mirror(self) -> Dict[str, int]:
+        """The host mirror ``text["ids"]``, with the terms of every commit that left its strings on the device
+        (``commit_vocabulary(mirror=False)``) decoded and added: called before any host-side lookup."""
         X = self.text
-        blob, ptr = pack_texts(texts)
+        for pending in X.pop("unmirrored", ()):
+            ids = X["ids"]
+            for i, t in enumerate(pending.terms):
+                ids[t] = pending.n_before + i
+        return X["ids"]
+
+    # ------------------------------------------------------------ numbering new terms on the device
+    def number_text_rows(self, texts: Sequence[str], hash_mask: Optional[int] = None, packed=None) -> NumberedRows:
+        """The token rows of a batch of chunk texts with the new terms NUMBERED on the device ->
+        NumberedRows(doc, term, n_before, pending): ``append_rows(lex=(doc, term, None, n_before +
+        pending.n_new))`` takes them as they are, ``commit_vocabulary(pending)`` then puts the new keys into
+        the vocabulary.  The numbering is ``text_rows``' and the host loop's: the next id at a token's first
+        sighting, in text order (thr_text_tokens, then thr_vocab_grow).  Until the commit nothing of the
+        vocabulary changes.  Two read-backs: the counts, then n_new / n_new_bytes / status.
+        A batch that holds an exceptional text, or whose call comes back with THR_VOCAB_GROW_COLLISION, is
+        answered through ``text_rows`` and the host numbering: the same object with the same values.
+        THR_VOCAB_GROW_OVERFLOW is a second call with the room it reported.
+        ``hash_mask`` is for tests (thr_hip.h); ``packed``: pack_texts(texts), when the caller has it."""
+        if self.text is None:
+            raise N.NativeError("number_text_rows: the index has no vocabulary (set_vocabulary)")
+        texts = list(texts)
+        X = self.text
+        n_before = X["term_ptr"].shape[0] - 1
+        if not texts:
+            empty = torch.empty(0, dtype=torch.int32, device=self.device)
+            return NumberedRows(empty, empty.clone(), n_before, PendingVocabulary(n_before, 0))
+        if X["table"].exceptional_among(texts):
+            return self._number_on_host(texts, n_before)
+        rows = self._text_tokens(texts, packed)
+        n_total, n_unknown = torch.cat([rows["n_total"], rows["n_unknown"]]).tolist()
+        assert n_total <= rows["capacity"]
+        doc, term = rows["doc"][:n_total], rows["term"][:n_total]
+        if n_unknown == 0:
+            return NumberedRows(doc, term, n_before, PendingVocabulary(n_before, 0))
+        n_bytes = int(rows["ptr"][-1])
+        room = min(3 * n_bytes // 2 + 16, 16 * n_unknown)
+        mask = (1 << 64) - 1 if hash_mask is None else int(hash_mask)
+        need = int(N.load().thr_vocab_grow_workspace_bytes(n_unknown))
+        patch = term
+        while True:
+            out = N.vocab_grow(rows["bytes_dev"], rows["ptr_dev"], n_bytes, X["table_dev"], rows, n_unknown, n_before,
+                               new_bytes_capacity=room, hash_mask=mask, term=patch,
+                               workspace=self._scratch("_ws_grow", max(need, 16)))
+            n_new, n_new_bytes, status = torch.cat([out["n_new"].long(), out["n_new_bytes"], out["status"].long()]).tolist()
+            if status & N.THR_VOCAB_GROW_COLLISION:
+                return self._number_on_host(texts, n_before)
+            if not status & N.THR_VOCAB_GROW_OVERFLOW:
+                break
+            room, patch = n_new_bytes, None     # (the rows are patched already: the ids do not depend on the room)
+        return NumberedRows(doc, term, n_before,
+                            PendingVocabulary(n_before, n_new, n_new_bytes, out["new_bytes"], out["new_ptr"]))
+
+    def _number_on_host(self, texts: Sequence[str], n_before: int) -> NumberedRows:
+        rows = self.text_rows(texts)
+        term = rows.term
+        if len(rows.unknown_which):
+            term = term.clone()
+            term[term < 0] = self._t((n_before + rows.unknown_which).astype(np.int32), torch.int32)
+        return NumberedRows(rows.doc, term, n_before,
+                            PendingVocabulary(n_before, len(rows.unknown), terms=list(rows.unknown)))
+
+    def commit_vocabulary(self, pending: PendingVocabulary, mirror: bool = True) -> "TextSearch":
+        """Put the new terms of a ``number_text_rows`` call into the vocabulary: the key bytes and pointers
+        are appended to the key store ON THE DEVICE (no re-encode, no upload), then thr_vocab_insert (above
+        1/2 load the table is reallocated and everything inserted again, as grow_vocabulary does).  A pending
+        set that was numbered from another vocabulary size is refused.  ``mirror=False`` leaves the host
+        mirror ``text["ids"]`` behind until a host-side lookup needs it (a bulk build: the strings are then
+        decoded once from the final key store)."""
+        if self.text is None:
+            raise N.NativeError("commit_vocabulary: the index has no vocabulary (set_vocabulary)")
+        X = self.text
+        v0 = X["term_ptr"].shape[0] - 1
+        if pending.n_before != v0:
+            raise ValueError(f"commit_vocabulary: the terms were numbered from {pending.n_before}, the vocabulary "
+                             f"holds {v0} (another commit came in between)")
+        if pending.n_new == 0:
+            return self
+        if pending.key_bytes is None:       # numbered on the host: the strings are encoded and uploaded
+            self._extend_vocabulary(pending.terms)
+        else:
+            nb = X["n_bytes"]
+            X["term_bytes"] = torch.cat([X["term_bytes"][:nb], pending.key_bytes[:pending.n_key_bytes],
+                                         torch.zeros(16, dtype=torch.uint8, device=self.device)])
+            X["term_ptr"] = torch.cat([X["term_ptr"], pending.key_ptr[1:pending.n_new + 1] + nb])
+            X["n_bytes"] = nb + pending.n_key_bytes
+            self._insert_keys(v0, v0 + pending.n_new)
+        X.setdefault("unmirrored", []).append(pending)
+        if mirror:
+            self._mirror()
+        return self
+
+    # ------------------------------------------------------------ texts
+    def _text_tokens(self, texts: Sequence[str], packed=None) -> dict:
+        X = self.text
+        blob, ptr = packed if packed is not None else pack_texts(texts)
         n_bytes = int(ptr[-1])
         cap = N.text_token_capacity(len(texts), n_bytes)
         need = int(N.load().thr_text_tokens_workspace_bytes(len(texts), n_bytes, cap))
-        rows = N.text_tokens(self._t(blob, torch.uint8), self._t(ptr, torch.int64), n_bytes, X["table_dev"], X["slots"],
+        bytes_dev, ptr_dev = self._t(blob, torch.uint8), self._t(ptr, torch.int64)
+        rows = N.text_tokens(bytes_dev, ptr_dev, n_bytes, X["table_dev"], X["slots"],
                              X["term_bytes"], X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)))
         rows["blob"], rows["ptr"] = blob, ptr
+        rows["bytes_dev"], rows["ptr_dev"] = bytes_dev, ptr_dev      # (thr_vocab_grow reads the batch again)
         return rows
 
     def query_terms(self, texts: Sequence[str], conjunctive: bool = False):
@@ -269,7 +413,7 @@ class TextSearch:
             host = np.full((len(redo), N.THR_BM25_MAX_TERMS), -1, dtype=np.int32)
             hflags = np.zeros(len(redo), dtype=np.int32)
             for i, q in enumerate(redo):
-                row, _, f = host_query_row(X["table"].tokenize(texts[q]), X["ids"])
+                row, _, f = host_query_row(X["table"].tokenize(texts[q]), self._mirror())
                 host[i, :len(row)] = row
                 hflags[i] = f | N.THR_TEXT_EXCEPTIONAL
             at = self._t(np.asarray(redo, dtype=np.int64), torch.int64)
@@ -289,7 +433,7 @@ class TextSearch:
             raise N.NativeError("text_rows: the index has no vocabulary (set_vocabulary)")
         texts = list(texts)
         X = self.text
-        table, ids = X["table"], X["ids"]
+        table, ids = X["table"], self._mirror()
         redo = table.exceptional_among(texts)
         keep = texts
         if redo:
