@@ -140,10 +140,8 @@ def main():
     v_before = len(c.store.vocab)
 
     def step_host():
-        R = idx.text_rows(texts)
-        t = R.term.clone()
-        t[t < 0] = torch.from_numpy((v_before + R.unknown_which).astype(np.int32)).to(idx.device)
-        return R.doc, t, R.unknown
+        R = idx.number_text_rows(texts, on_device=False)
+        return R.doc, R.term, R.pending.terms
 
     def step_device():
         R = idx.number_text_rows(texts)

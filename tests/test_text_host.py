@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import text_cases as TC  # noqa: E402
+import vocab_grow_cases as VG  # noqa: E402
 
 import triple_hybrid_rag_amd as T  # noqa: E402
 from triple_hybrid_rag_amd import backend, index_text as IT  # noqa: E402
@@ -251,6 +252,8 @@ class StubIndex(IT.TextSearch):
 
     def _extend_vocabulary(self, terms):
         self.log.append(("vocabulary", list(terms)))
+        # (the key store's pointers stay in step: commit_vocabulary reads the vocabulary's size off them)
+        self.text["term_ptr"] = self.torch.zeros(self.text["term_ptr"].shape[0] + len(terms), dtype=self.torch.int64)
 
     def _text_tokens(self, texts):
         X = self.text
@@ -340,3 +343,49 @@ def test_device_text_refuses_a_custom_tokenizer_by_name():
         StubIndex(3).set_vocabulary(["a", "b", "a"])
     with pytest.raises(ValueError, match="lexical index"):
         StubIndex(3).set_vocabulary(["a", "b"])
+
+
+def test_the_host_route_tokenises_each_text_once_and_hands_over_what_the_device_text_twin_does():
+    calls = []
+
+    def counting(text):
+        calls.append(text)
+        return backend.tokenize(text)
+    vocab = ["w1", "w2", "w3"]
+    host, twin = _client(vocab, tokenizer=counting), _client(vocab, device_text=True)
+    assert host.insert_children(_rows(BATCH)) == twin.insert_children(_rows(BATCH))
+    assert calls == BATCH                                        # once per row: not again for the store
+    assert list(host.store.vocab.items()) == list(twin.store.vocab.items()) and len(host.store.vocab) == 10
+    assert host.store.texts == twin.store.texts == BATCH
+    assert [k for k, _ in host.index.log] == ["append_rows"] and host.index.text is None
+    a, b = host.index.log[0][1]["lex"], twin.index.log[1][1]["lex"]
+    assert np.asarray(a[0]).tolist() == b[0].tolist() and np.asarray(a[1]).tolist() == b[1].tolist()
+    assert np.asarray(a[0]).dtype == np.asarray(a[1]).dtype == np.int32 and a[2:] == b[2:] == (None, 10)
+
+
+def test_tokenizer_table_maps_tokenize_and_a_tables_tokenize_and_refuses_the_rest_by_name():
+    fold = TextTable.from_char_map(fold_accents)
+    assert IT.tokenizer_table(backend.tokenize, "x") is TextTable.default()
+    assert IT.tokenizer_table(fold.tokenize, "x") is fold
+
+    def plain_function(text):
+        return text.split()
+    for prefix in ("device_text=True", "from_rows(device=\"text\")"):
+        for fn, name in ((fold.restate, "TextTable.restate"), (plain_function, "plain_function")):
+            with pytest.raises(ValueError) as err:
+                IT.tokenizer_table(fn, prefix)
+            assert str(err.value).startswith(prefix + " needs ") and name in str(err.value)
+
+
+def test_numbering_on_the_host_does_not_depend_on_hash_mask_or_packed():
+    """Over the stub this shows the two arguments inert on the host route; that a forced collision on the
+    device falls back to these values is tests/test_gpu_vocab_grow.py's."""
+    vocab = ["w1", "w2", "w3"]
+    idx = StubIndex(3).set_vocabulary(vocab)
+    ids = {t: i for i, t in enumerate(vocab)}
+    d_tok, t_tok, grown = VG.expect_numbered(BATCH, ids)
+    for kw in ({}, {"hash_mask": 0x7}, {"packed": IT.pack_texts(BATCH)}, {"hash_mask": 0x7, "packed": IT.pack_texts(BATCH)}):
+        R = idx.number_text_rows(BATCH, on_device=False, **kw)
+        assert R.doc.tolist() == d_tok.tolist() and R.term.tolist() == t_tok.tolist(), kw
+        assert R.pending.terms == grown and R.n_before == 3 and R.pending.key_bytes is None, kw
+    assert idx.text["ids"] == ids and idx.log == [("vocabulary", vocab)]       # nothing was committed

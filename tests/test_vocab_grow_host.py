@@ -226,6 +226,25 @@ def _rows(texts, first=0):
 BATCH = ["novo termo w1 novo", "", "w2 İstanbul primeiro termo", "outro Novo W3 primeiro", " ,, ", "İstanbul de novo"]
 
 
+NUMBERED = [("the_batch", BATCH, ["w1", "w2", "w3"]), ("the_empty_batch", [], ["w1"]),
+            ("every_token_known", ["w1 W2", "", "w2 w1 W1"], ["w1", "w2"]),
+            ("every_token_new", ["novo termo Novo", " ,, ", "outro termo novo"], [])]
+
+
+@pytest.mark.parametrize("name,texts,vocab", NUMBERED, ids=[n for n, _, _ in NUMBERED])
+def test_number_tokens_is_the_restatement(name, texts, vocab):
+    ids = ids_of(vocab)
+    doc, term, new_terms = IT.number_tokens([backend.tokenize(t) for t in texts], ids)
+    d_tok, t_tok, grown = VG.expect_numbered(texts, ids_of(vocab))
+    assert doc.dtype == term.dtype == np.int32 and doc.shape == term.shape == d_tok.shape
+    assert np.array_equal(doc, d_tok) and np.array_equal(term, t_tok) and new_terms == grown
+    assert ids == ids_of(vocab)                                   # the vocabulary is only read
+    if name == "every_token_known":
+        assert new_terms == [] and len(term) == 5
+    if name == "every_token_new":
+        assert new_terms == ["novo", "termo", "outro"] and term.tolist() == [0, 1, 0, 2, 1, 0]
+
+
 def test_number_on_device_takes_number_append_commit_store_in_that_order():
     vocab = ["w1", "w2", "w3"]
     client = _client(vocab, device_text=True, number_on_device=True)

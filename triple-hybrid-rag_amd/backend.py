@@ -54,7 +54,7 @@ import torch
 from . import _native as N
 from .index import GpuIndex
 from .index_scope import In
-from .index_text import TextTable, is_table_tokenizer
+from .index_text import NumberedRows, PendingVocabulary, TextTable, host_query_row, number_tokens, tokenizer_table
 
 _TOKEN = re.compile(r"[\w]+", re.UNICODE)
 
@@ -198,10 +198,10 @@ class CorpusStore:
                 self.org_ids.append(r.get("org_id"))
             self.content_hashes.append(r.get("content_hash"))
             self._row_of[r["id"]] = n0 + i
-            if tokenizer is not None:
-                for tok in tokenizer(r.get("text", "")):
-                    if tok not in self.vocab:
-                        self.vocab[tok] = len(self.vocab)
+        if tokenizer is not None:
+            v0 = len(self.vocab)
+            new_terms = number_tokens((tokenizer(r.get("text", "")) for r in rows), self.vocab)[2]
+            self.vocab.update((tok, v0 + i) for i, tok in enumerate(new_terms))
         self._hashes.update(h for h in hashes if h is not None)
         return range(n0, n0 + len(rows))
 
@@ -504,14 +504,7 @@ class GpuIndexClient:
     # -------------------------------------------------------------- text on the device
     def _text_table(self) -> TextTable:
         """The analysis table of this client's tokenizer; a tokenizer that is no table is refused."""
-        if self.tokenizer is tokenize:
-            return TextTable.default()
-        table = is_table_tokenizer(self.tokenizer)
-        if table is None:
-            name = getattr(self.tokenizer, "__qualname__", None) or repr(self.tokenizer)
-            raise ValueError(f"device_text=True needs backend.tokenize or a TextTable's .tokenize as the tokenizer, "
-                             f"not {name}: the device restates a table, not a function")
-        return table
+        return tokenizer_table(self.tokenizer, "device_text=True")
 
     def _sync_vocabulary(self) -> None:
         """The index's device vocabulary is store.vocab's (built on first use, rebuilt when another writer
@@ -743,22 +736,15 @@ class GpuIndexClient:
     def _query_terms(self, query: str) -> Optional[List[int]]:
         """The distinct term ids of the query in order of first appearance (at most
         THR_BM25_MAX_TERMS), or None when nothing can match."""
-        terms: List[int] = []
-        unknown = False
-        for tok in tokenize(query):
-            t = self.store.vocab.get(tok)
-            if t is None:
-                unknown = True
-            elif t not in terms:
-                terms.append(t)
+        terms, _, flags = host_query_row(tokenize(query), self.store.vocab)
         if not terms or getattr(self.index, "lex", True) is None:
             return None
         # AND semantics (plainto_tsquery, rag2_schema.sql:365): a token no chunk holds, or a term
         # the kernel's term list would have to drop, makes the conjunction unsatisfiable -- the
         # SQL returns no rows, so does this (the OR form just ignores what it does not know)
-        if self.lexical_and and (unknown or len(terms) > N.THR_BM25_MAX_TERMS):
+        if self.lexical_and and flags & (N.THR_TEXT_UNKNOWN | N.THR_TEXT_TOO_MANY):
             return None
-        return terms[: N.THR_BM25_MAX_TERMS]
+        return terms
 
     def _lexical(self, query: str, limit: int, collection, defer: bool = False, org=None):
         """defer=True (``_defer`` in the RPC's params; RAG2Retriever sets it): the kernels are
@@ -822,6 +808,20 @@ class GpuIndexClient:
             raise ValueError("insert refused: the rows belong to another org_id than this index "
                              "(data isolation, as rpc() answers another tenant with no rows)")
 
+    def _number_texts(self, texts: Sequence[str]) -> NumberedRows:
+        """The token rows of a batch of chunk texts, new terms numbered, on the route the client was made
+        with: ``self.tokenizer`` and ``number_tokens`` (host arrays, the new terms as strings), or under
+        device_text the index's ``number_text_rows`` (device tensors; with number_on_device the new keys
+        stay there).  Nothing is committed: neither vocabulary has changed when this returns."""
+        if self.device_text:
+            self._sync_vocabulary()
+            if self.number_on_device:
+                return self.index.number_text_rows(texts)
+            return self.index.number_text_rows(texts, on_device=False)
+        n_before = len(self.store.vocab)
+        doc, term, new_terms = number_tokens(map(self.tokenizer, texts), self.store.vocab)
+        return NumberedRows(doc, term, n_before, PendingVocabulary(n_before, len(new_terms), terms=new_terms))
+
     def insert_children(self, rows: Sequence[Dict[str, Any]], embedding_key: str = "embedding_1024"):
         """``table("rag_child_chunks").insert(rows)``: one append of len(rows) chunks to the store
         and to the live index -> [{"id": ...}, ...].  A row is stored as ``index_build.from_rows``
@@ -855,41 +855,12 @@ class GpuIndexClient:
             parts["docs"] = docs
         else:
             parts.update(docs=None, n_rows=m)
-        vocab = st.vocab
-        text_rows = numbered = None
-        if getattr(idx, "lex", None) is not None and self.device_text and self.number_on_device:
-            # tokenised AND numbered on the device: the rows come with their final ids, the new keys stay
-            # there until the index has taken the rows (commit_vocabulary below)
-            self._sync_vocabulary()
-            numbered = idx.number_text_rows([r.get("text", "") for r in rows])
-            parts["lex"] = (numbered.doc, numbered.term, None, max(len(vocab) + numbered.pending.n_new, 1))
-        elif getattr(idx, "lex", None) is not None and self.device_text:
-            # the same on the device: the unknown tokens come back as strings and are numbered here, in
-            # order of first appearance across the batch, exactly as the loop below numbers them
-            self._sync_vocabulary()
-            text_rows = idx.text_rows([r.get("text", "") for r in rows])
-            grown = {tok: len(vocab) + i for i, tok in enumerate(text_rows.unknown)}
-            t_dev = text_rows.term
-            if len(text_rows.unknown_which):
-                t_dev = t_dev.clone()
-                t_dev[t_dev < 0] = torch.from_numpy((len(vocab) + text_rows.unknown_which).astype(np.int32)).to(idx.device)
-            parts["lex"] = (text_rows.doc, t_dev, None, max(len(vocab) + len(grown), 1))
-        elif getattr(idx, "lex", None) is not None:
-            # term ids of the store's vocabulary; unseen terms get the next ids (committed to the
-            # store only after the index took the rows)
-            grown: Dict[str, int] = {}
-            d_tok, t_tok = [], []
-            for i, r in enumerate(rows):
-                for tok in self.tokenizer(r.get("text", "")):
-                    t = vocab.get(tok)
-                    if t is None:
-                        t = grown.get(tok)
-                        if t is None:
-                            t = grown[tok] = len(vocab) + len(grown)
-                    d_tok.append(i)
-                    t_tok.append(t)
-            parts["lex"] = (np.asarray(d_tok, dtype=np.int32), np.asarray(t_tok, dtype=np.int32), None,
-                            max(len(vocab) + len(grown), 1))
+        numbered = None
+        if getattr(idx, "lex", None) is not None:
+            # term ids of the vocabulary; unseen terms get the next ids (committed to the device vocabulary
+            # and to the store only after the index took the rows)
+            numbered = self._number_texts([r.get("text", "") for r in rows])
+            parts["lex"] = (numbered.doc, numbered.term, None, max(numbered.n_before + numbered.pending.n_new, 1))
         if idx.doc_coll is not None:
             for r in rows:   # a collection no earlier row carries gets the next id (ids never move)
                 c = r.get("collection")
@@ -917,17 +888,12 @@ class GpuIndexClient:
             parts["mentions"] = (np.asarray(me, dtype=np.int64), np.asarray(mc, dtype=np.int64),
                                  np.asarray(mw, dtype=np.float32))
         idx.append_rows(**parts)
-        if numbered is not None:        # index, device vocabulary, store rows, store vocabulary: in that order
+        # index, device vocabulary, store rows, store vocabulary: in that order
+        if numbered is not None and self.device_text:
             idx.commit_vocabulary(numbered.pending)
-            st.append(rows, tokenizer=None)
+        st.append(rows)
+        if numbered is not None:
             st.vocab.update((tok, numbered.n_before + i) for i, tok in enumerate(numbered.pending.terms))
-        elif text_rows is not None:       # index before store: the device vocabulary, then the rows, then the terms
-            if text_rows.unknown:
-                idx.grow_vocabulary(text_rows.unknown)
-            st.append(rows, tokenizer=None)
-            st.vocab.update(grown)
-        else:
-            st.append(rows, tokenizer=self.tokenizer if getattr(idx, "lex", None) is not None else None)
         if self.multi_tenant:
             self._org_code = org_code
             self._settle_deferred()   # (a deferred search may still read the plans' labels)

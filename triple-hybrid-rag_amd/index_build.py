@@ -133,12 +133,8 @@ def lexical_rows_device(texts: Sequence[str], tokenizer: Callable[[str], List[st
     decoded once, from the final key store."""
     import torch
     from .index import GpuIndex
-    from .index_text import TextTable, decode_keys, is_table_tokenizer
-    table = TextTable.default() if tokenizer is tokenize else is_table_tokenizer(tokenizer)
-    if table is None:
-        name = getattr(tokenizer, "__qualname__", None) or repr(tokenizer)
-        raise ValueError(f"from_rows(device=\"text\") needs backend.tokenize or a TextTable's .tokenize as the "
-                         f"tokenizer, not {name}: the device restates a table, not a function")
+    from .index_text import decode_keys, pack_encoded, tokenizer_table
+    table = tokenizer_table(tokenizer, "from_rows(device=\"text\")")
     if batch_bytes < 1:
         raise ValueError("from_rows(device=\"text\"): batch_bytes is at least 1")
     idx = GpuIndex().set_vocabulary([], table)
@@ -150,10 +146,7 @@ def lexical_rows_device(texts: Sequence[str], tokenizer: Callable[[str], List[st
         while b < len(enc) and size + len(enc[b]) <= batch_bytes:
             size += len(enc[b])
             b += 1
-        ptr = np.zeros(b - a + 1, dtype=np.int64)
-        np.cumsum(np.fromiter(map(len, enc[a:b]), dtype=np.int64, count=b - a), out=ptr[1:])
-        packed = (np.frombuffer(b"".join(enc[a:b]) + bytes(16), dtype=np.uint8), ptr)
-        rows = idx.number_text_rows(texts[a:b], packed=packed)
+        rows = idx.number_text_rows(texts[a:b], packed=pack_encoded(enc[a:b]))
         idx.commit_vocabulary(rows.pending, mirror=False)
         docs.append(rows.doc + a if a else rows.doc)
         terms.append(rows.term)
@@ -263,21 +256,17 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
     texts = [r.get("text", "") for r in child_rows]
     if isinstance(device, str) and device != "text":
         raise ValueError(f"from_rows: device is False, True or \"text\", not {device!r}")
-    if device == "text":
+    if device:
         from . import _native as N
-        vocab, d_dev, t_dev = lexical_rows_device(texts, tokenizer, batch_bytes)
+        if device == "text":
+            vocab, d_dev, t_dev = lexical_rows_device(texts, tokenizer, batch_bytes)
+        else:
+            import torch
+            vocab, d_tok, t_tok = lexical_rows(texts, tokenizer)
+            dev = torch.device("cuda", torch.cuda.current_device())
+            d_dev, t_dev = torch.from_numpy(d_tok).to(dev), torch.from_numpy(t_tok).to(dev)
         rowptr, pd, ptf, dl, df = (a.cpu().numpy() for a in N.lexical_build(d_dev, t_dev, None, n, max(len(vocab), 1)))
         rowptr, df = rowptr[:len(vocab) + 1], df[:len(vocab)]      # (no token at all: build_lexical's empty CSR)
-        dfh = df.astype(np.float64)
-        idf = np.log(1.0 + (float(n) - dfh + 0.5) / (dfh + 0.5))
-        avgdl = float(dl.astype(np.float64).sum()) / max(n, 1) or 1.0
-    elif device:
-        from . import _native as N
-        import torch
-        vocab, d_tok, t_tok = lexical_rows(texts, tokenizer)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        rowptr, pd, ptf, dl, df = (a.cpu().numpy() for a in N.lexical_build(
-            torch.from_numpy(d_tok).to(dev), torch.from_numpy(t_tok).to(dev), None, n, max(len(vocab), 1)))
         dfh = df.astype(np.float64)
         idf = np.log(1.0 + (float(n) - dfh + 0.5) / (dfh + 0.5))
         avgdl = float(dl.astype(np.float64).sum()) / max(n, 1) or 1.0

@@ -139,14 +139,46 @@ def is_table_tokenizer(tokenizer) -> Optional[TextTable]:
     return owner if isinstance(owner, TextTable) and getattr(tokenizer, "__func__", None) is TextTable.tokenize else None
 
 
+def tokenizer_table(tokenizer, needs: str) -> TextTable:
+    """The analysis table a tokenizer stands for: ``backend.tokenize`` is ``TextTable.default()``, a table's
+    ``.tokenize`` that table.  Any other is refused by name; ``needs`` begins the message (the caller's option)."""
+    from .backend import tokenize
+    table = TextTable.default() if tokenizer is tokenize else is_table_tokenizer(tokenizer)
+    if table is None:
+        name = getattr(tokenizer, "__qualname__", None) or repr(tokenizer)
+        raise ValueError(f"{needs} needs backend.tokenize or a TextTable's .tokenize as the tokenizer, "
+                         f"not {name}: the device restates a table, not a function")
+    return table
+
+
 def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     """The text store of thr_text_tokens -> (bytes uint8 with 16 zero bytes of padding behind the last text,
     ptr int64 [n + 1]); text d is bytes[ptr[d] : ptr[d + 1]]."""
-    enc = [t.encode("utf-8", "surrogatepass") for t in texts]
+    return pack_encoded([t.encode("utf-8", "surrogatepass") for t in texts])
+
+
+def pack_encoded(enc: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
+    """``pack_texts`` for texts that are encoded already (a caller that sized its batches by those lengths)."""
     ptr = np.zeros(len(enc) + 1, dtype=np.int64)
     if enc:
         np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc)), out=ptr[1:])
     return np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8), ptr
+
+
+def number_tokens(per_text_tokens, vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray, List[str]]:
+    """THE host numbering: the token lists of a batch, one per text -> (doc int32 [T], term int32 [T], the new
+    terms in id order).  A token outside ``vocab`` gets the next id at its first sighting, in text order
+    (build_lexical's numbering; thr_vocab_grow's on the device); ``vocab`` itself is not changed."""
+    grown: Dict[str, int] = {}
+    doc, term = [], []
+    for d, tokens in enumerate(per_text_tokens):
+        for tok in tokens:
+            t = vocab.get(tok)
+            if t is None:
+                t = grown.setdefault(tok, len(vocab) + len(grown))
+            doc.append(d)
+            term.append(t)
+    return np.asarray(doc, dtype=np.int32), np.asarray(term, dtype=np.int32), list(grown)
 
 
 def vocab_capacity(n_terms: int) -> int:
@@ -167,10 +199,10 @@ def host_query_row(tokens: Sequence[str], ids: Dict[str, int]) -> Tuple[List[int
         if t is None:
             flags |= N.THR_TEXT_UNKNOWN
         else:
-            seen.setdefault(t, None)
+            seen[t] = None      # (a key that is there keeps its place)
     if len(seen) > N.THR_BM25_MAX_TERMS:
-        flags |= N.THR_TEXT_TOO_MANY
-    return list(seen)[:N.THR_BM25_MAX_TERMS], min(len(seen), N.THR_BM25_MAX_TERMS + 1), flags
+        return list(seen)[:N.THR_BM25_MAX_TERMS], N.THR_BM25_MAX_TERMS + 1, flags | N.THR_TEXT_TOO_MANY
+    return list(seen), len(seen), flags
 
 
 class TextRows(NamedTuple):
@@ -262,9 +294,8 @@ class TextSearch:
         v0 = X["term_ptr"].shape[0] - 1
         v1 = v0 + len(terms)
         if terms:
-            enc = [t.encode("utf-8", "surrogatepass") for t in terms]
-            ptr = X["n_bytes"] + np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc)))
-            blob = np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8)
+            blob, ptr = pack_texts(terms)
+            ptr = X["n_bytes"] + ptr[1:]
             X["term_bytes"] = torch.cat([X["term_bytes"][:X["n_bytes"]], self._t(blob, torch.uint8)])
             X["term_ptr"] = torch.cat([X["term_ptr"], self._t(ptr, torch.int64)])
             X["n_bytes"] = int(ptr[-1])
@@ -291,16 +322,19 @@ class TextSearch:
         return X["ids"]
 
     # ------------------------------------------------------------ numbering new terms on the device
-    def number_text_rows(self, texts: Sequence[str], hash_mask: Optional[int] = None, packed=None) -> NumberedRows:
+    def number_text_rows(self, texts: Sequence[str], hash_mask: Optional[int] = None, packed=None,
+                         on_device: bool = True) -> NumberedRows:
         """The token rows of a batch of chunk texts with the new terms NUMBERED on the device ->
         NumberedRows(doc, term, n_before, pending): ``append_rows(lex=(doc, term, None, n_before +
         pending.n_new))`` takes them as they are, ``commit_vocabulary(pending)`` then puts the new keys into
-        the vocabulary.  The numbering is ``text_rows``' and the host loop's: the next id at a token's first
-        sighting, in text order (thr_text_tokens, then thr_vocab_grow).  Until the commit nothing of the
-        vocabulary changes.  Two read-backs: the counts, then n_new / n_new_bytes / status.
-        A batch that holds an exceptional text, or whose call comes back with THR_VOCAB_GROW_COLLISION, is
-        answered through ``text_rows`` and the host numbering: the same object with the same values.
-        THR_VOCAB_GROW_OVERFLOW is a second call with the room it reported.
+        the vocabulary.  The numbering is ``number_tokens``': the next id at a token's first sighting, in text
+        order (thr_text_tokens, then thr_vocab_grow).  Until the commit nothing of the vocabulary changes.
+        Two read-backs: the counts, then n_new / n_new_bytes / status.
+        ``on_device=False`` numbers on the host: ``text_rows`` (the unknown tokens come back as strings), its
+        numbering, one patch of the -1 rows; the pending set then holds the strings.  A batch that holds an
+        exceptional text, or whose call comes back with THR_VOCAB_GROW_COLLISION, is answered that way too:
+        the same object with the same values.  THR_VOCAB_GROW_OVERFLOW is a second call with the room it
+        reported.
         ``hash_mask`` is for tests (thr_hip.h); ``packed``: pack_texts(texts), when the caller has it."""
         if self.text is None:
             raise N.NativeError("number_text_rows: the index has no vocabulary (set_vocabulary)")
@@ -310,8 +344,16 @@ class TextSearch:
         if not texts:
             empty = torch.empty(0, dtype=torch.int32, device=self.device)
             return NumberedRows(empty, empty.clone(), n_before, PendingVocabulary(n_before, 0))
+        if not on_device:
+            rows = self.text_rows(texts)
+            term = rows.term
+            if len(rows.unknown_which):
+                term = term.clone()
+                term[term < 0] = self._t((n_before + rows.unknown_which).astype(np.int32), torch.int32)
+            return NumberedRows(rows.doc, term, n_before,
+                                PendingVocabulary(n_before, len(rows.unknown), terms=list(rows.unknown)))
         if X["table"].exceptional_among(texts):
-            return self._number_on_host(texts, n_before)
+            return self.number_text_rows(texts, on_device=False)
         rows = self._text_tokens(texts, packed)
         n_total, n_unknown = torch.cat([rows["n_total"], rows["n_unknown"]]).tolist()
         assert n_total <= rows["capacity"]
@@ -329,21 +371,12 @@ class TextSearch:
                                workspace=self._scratch("_ws_grow", max(need, 16)))
             n_new, n_new_bytes, status = torch.cat([out["n_new"].long(), out["n_new_bytes"], out["status"].long()]).tolist()
             if status & N.THR_VOCAB_GROW_COLLISION:
-                return self._number_on_host(texts, n_before)
+                return self.number_text_rows(texts, on_device=False)
             if not status & N.THR_VOCAB_GROW_OVERFLOW:
                 break
             room, patch = n_new_bytes, None     # (the rows are patched already: the ids do not depend on the room)
         return NumberedRows(doc, term, n_before,
                             PendingVocabulary(n_before, n_new, n_new_bytes, out["new_bytes"], out["new_ptr"]))
-
-    def _number_on_host(self, texts: Sequence[str], n_before: int) -> NumberedRows:
-        rows = self.text_rows(texts)
-        term = rows.term
-        if len(rows.unknown_which):
-            term = term.clone()
-            term[term < 0] = self._t((n_before + rows.unknown_which).astype(np.int32), torch.int32)
-        return NumberedRows(rows.doc, term, n_before,
-                            PendingVocabulary(n_before, len(rows.unknown), terms=list(rows.unknown)))
 
     def commit_vocabulary(self, pending: PendingVocabulary, mirror: bool = True) -> "TextSearch":
         """Put the new terms of a ``number_text_rows`` call into the vocabulary: the key bytes and pointers
