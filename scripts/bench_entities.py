@@ -116,7 +116,7 @@ def main():
             plan = plan_needles(sub, 20)
             tabs = [idx._t(a, dt) for a, dt in ((plan.needles, torch.uint8), (plan.needle_len, torch.int32),
                                                 (plan.query_needles, torch.int32), (plan.query_per, torch.int32))]
-            need = int(N.load().thr_entity_match_workspace_bytes(Ent["n"], plan.needles.shape[0], len(sub)))
+            need = N.entity_match_workspace_bytes(Ent["n"], plan.needles.shape[0], len(sub))
             ws = torch.empty(need, dtype=torch.uint8, device=idx.device)
             call = lambda: N.entity_match(Ent["name_bytes"], Ent["name_ptr"], *tabs, workspace=ws)
             for _ in range(3):

@@ -162,7 +162,7 @@ def main():
     tokens_ms = events_ms(lambda: N.text_tokens(rows["bytes_dev"], rows["ptr_dev"], n_bytes, X["table_dev"], X["slots"],
                                                 X["term_bytes"], X["term_ptr"], workspace=idx._ws_text), args.rounds)
     term = rows["term"][:n_total].clone()
-    ws = torch.empty(int(N.load().thr_vocab_grow_workspace_bytes(n_unknown)), dtype=torch.uint8, device=idx.device)
+    ws = torch.empty(N.vocab_grow_workspace_bytes(n_unknown), dtype=torch.uint8, device=idx.device)
     fresh = rows["term"][:n_total].clone()
 
     def grow():

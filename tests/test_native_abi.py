@@ -3,6 +3,8 @@ include/thr_hip.h declares (no compute calls without a GPU)."""
 import os
 import re
 
+import pytest
+
 import triple_hybrid_rag_amd as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -124,3 +126,179 @@ def test_no_cpu_fallback_in_the_product_package():
             if f.endswith(".py"):
                 src = open(os.path.join(dirpath, f)).read()
                 assert "import oracle" not in src and "from oracle" not in src, f
+
+
+# ----------------------------------------------------------- the binding against the header
+def header_text():
+    """include/thr_hip.h without comments and preprocessor lines (#define lines are kept apart)."""
+    text = open(os.path.join(ROOT, "include", "thr_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    lines = text.split("\n")
+    defines = [ln for ln in lines if ln.lstrip().startswith("#")]
+    return "\n".join(ln for ln in lines if not ln.lstrip().startswith("#")), defines
+
+
+def ctype_class(ct):
+    """What the comparison knows of a ctypes type: a pointer, or (float?, bytes, signed?) of a scalar
+    -- by size and signedness, not by name (c_size_t IS c_uint64 here, c_int64 is c_long)."""
+    import ctypes as C
+    if ct is None:
+        return "void"
+    if issubclass(ct, C._Pointer) or ct._type_ in "Pz":
+        return "pointer"
+    return (ct._type_ in "fdg", C.sizeof(ct), ct._type_ not in "fdg" and ct(-1).value < 0)
+
+
+def header_class(ctype: str):
+    """The class of one C type of the header (the issue's table: pointers and thr_stream_t are
+    pointers; int, int64_t, uint64_t, size_t and double by their size and signedness)."""
+    import ctypes as C
+    words = [w for w in re.sub(r"\*", " * ", ctype).split() if w != "const"]
+    if "*" in words or words == ["thr_stream_t"]:
+        return "pointer"
+    scalar = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+              "double": C.c_double}
+    assert len(words) == 1 and words[0] in scalar, f"thr_hip.h uses a type this test does not know: {ctype!r}"
+    return ctype_class(scalar[words[0]])
+
+
+def header_prototypes():
+    """{name: (result class, [parameter classes])} of every thr_* function thr_hip.h declares."""
+    text, _ = header_text()
+    protos = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(thr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text):
+        res, name, params = m.group(1), m.group(2), m.group(3).strip()
+        res = " ".join(w for w in res.split() if w != "extern")
+        args = []
+        if params != "void":
+            for p in params.split(","):
+                p = p.strip()
+                ctype = re.sub(r"[A-Za-z_]\w*$", "", p) if re.search(r"[\s\*][A-Za-z_]\w*$", p) else p   # drop the name
+                args.append(header_class(ctype))
+        protos[name] = (header_class(res), args)
+    return protos
+
+
+def test_signatures_agree_with_the_header():
+    """Every entry of _SIGNATURES has the header's result type and, argument by argument, the
+    header's parameter classes: an argtypes list that gains or loses one entry (every later argument
+    of that call shifts by one) fails here, on the CPU.  (Tried by hand once: with one _vp taken
+    from thr_dense_rescue's list and with one added to thr_rrf_fuse's, this test fails naming the
+    symbol.)"""
+    N = T._native
+    protos = header_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(N._SIGNATURES) and len(protos) == 65
+    for name, (res, args) in N._SIGNATURES.items():
+        want_res, want_args = protos[name]
+        assert ctype_class(res) == want_res, f"{name}: result type differs from thr_hip.h"
+        got = [ctype_class(a) for a in args]
+        assert len(got) == len(want_args), f"{name}: {len(got)} argtypes, thr_hip.h declares {len(want_args)} parameters"
+        for i, (g, w) in enumerate(zip(got, want_args)):
+            assert g == w, f"{name}: argument {i} is {args[i].__name__}, thr_hip.h wants {w}"
+
+
+# THR_* names of _native that thr_hip.h does not #define, each with its reason (none today)
+NOT_IN_HEADER = {}
+
+
+def test_constants_agree_with_the_header():
+    N = T._native
+    _, defines = header_text()
+    header = {}
+    for ln in defines:
+        m = re.match(r"\s*#\s*define\s+(THR_[A-Z0-9_]+)\s+(\S.*)$", ln)
+        if m:
+            expr = re.sub(r"\b(0[xX][0-9a-fA-F]+|\d+)[uUlL]*\b", r"\1", m.group(2).strip())
+            assert re.fullmatch(r"[0-9a-fA-FxX<>()|+*\s-]+", expr), f"{m.group(1)}: cannot evaluate {m.group(2)!r}"
+            header[m.group(1)] = eval(expr, {"__builtins__": {}})
+    assert header["THR_ABI_VERSION"] == N.ABI_VERSION
+    assert header["THR_BM25_MAX_QUERIES"] == 1 << 20 and header["THR_TEXT_MAX_BYTES"] == 0x7FFFFFFF and \
+        header["THR_FLAG_CERTIFIED"] == 1                       # the three forms are evaluated
+    mine = {k: v for k, v in vars(N).items() if k.startswith("THR_") and isinstance(v, int)}
+    assert len(mine) >= 30
+    for name, value in mine.items():
+        if name in NOT_IN_HEADER:
+            assert name not in header, f"{name} is in thr_hip.h now: drop it from NOT_IN_HEADER"
+            continue
+        assert name in header, f"_native.{name} is not a #define of thr_hip.h (list it in NOT_IN_HEADER with the reason, or remove it)"
+        assert value == header[name], f"_native.{name} = {value}, thr_hip.h says {header[name]}"
+
+
+# ----------------------------------------------------------- twins and accessors, library stubbed
+class RecordingLibrary:
+    """Stands in for libthr_hip.so: every thr_* attribute is a function that records its call."""
+
+    def __init__(self, result=0):
+        self.calls, self.result = [], result
+
+    def __getattr__(self, name):
+        if not name.startswith("thr_"):
+            raise AttributeError(name)
+        return lambda *args: (self.calls.append((name, args)), self.result)[1]
+
+
+def test_rrf_twins_reach_their_own_entry_with_the_same_arguments(monkeypatch):
+    """rrf_fuse and rrf_fuse_standalone share one body: each still calls its own entry point with
+    the argument tuple it passed when it had a body of its own -- three (pointer, width) pairs, nq,
+    the three weights, its own scalar (rrf_k / the two_channels flag), top_k, the four outputs
+    (a null ranks pointer unless asked for) and the stream."""
+    torch = pytest.importorskip("torch")
+    N = T._native
+    lib = RecordingLibrary()
+    monkeypatch.setattr(N, "load", lambda build_if_missing=True: lib)
+    monkeypatch.setattr(N, "_dev", lambda t, dtype, name, ndim=None: 0 if t is None else t.data_ptr())   # (host tensors)
+    monkeypatch.setattr(N, "_stream", lambda: 77)
+    lex = torch.zeros((3, 5), dtype=torch.int64)
+    sem = torch.zeros((3, 7), dtype=torch.int64)
+
+    def outputs(a, ranks):
+        assert all(isinstance(p, int) and p for p in a[12:14] + a[15:16]) and (a[14] != 0) == ranks and a[16] == 77
+    head = (lex.data_ptr(), 5, sem.data_ptr(), 7, 0, 0, 3)
+    ids, sc, rk, cnt = N.rrf_fuse(lex, sem, None, 4, rrf_k=61)
+    (name, a), = lib.calls
+    assert name == "thr_rrf_fuse" and a[:12] == head + (0.7, 0.8, 1.0, 61, 4) and len(a) == 17
+    outputs(a, False)
+    assert rk is None and (ids.shape, sc.shape, cnt.shape) == ((3, 4), (3, 4), (3,))
+    assert a[12:16] == (ids.data_ptr(), sc.data_ptr(), 0, cnt.data_ptr())
+    lib.calls.clear()
+    ids, sc, rk, cnt = N.rrf_fuse_standalone(lex, sem, None, 6, w_lex=0.5, two_channels=True)
+    (name, a), = lib.calls
+    assert name == "thr_rrf_fuse_standalone" and a[:12] == head + (0.5, 0.8, 1.0, 1, 6) and len(a) == 17
+    outputs(a, True)
+    assert a[12:16] == (ids.data_ptr(), sc.data_ptr(), rk.data_ptr(), cnt.data_ptr()) and rk.shape == (3, 6, 3)
+    lib.calls.clear()
+    N.rrf_fuse_standalone(None, sem, None, 2, want_ranks=False)
+    (name, a), = lib.calls
+    assert name == "thr_rrf_fuse_standalone" and a[:12] == (0, 0, sem.data_ptr(), 7, 0, 0, 3, 0.7, 0.8, 1.0, 0, 2)
+    outputs(a, False)
+    lib.calls.clear()
+    N.rrf_fuse(lex, None, None, 3, want_ranks=True)
+    (name, a), = lib.calls
+    assert name == "thr_rrf_fuse" and a[:12] == (lex.data_ptr(), 5, 0, 0, 0, 0, 3, 0.7, 0.8, 1.0, 60, 3)
+    outputs(a, True)
+    for fuse, what in ((N.rrf_fuse, "rrf_fuse:"), (N.rrf_fuse_standalone, "rrf_fuse_standalone:")):
+        with pytest.raises(N.NativeError, match=what + ".*512"):
+            fuse(lex, sem, None, 513)
+    lib.result = -1                                              # a failing call is reported under its own name
+    monkeypatch.setattr(lib, "thr_error_string", lambda rc: b"invalid argument", raising=False)
+    with pytest.raises(N.NativeError, match="thr_rrf_fuse_standalone failed"):
+        N.rrf_fuse_standalone(lex, sem, None, 2)
+
+
+def test_workspace_size_accessors_forward_their_arguments(monkeypatch):
+    N = T._native
+    lib = RecordingLibrary(result=4096)
+    monkeypatch.setattr(N, "load", lambda build_if_missing=True: lib)
+    for accessor, args in ((N.entity_match_workspace_bytes, (1000, 7, 3)), (N.text_tokens_workspace_bytes, (5, 300, 152)),
+                           (N.query_terms_workspace_bytes, (9,)), (N.vocab_grow_workspace_bytes, (31,)),
+                           (N.bm25_workspace_bytes, (2048, 4, 50))):
+        lib.calls.clear()
+        got = accessor(*args)
+        assert type(got) is int and got == 4096
+        assert lib.calls == [("thr_" + accessor.__name__, args)]
+    # ... and no file of the package reaches around them: thr_* entry points are called in _native alone
+    pkg = os.path.join(ROOT, "triple-hybrid-rag_amd")
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py") and f != "_native.py":
+            assert not re.search(r"\.thr_[a-z0-9_]+\(", open(os.path.join(pkg, f)).read()), f

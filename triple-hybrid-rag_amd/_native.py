@@ -205,6 +205,20 @@ def _dev(t: Optional[torch.Tensor], dtype, name: str, ndim: Optional[int] = None
     return t.data_ptr()
 
 
+def _workspace(workspace: Optional[torch.Tensor], need: int, device) -> Tuple[torch.Tensor, int]:
+    """THE workspace rule -> (the tensor to hand to the library, its size in bytes): the caller's
+    ``workspace`` when it holds at least ``need`` bytes (any dtype: bytes are numel x element size;
+    a contiguous device tensor), else a fresh uint8 one of max(need, 16) bytes (no call hands the
+    library a null workspace)."""
+    if workspace is not None:
+        nbytes = workspace.numel() * workspace.element_size()
+        if nbytes >= need:
+            _dev(workspace, workspace.dtype, "workspace")
+            return workspace, nbytes
+    nbytes = max(int(need), 16)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
 def device_info() -> Tuple[int, int, str]:
     cus, hbm = C.c_int(0), C.c_int64(0)
     arch = C.create_string_buffer(128)
@@ -260,9 +274,11 @@ def _coll(doc_coll, query_coll, n: int, nq: int):
     return _dev(doc_coll, torch.int32, "doc_coll", 1), _dev(query_coll, torch.int32, "query_coll", 1)
 
 
-def dense_topk(docs, dnorm, inv_norm, queries, k: int, kprime: int, id_base: int = 0,
-               workspace: Optional[torch.Tensor] = None, doc_coll=None, query_coll=None):
-    """-> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
+def _dense_operands(docs, queries, dnorm=None, inv_norm=None, docs16=None):
+    """THE operand check of the dense calls -> (docs, queries, dnorm, inv_norm, docs16 pointers, n, d, nq).
+    docs f32 [n, d]; queries f32 [nq, d]; of the rest what the entry takes (None: a null pointer, which
+    the library refuses where the operand is not optional): dnorm f64 [n], inv_norm f32 [n], docs16 the
+    fragment-major f16 [ceil32(n), d] image of docs."""
     pd = _dev(docs, torch.float32, "docs", 2)
     n, d = docs.shape
     pq = _dev(queries, torch.float32, "queries", 2)
@@ -271,51 +287,42 @@ def dense_topk(docs, dnorm, inv_norm, queries, k: int, kprime: int, id_base: int
         raise NativeError(f"queries dim {queries.shape[1]} != docs dim {d}")
     pn = _dev(dnorm, torch.float64, "dnorm", 1)
     pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    if dnorm.shape[0] != n or inv_norm.shape[0] != n:
+    if (dnorm is not None and dnorm.shape[0] != n) or (inv_norm is not None and inv_norm.shape[0] != n):
         raise NativeError("dnorm / inv_norm length != n_docs")
-    need = dense_workspace_bytes(n, d, nq, kprime)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=docs.device)
-    pw = _dev(workspace, workspace.dtype, "workspace")
+    ph = _dev(docs16, torch.float16, "docs16", 2)
+    if docs16 is not None and tuple(docs16.shape) != ((n + 31) // 32 * 32, d):
+        raise NativeError("docs16 is not the fragment-major copy of docs (thr_dense_quantize_f16)")
+    return pd, pq, pn, pi, ph, n, d, nq
+
+
+def dense_topk(docs, dnorm, inv_norm, queries, k: int, kprime: int, id_base: int = 0,
+               workspace: Optional[torch.Tensor] = None, doc_coll=None, query_coll=None):
+    """-> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
+    pd, pq, pn, pi, _, n, d, nq = _dense_operands(docs, queries, dnorm, inv_norm)
+    ws, nbytes = _workspace(workspace, dense_workspace_bytes(n, d, nq, kprime), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_topk(pd, pn, pi, n, d, id_base, pq, nq, k, kprime, pdc, pqc, S.data_ptr(),
-                                 I.data_ptr(), cnt.data_ptr(), flg.data_ptr(), pw,
-                                 workspace.numel() * workspace.element_size(), _stream()),
+                                 I.data_ptr(), cnt.data_ptr(), flg.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_dense_topk")
     return S, I, cnt, flg
 
 
 def dense_topk_exact(docs, dnorm, queries, k: int, id_base: int = 0, doc_coll=None, query_coll=None):
-    pd = _dev(docs, torch.float32, "docs", 2)
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise NativeError(f"queries dim {queries.shape[1]} != docs dim {d}")
-    pn = _dev(dnorm, torch.float64, "dnorm", 1)
-    if dnorm.shape[0] != n:
-        raise NativeError("dnorm length != n_docs")
-    need = int(load().thr_dense_exact_workspace_bytes(n, nq))
-    ws = torch.empty(need, dtype=torch.uint8, device=docs.device)
+    pd, pq, pn, _, _, n, d, nq = _dense_operands(docs, queries, dnorm)
+    ws, nbytes = _workspace(None, int(load().thr_dense_exact_workspace_bytes(n, nq)), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_topk_exact(pd, pn, n, d, id_base, pq, nq, k, pdc, pqc, S.data_ptr(),
                                        I.data_ptr(), cnt.data_ptr(), flg.data_ptr(),
-                                       ws.data_ptr(), need, _stream()), "thr_dense_topk_exact")
+                                       ws.data_ptr(), nbytes, _stream()), "thr_dense_topk_exact")
     return S, I, cnt, flg
 
 
 def dense_scan_probe(docs, inv_norm, queries, workspace: torch.Tensor) -> None:
-    pd = _dev(docs, torch.float32, "docs", 2)
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    if queries.shape[1] != d or inv_norm.shape[0] != n:
-        raise NativeError("probe: shape mismatch")
-    pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    pw = _dev(workspace, workspace.dtype, "workspace")
-    _check(load().thr_dense_scan_probe(pd, pi, n, d, pq, queries.shape[0], pw,
-                                       workspace.numel() * workspace.element_size(), _stream()),
+    pd, pq, _, pi, _, n, d, nq = _dense_operands(docs, queries, inv_norm=inv_norm)
+    ws, nbytes = _workspace(workspace, 0, docs.device)      # (the caller's as it is: the library judges its size)
+    _check(load().thr_dense_scan_probe(pd, pi, n, d, pq, nq, ws.data_ptr(), nbytes, _stream()),
            "thr_dense_scan_probe")
 
 
@@ -356,20 +363,25 @@ def dense_rescue(docs, dnorm, queries, S, I, cnt, flg, id_base: int = 0,
                  workspace: Optional[torch.Tensor] = None, doc_coll=None, query_coll=None) -> torch.Tensor:
     """Redo, in place and without a host read-back, the queries of a dense_topk[_f16] result
     whose flags lack THR_FLAG_CERTIFIED.  -> device int32[1]: how many were redone."""
-    pd = _dev(docs, torch.float32, "docs", 2)
-    pn = _dev(dnorm, torch.float64, "dnorm", 1)
-    pq = _dev(queries, torch.float32, "queries", 2)
-    n, d = docs.shape
-    nq, k = I.shape
-    need = int(load().thr_dense_rescue_workspace_bytes(nq, k))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=docs.device)
-    n_rescued = torch.empty(1, dtype=torch.int32, device=docs.device)   # (thr_dense_rescue writes the zero)
+    pd, pq, pn, _, _, n, d, nq = _dense_operands(docs, queries, dnorm)
+    # the one dense call that writes into tensors the caller made (one test for the four of them,
+    # written out: this runs in front of every search step)
+    k = I.shape[1] if I.dim() == 2 else 0
+    dev, SI, CF = docs.device, (nq, k), (nq,)
+    if S.dtype != torch.float64 or I.dtype != torch.int64 or cnt.dtype != torch.int32 or flg.dtype != torch.int32 or \
+            S.shape != SI or I.shape != SI or cnt.shape != CF or flg.shape != CF or \
+            S.device != dev or I.device != dev or cnt.device != dev or flg.device != dev or \
+            not (S.is_contiguous() and I.is_contiguous() and cnt.is_contiguous() and flg.is_contiguous()) or \
+            not 1 <= k <= THR_DENSE_MAX_K:
+        raise NativeError(f"dense_rescue: S float64 and I int64 [{nq}, k], 1 <= k <= {THR_DENSE_MAX_K}, cnt and flg "
+                          f"int32 [{nq}], all contiguous and on docs' device; got " +
+                          ", ".join(f"{tuple(t.shape)} {t.dtype} {t.device}" for t in (S, I, cnt, flg)))
+    lib = load()
+    ws, nbytes = _workspace(workspace, lib.thr_dense_rescue_workspace_bytes(nq, k), dev)
+    n_rescued = torch.empty(1, dtype=torch.int32, device=dev)   # (thr_dense_rescue writes the zero)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
-    _check(load().thr_dense_rescue(pd, pn, n, d, id_base, pq, nq, k, pdc, pqc, S.data_ptr(), I.data_ptr(),
-                                   cnt.data_ptr(), flg.data_ptr(), n_rescued.data_ptr(),
-                                   workspace.data_ptr(),
-                                   workspace.numel() * workspace.element_size(), _stream()),
+    _check(lib.thr_dense_rescue(pd, pn, n, d, id_base, pq, nq, k, pdc, pqc, S.data_ptr(), I.data_ptr(),
+                                cnt.data_ptr(), flg.data_ptr(), n_rescued.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_dense_rescue")
     return n_rescued
 
@@ -421,31 +433,25 @@ def dense_f16_workspace_bytes(n_docs: int, dim: int, n_queries: int, kprime: int
 def dense_topk_f16(docs, docs16, doc_rel_err: float, dnorm, inv_norm, queries, k: int,
                    kprime: int, id_base: int = 0, workspace: Optional[torch.Tensor] = None,
                    doc_coll=None, query_coll=None):
-    pd = _dev(docs, torch.float32, "docs", 2)
-    ph = _dev(docs16, torch.float16, "docs16", 2) if docs16 is not None else None
-    n, d = docs.shape
-    if docs16 is not None and tuple(docs16.shape) != ((n + 31) // 32 * 32, d):
-        raise NativeError("docs16 is not the fragment-major copy of docs (thr_dense_quantize_f16)")
-    pq = _dev(queries, torch.float32, "queries", 2)
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise NativeError(f"queries dim {queries.shape[1]} != docs dim {d}")
-    pn = _dev(dnorm, torch.float64, "dnorm", 1)
-    pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    if dnorm.shape[0] != n or inv_norm.shape[0] != n:
-        raise NativeError("dnorm / inv_norm length != n_docs")
-    need = dense_f16_workspace_bytes(n, d, nq, kprime)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=docs.device)
-    pw = _dev(workspace, workspace.dtype, "workspace")
+    pd, pq, pn, pi, ph, n, d, nq = _dense_operands(docs, queries, dnorm, inv_norm, docs16)
+    ws, nbytes = _workspace(workspace, dense_f16_workspace_bytes(n, d, nq, kprime), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_topk_f16(pd, ph, float(doc_rel_err), pn, pi, n, d, id_base, pq, nq, k,
                                      kprime, pdc, pqc, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
-                                     flg.data_ptr(), pw,
-                                     workspace.numel() * workspace.element_size(), _stream()),
+                                     flg.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_dense_topk_f16")
     return S, I, cnt, flg
+
+
+def _held_workspace(what: str, workspace: torch.Tensor, need: int) -> Tuple[torch.Tensor, int]:
+    """The workspace rule for the one that carries the candidate lists from dense_shortlist_f16 to the
+    matching dense_finish_f16: the caller's or none -- a too-small one is refused, not replaced."""
+    nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    if nbytes < need:
+        raise NativeError(f"{what}: workspace smaller than thr_dense_f16_workspace_bytes")
+    _dev(workspace, workspace.dtype, "workspace")
+    return workspace, nbytes
 
 
 def dense_shortlist_f16(docs, docs16, doc_rel_err: float, inv_norm, queries, kprime: int, m: int,
@@ -453,23 +459,12 @@ def dense_shortlist_f16(docs, docs16, doc_rel_err: float, inv_norm, queries, kpr
     """First half of the search split around the shards' exchange (thr_hip.h e1): the filter scan
     (candidate lists left in ``workspace``) and per query the ``m`` largest scan scores as lower
     bounds of ||q|| x cosine -> float32 [nq, m], -inf padded."""
-    pd = _dev(docs, torch.float32, "docs", 2)
-    ph = _dev(docs16, torch.float16, "docs16", 2) if docs16 is not None else None
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    nq = queries.shape[0]
-    if queries.shape[1] != d or inv_norm.shape[0] != n:
-        raise NativeError("shortlist: shape mismatch")
-    pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    need = dense_f16_workspace_bytes(n, d, nq, kprime)
-    if workspace.numel() * workspace.element_size() < need:
-        raise NativeError("shortlist: workspace smaller than thr_dense_f16_workspace_bytes")
-    pw = _dev(workspace, workspace.dtype, "workspace")
+    pd, pq, _, pi, ph, n, d, nq = _dense_operands(docs, queries, inv_norm=inv_norm, docs16=docs16)
+    ws, nbytes = _held_workspace("shortlist", workspace, dense_f16_workspace_bytes(n, d, nq, kprime))
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     lb = torch.empty((nq, m), dtype=torch.float32, device=docs.device)
     _check(load().thr_dense_shortlist_f16(pd, ph, float(doc_rel_err), pi, n, d, pq, nq, kprime, pdc, pqc,
-                                          m, lb.data_ptr(), pw,
-                                          workspace.numel() * workspace.element_size(), _stream()),
+                                          m, lb.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_dense_shortlist_f16")
     return lb
 
@@ -491,15 +486,7 @@ def dense_finish_f16(docs, docs16, doc_rel_err: float, dnorm, inv_norm, queries,
     matching dense_shortlist_f16 call left in ``workspace`` (same arguments), with the shards'
     common floor: ``gfloor`` [nq] (dense_floor's output), or ``lb_all`` [n_shards, nq, m] -- the
     gathered bounds themselves, the k-th largest found inside the band kernel."""
-    pd = _dev(docs, torch.float32, "docs", 2)
-    ph = _dev(docs16, torch.float16, "docs16", 2) if docs16 is not None else None
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    nq = queries.shape[0]
-    pn = _dev(dnorm, torch.float64, "dnorm", 1)
-    pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    if queries.shape[1] != d or dnorm.shape[0] != n or inv_norm.shape[0] != n:
-        raise NativeError("finish: shape mismatch")
+    pd, pq, pn, pi, ph, n, d, nq = _dense_operands(docs, queries, dnorm, inv_norm, docs16)
     pg = None
     if gfloor is not None:
         pg = _dev(gfloor, torch.float32, "gfloor", 1)
@@ -513,37 +500,29 @@ def dense_finish_f16(docs, docs16, doc_rel_err: float, dnorm, inv_norm, queries,
         g, nq_l, m = lb_all.shape
         if nq_l != nq:
             raise NativeError("lb_all: [n_shards, nq, m]")
-    pw = _dev(workspace, workspace.dtype, "workspace")
+    ws, nbytes = _held_workspace("finish", workspace, dense_f16_workspace_bytes(n, d, nq, kprime))
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_finish_f16(pd, ph, float(doc_rel_err), pn, pi, n, d, id_base, pq, nq, k,
                                        kprime, pdc, pqc, pg, pl, g, m, S.data_ptr(), I.data_ptr(),
-                                       cnt.data_ptr(), flg.data_ptr(), pw,
-                                       workspace.numel() * workspace.element_size(), _stream()),
+                                       cnt.data_ptr(), flg.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_dense_finish_f16")
     return S, I, cnt, flg
 
 
 def dense_scan_probe_f16(docs, docs16, inv_norm, queries, workspace: torch.Tensor) -> None:
-    pd = _dev(docs, torch.float32, "docs", 2)
-    ph = _dev(docs16, torch.float16, "docs16", 2) if docs16 is not None else None
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    if queries.shape[1] != d or inv_norm.shape[0] != n:
-        raise NativeError("probe: shape mismatch")
-    pi = _dev(inv_norm, torch.float32, "inv_norm", 1)
-    pw = _dev(workspace, workspace.dtype, "workspace")
-    _check(load().thr_dense_scan_probe_f16(pd, ph, pi, n, d, pq, queries.shape[0], pw,
-                                           workspace.numel() * workspace.element_size(),
-                                           _stream()), "thr_dense_scan_probe_f16")
+    pd, pq, _, pi, ph, n, d, nq = _dense_operands(docs, queries, inv_norm=inv_norm, docs16=docs16)
+    ws, nbytes = _workspace(workspace, 0, docs.device)      # (the caller's as it is: the library judges its size)
+    _check(load().thr_dense_scan_probe_f16(pd, ph, pi, n, d, pq, nq, ws.data_ptr(), nbytes, _stream()),
+           "thr_dense_scan_probe_f16")
 
 
 def dense_scan_stamps_f16(docs16, n_docs: int, queries_n: int, workspace: torch.Tensor):
     """Phase stamps of the float16-copy scan -> int64 [n_waves, 8] (see thr_hip.h)."""
     ph = _dev(docs16, torch.float16, "docs16", 2)
     d = docs16.shape[1]
-    pw = _dev(workspace, workspace.dtype, "workspace")
-    nbytes = workspace.numel() * workspace.element_size()
+    ws, nbytes = _workspace(workspace, 0, docs16.device)    # (as the probes: the library judges its size)
+    pw = ws.data_ptr()
     nw = C.c_int(0)
     _check(load().thr_dense_scan_stamps_f16(ph, n_docs, d, queries_n, pw, nbytes, None, C.byref(nw),
                                             _stream()), "thr_dense_scan_stamps_f16")
@@ -575,11 +554,10 @@ def lexical_build(doc: torch.Tensor, term: torch.Tensor, tf: Optional[torch.Tens
     nnz = torch.zeros(1, dtype=torch.int64, device=dev)
     if n == 0:
         return rowptr.zero_(), post_doc[:0], post_tf[:0], doclen.zero_(), df.zero_()
-    need = int(load().thr_lexical_build_workspace_bytes(n, n_vocab))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(None, int(load().thr_lexical_build_workspace_bytes(n, n_vocab)), dev)
     _check(load().thr_lexical_build(pdoc, pterm, ptf, n, n_docs, n_vocab, rowptr.data_ptr(),
                                     post_doc.data_ptr(), post_tf.data_ptr(), doclen.data_ptr(),
-                                    df.data_ptr(), nnz.data_ptr(), ws.data_ptr(), need, _stream()),
+                                    df.data_ptr(), nnz.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_lexical_build")
     k = int(nnz.item())
     return rowptr, post_doc[:k].clone(), post_tf[:k].clone(), doclen, df
@@ -662,15 +640,14 @@ def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out
         pay_out = torch.empty(nnz, dtype=pay.dtype, device=dev)
     rowptr_out = torch.empty(rows + 1, dtype=torch.int64, device=dev)
     kept = torch.zeros(1, dtype=torch.int64, device=dev)
-    need = int(load().thr_csr_compact_workspace_bytes(rows, nnz))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(None, int(load().thr_csr_compact_workspace_bytes(rows, nnz)), dev)
     cap = ids_out.shape[0] if pay is None else min(ids_out.shape[0], pay_out.shape[0])
     _check(load().thr_csr_compact(prp, rows, nnz, pid if nnz else None,
                                   _dev(pay, pay.dtype, "pay", 1) if nnz and pay is not None else None,
                                   prm if remap.shape[0] else None, remap.shape[0], int(id_base),
                                   rowptr_out.data_ptr(), _dev(ids_out, torch.int32, "ids_out", 1) if nnz else None,
                                   _dev(pay_out, pay.dtype, "pay_out", 1) if nnz and pay is not None else None,
-                                  cap, kept.data_ptr(), ws.data_ptr(), need, _stream()), "thr_csr_compact")
+                                  cap, kept.data_ptr(), ws.data_ptr(), nbytes, _stream()), "thr_csr_compact")
     return rowptr_out, ids_out, (pay_out if pay is not None else None), int(kept.item())
 
 
@@ -697,7 +674,7 @@ def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool
     ``pay_*`` 4-byte tensors [nnz] of one dtype, on both sides or on neither.  ``drop_present``: the
     set union (a B entry whose id is in A's row is dropped; both sides strictly ascending within a
     row), else the multiset merge.  ``ids_out`` / ``pay_out``: capacity-reserved 1-d destinations
-    (allocated for nnz_a + nnz_b when None); ``workspace``: uint8, reused when large enough.  One
+    (allocated for nnz_a + nnz_b when None); ``workspace``: reused when large enough (_workspace).  One
     host read-back at the end (the count and the status word).  ``check``: raise NativeError on a
     non-zero status (inputs not in canonical form, destination too small) instead of returning it.
     -> (rowptr_out, ids_out, pay_out or None, nnz_out, status)."""
@@ -732,9 +709,7 @@ def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool
         pay_out = torch.empty(nnz_a + nnz_b, dtype=pay_like.dtype, device=dev)
     rowptr_out = torch.empty(rows_b + 1, dtype=torch.int64, device=dev)
     tail = torch.zeros(2, dtype=torch.int64, device=dev)      # *nnz_out, *status_out
-    need = int(load().thr_csr_merge_workspace_bytes(rows_b, nnz_a, nnz_b))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(workspace, int(load().thr_csr_merge_workspace_bytes(rows_b, nnz_a, nnz_b)), dev)
     cap = ids_out.shape[0] if pay_like is None else min(ids_out.shape[0], pay_out.shape[0])
     has = pay_like is not None
     _check(load().thr_csr_merge(pra if rows_a else None, rows_a, nnz_a, pia if nnz_a else None,
@@ -744,8 +719,8 @@ def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool
                                 1 if drop_present else 0, rowptr_out.data_ptr(),
                                 _dev(ids_out, torch.int32, "ids_out", 1) if cap else None,
                                 _dev(pay_out, pay_like.dtype, "pay_out", 1) if has and cap else None,
-                                cap, tail.data_ptr(), tail.data_ptr() + 8, _dev(workspace, torch.uint8, "workspace", 1),
-                                workspace.numel(), _stream()), "thr_csr_merge")
+                                cap, tail.data_ptr(), tail.data_ptr() + 8, ws.data_ptr(), nbytes, _stream()),
+           "thr_csr_merge")
     nnz_out, status = (int(v) for v in tail.tolist())
     status &= 0xFFFFFFFF
     if check and status:
@@ -761,37 +736,56 @@ def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = Tr
     is the room for the lists: rowptr is complete either way and the caller compares rowptr[P] with
     cap before it reads ``rows``.  ``rows_out``: an int32 buffer of at least cap entries to write the
     lists into (returned as ``rows``; nothing behind cap is written).  No host read-back."""
-    cols = list(cols)
-    if not 1 <= len(cols) <= THR_SCOPE_MAX_COLS:
-        raise NativeError(f"scope_resolve: 1 .. {THR_SCOPE_MAX_COLS} attribute columns, got {len(cols)}")
-    n = cols[0].shape[0]
-    if any(c.dim() != 1 or c.shape[0] != n for c in cols):
-        raise NativeError("scope_resolve: every column is 1-d of the same length")
+    cols, n = _scope_columns("scope_resolve", cols)
     if preds.dim() != 2 or preds.shape[1] != len(cols):
         raise NativeError(f"scope_resolve: preds must be [P, {len(cols)}]")
     P = preds.shape[0]
     if not 1 <= P <= THR_SCOPE_MAX_PREDS:
         raise NativeError(f"scope_resolve: 1 .. {THR_SCOPE_MAX_PREDS} predicates per call, got {P}")
+    cap = _scope_cap("scope_resolve", cap, n)
+    lib = load()
+    return _scope_call("scope_resolve", lib.thr_scope_resolve, lib.thr_scope_resolve_workspace_bytes, cols, n,
+                       lambda: (_dev(preds, torch.int32, "preds", 2), P), P, cap, want_labels, preds.device, rows_out)
+
+
+def _scope_columns(what: str, cols):
+    """The column checks the two scope calls share, made before any device pointer is taken (they are
+    refused on any device) -> (cols as a list, n_docs)."""
+    cols = list(cols)
+    if not 1 <= len(cols) <= THR_SCOPE_MAX_COLS:
+        raise NativeError(f"{what}: 1 .. {THR_SCOPE_MAX_COLS} attribute columns, got {len(cols)}")
+    n = cols[0].shape[0]
+    if any(c.dim() != 1 or c.shape[0] != n for c in cols):
+        raise NativeError(f"{what}: every column is 1-d of the same length")
+    return cols, n
+
+
+def _scope_cap(what: str, cap: Optional[int], n: int) -> int:
     cap = n if cap is None else int(cap)
     if cap < 0:
-        raise NativeError("scope_resolve: cap is negative")
+        raise NativeError(f"{what}: cap is negative")
+    return cap
+
+
+def _scope_call(what: str, entry, workspace_bytes, cols, n: int, table, P: int, cap: int, want_labels: bool, dev,
+                rows_out=None):
+    """The device half the two scope calls share: column pointers, outputs, workspace and the call of
+    ``entry`` (thr_<what>; ``workspace_bytes`` its size function).  ``table()`` -> the entry's
+    predicate-table arguments (pointers of device tensors and counts), taken behind the columns'."""
     ptrs = (C.c_void_p * len(cols))(*[_dev(c, torch.int32, "column", 1) for c in cols])
-    pp = _dev(preds, torch.int32, "preds", 2)
-    dev = preds.device
+    table = table()
     rowptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
     if rows_out is not None:
         if rows_out.dim() != 1 or rows_out.shape[0] < cap:
-            raise NativeError("scope_resolve: rows_out holds fewer than cap entries")
+            raise NativeError(f"{what}: rows_out holds fewer than cap entries")
         _dev(rows_out, torch.int32, "rows_out", 1)
     rows = torch.empty(cap, dtype=torch.int32, device=dev) if rows_out is None else rows_out
     labels = torch.empty(n, dtype=torch.int32, device=dev) if want_labels else None
     overlap = torch.empty(1, dtype=torch.int32, device=dev) if want_labels else None
-    need = int(load().thr_scope_resolve_workspace_bytes(n, P))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    _check(load().thr_scope_resolve(ptrs, len(cols), n, pp, P, rowptr.data_ptr(), rows.data_ptr() if cap else None,
-                                    cap, labels.data_ptr() if want_labels else None,
-                                    overlap.data_ptr() if want_labels else None, ws.data_ptr(), need, _stream()),
-           "thr_scope_resolve")
+    ws, nbytes = _workspace(None, workspace_bytes(n, P), dev)
+    _check(entry(ptrs, len(cols), n, *table, rowptr.data_ptr(), rows.data_ptr() if cap else None, cap,
+                 labels.data_ptr() if want_labels else None, overlap.data_ptr() if want_labels else None,
+                 ws.data_ptr(), nbytes, _stream()), f"thr_{what}")
     return rowptr, rows, labels, overlap
 
 
@@ -835,51 +829,27 @@ def scope_resolve_clauses(cols, clauses, set_values=None, cap: Optional[int] = N
     """thr_scope_resolve_clauses: scope_resolve over predicates of CLAUSES.  ``clauses`` int32 [P, C, 4]
     and ``set_values`` int32 [n] are HOST numpy arrays: they are validated here (scope_check_clauses:
     the device cannot be asked) and uploaded.  -> scope_resolve's (rowptr, rows, labels, overlap)."""
-    cols = list(cols)
-    if not 1 <= len(cols) <= THR_SCOPE_MAX_COLS:
-        raise NativeError(f"scope_resolve_clauses: 1 .. {THR_SCOPE_MAX_COLS} attribute columns, got {len(cols)}")
-    n = cols[0].shape[0]
-    if any(c.dim() != 1 or c.shape[0] != n for c in cols):
-        raise NativeError("scope_resolve_clauses: every column is 1-d of the same length")
+    cols, n = _scope_columns("scope_resolve_clauses", cols)
     if isinstance(clauses, torch.Tensor) or isinstance(set_values, torch.Tensor):
         raise NativeError("scope_resolve_clauses: the clause table and the set values are host numpy arrays")
     tab, sv = scope_check_clauses(clauses, set_values, len(cols))
     P = tab.shape[0]
-    cap = n if cap is None else int(cap)
-    if cap < 0:
-        raise NativeError("scope_resolve_clauses: cap is negative")
-    ptrs = (C.c_void_p * len(cols))(*[_dev(c, torch.int32, "column", 1) for c in cols])
+    cap = _scope_cap("scope_resolve_clauses", cap, n)
     dev = cols[0].device
     dtab = torch.from_numpy(tab).to(dev)
     dsv = torch.from_numpy(sv).to(dev) if sv.shape[0] else None
-    rowptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
-    rows = torch.empty(cap, dtype=torch.int32, device=dev)
-    labels = torch.empty(n, dtype=torch.int32, device=dev) if want_labels else None
-    overlap = torch.empty(1, dtype=torch.int32, device=dev) if want_labels else None
-    need = int(load().thr_scope_resolve_clauses_workspace_bytes(n, P))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    _check(load().thr_scope_resolve_clauses(ptrs, len(cols), n, dtab.data_ptr(), P,
-                                            dsv.data_ptr() if dsv is not None else None, sv.shape[0],
-                                            rowptr.data_ptr(), rows.data_ptr() if cap else None, cap,
-                                            labels.data_ptr() if want_labels else None,
-                                            overlap.data_ptr() if want_labels else None, ws.data_ptr(), need, _stream()),
-           "thr_scope_resolve_clauses")
-    return rowptr, rows, labels, overlap
+    lib = load()
+    return _scope_call("scope_resolve_clauses", lib.thr_scope_resolve_clauses,
+                       lib.thr_scope_resolve_clauses_workspace_bytes, cols, n,
+                       lambda: (dtab.data_ptr(), P, dsv.data_ptr() if dsv is not None else None, sv.shape[0]), P, cap,
+                       want_labels, dev)
 
 
 def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_base: int = 0):
     """thr_dense_topk_rows: exact cosine top-k of every query over the row list of its scope
     (rowptr i64 [P + 1] / rows i32 of scope_resolve, query_scope i32 [nq] in [0, P), anything else =
     no rows).  -> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
-    pd = _dev(docs, torch.float32, "docs", 2)
-    n, d = docs.shape
-    pq = _dev(queries, torch.float32, "queries", 2)
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise NativeError(f"queries dim {queries.shape[1]} != docs dim {d}")
-    pn = _dev(dnorm, torch.float64, "dnorm", 1)
-    if dnorm.shape[0] != n:
-        raise NativeError("dnorm length != n_docs")
+    pd, pq, pn, _, _, n, d, nq = _dense_operands(docs, queries, dnorm)
     P = rowptr.shape[0] - 1
     if not 1 <= P <= THR_SCOPE_MAX_PREDS:
         raise NativeError(f"dense_topk_rows: 1 .. {THR_SCOPE_MAX_PREDS} scopes")
@@ -890,12 +860,11 @@ def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_
     prp = _dev(rowptr, torch.int64, "rowptr", 1)
     prw = _dev(rows, torch.int32, "rows", 1)
     pqs = _dev(query_scope, torch.int32, "query_scope", 1)
-    need = int(load().thr_dense_topk_rows_workspace_bytes(nq, P, k))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=docs.device)
+    ws, nbytes = _workspace(None, int(load().thr_dense_topk_rows_workspace_bytes(nq, P, k)), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     _check(load().thr_dense_topk_rows(pd, pn, n, d, int(id_base), pq, nq, k, prp, prw if rows.shape[0] else None,
                                       rows.shape[0], P, pqs, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
-                                      flg.data_ptr(), ws.data_ptr(), need, _stream()), "thr_dense_topk_rows")
+                                      flg.data_ptr(), ws.data_ptr(), nbytes, _stream()), "thr_dense_topk_rows")
     return S, I, cnt, flg
 
 
@@ -995,7 +964,7 @@ def bm25_topk(rowptr, post_doc, post_tf, doclen, idf, avgdl: float, query_terms,
               conjunctive: bool = False, doc_coll=None, query_coll=None,
               workspace: Optional[torch.Tensor] = None, dense=None):
     """``dense``: bm25_dense_terms' tuple (needs ``bounds`` with the impacts).
-    ``workspace``: a uint8 device tensor of >= bm25_workspace_bytes(nq, max_terms, k) bytes
+    ``workspace``: a device tensor of >= bm25_workspace_bytes(nq, max_terms, k) bytes
     (item list, slice edges and per-slice lists of the work decomposition); allocated when
     missing or too small."""
     pr = _dev(rowptr, torch.int64, "rowptr", 1)
@@ -1028,23 +997,13 @@ def bm25_topk(rowptr, post_doc, post_tf, doclen, idf, avgdl: float, query_terms,
         pdt, dstride = _dev(dense[2], torch.int16, "dense_tf", 2), int(dense[3])
         if dense[0].shape[0] != idf.shape[0] or dense[1].shape != dense[2].shape or dense[1].shape[1] != dstride:
             raise NativeError("bm25: dense rows are inconsistent")
-    pdc = pqc = None
-    if query_coll is not None:
-        if doc_coll is None:
-            raise NativeError("bm25: query_coll without doc_coll")
-        pdc, pqc = _dev(doc_coll, torch.int32, "doc_coll", 1), _dev(query_coll, torch.int32, "query_coll", 1)
-        if doc_coll.shape[0] != doclen.shape[0] or query_coll.shape[0] != nq:
-            raise NativeError("bm25: doc_coll / query_coll have the wrong length")
+    pdc, pqc = _coll(doc_coll, query_coll, doclen.shape[0], nq)
     S, I, cnt, _ = _alloc_out(nq, k, rowptr.device)
-    need = bm25_workspace_bytes(nq, mt, k)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rowptr.device)
-    pw = _dev(workspace, workspace.dtype, "workspace")
+    ws, nbytes = _workspace(workspace, bm25_workspace_bytes(nq, mt, k), rowptr.device)
     _check(load().thr_bm25_topk(pr, pdoc, ptf, pdl, pidf, ptu, pbu, pim, pds, pdi, pdt, dstride,
                                 avgdl, k1, b, doclen.shape[0],
                                 idf.shape[0], id_base, pqt, nq, mt, k, 1 if conjunctive else 0, pdc,
-                                pqc, S.data_ptr(), I.data_ptr(), cnt.data_ptr(), pw,
-                                workspace.numel() * workspace.element_size(), _stream()),
+                                pqc, S.data_ptr(), I.data_ptr(), cnt.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            "thr_bm25_topk")
     return S, I, cnt
 
@@ -1103,16 +1062,18 @@ def _graph_call(entry, ent_rowptr, ent_col, men_rowptr, men_chunk, men_conf, que
         scoped = (_dev(doc_label, torch.int32, "doc_label", 1), _dev(query_label, torch.int32, "query_label", 1))
         if doc_label.shape[0] != n_chunks or query_label.shape[0] != nq:
             raise NativeError("graph: doc_label holds one label per chunk of the shard, query_label one per query")
-    need = int(load().thr_graph_workspace_bytes(nq, n_ent if transposed is not None else 0))
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=ent_rowptr.device)
+    ws, nbytes = _workspace(workspace, load().thr_graph_workspace_bytes(nq, n_ent if transposed is not None else 0),
+                            ent_rowptr.device)
     S, I, cnt, flg = _alloc_out(nq, k, ent_rowptr.device)
     _check(getattr(load(), entry)(per, pec, n_ent, pmr, pmc, pmw, ptr, pte, ptw, chunk_base, n_chunks, *scoped,
                                   pqs, nq, ms, hops, k, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
-                                  flg.data_ptr(), ws.data_ptr(), need, _stream()),
+                                  flg.data_ptr(), ws.data_ptr(), nbytes, _stream()),
            entry)
     return S, I, cnt, flg
+
+
+def entity_match_workspace_bytes(n_entities: int, n_needles: int, n_queries: int) -> int:
+    return int(load().thr_entity_match_workspace_bytes(n_entities, n_needles, n_queries))
 
 
 def entity_match(name_bytes, name_ptr, needles, needle_len, query_needles, query_per, workspace=None):
@@ -1138,14 +1099,11 @@ def entity_match(name_bytes, name_ptr, needles, needle_len, query_needles, query
         raise NativeError(f"entity_match: 1 .. {THR_ENTITY_MAX_QUERIES} queries per call, got {nq}")
     if n_ent < 1 or not 1 <= M <= THR_ENTITY_MAX_KEYWORDS * nq:
         raise NativeError(f"entity_match: {n_ent} entities, {M} needles for {nq} queries")
-    need = int(load().thr_entity_match_workspace_bytes(n_ent, M, nq))
-    ws = workspace
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=name_bytes.device)
+    ws, nbytes = _workspace(workspace, entity_match_workspace_bytes(n_ent, M, nq), name_bytes.device)
     seeds = torch.empty((nq, THR_GRAPH_MAX_SEEDS), dtype=torch.int32, device=name_bytes.device)
     counts = torch.empty(nq, dtype=torch.int32, device=name_bytes.device)
     _check(load().thr_entity_match(pb, pp, n_ent, pn, pl, M, pq, pr, nq, seeds.data_ptr(), counts.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), _stream()), "thr_entity_match")
+                                   ws.data_ptr(), nbytes, _stream()), "thr_entity_match")
     return seeds, counts
 
 
@@ -1166,6 +1124,18 @@ def vocab_insert(slots, term_bytes, term_ptr, first_id: int, count: int) -> None
 def text_token_capacity(n_texts: int, n_bytes: int) -> int:
     """Token rows that always suffice: a token takes a byte and two tokens of a text a byte between them."""
     return max((n_bytes + n_texts + 1) // 2, 1)
+
+
+def text_tokens_workspace_bytes(n_texts: int, n_bytes: int, token_capacity: int) -> int:
+    return int(load().thr_text_tokens_workspace_bytes(n_texts, n_bytes, token_capacity))
+
+
+def query_terms_workspace_bytes(n_queries: int) -> int:
+    return int(load().thr_query_terms_workspace_bytes(n_queries))
+
+
+def vocab_grow_workspace_bytes(unknown_capacity: int) -> int:
+    return int(load().thr_vocab_grow_workspace_bytes(unknown_capacity))
 
 
 def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, term_ptr, workspace=None,
@@ -1190,11 +1160,8 @@ def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, te
         raise NativeError(f"text_tokens: {n_bytes} bytes (at most {THR_TEXT_MAX_BYTES}) and 4 of padding behind them, "
                           f"the array holds {text_bytes.shape[0]}")
     cap = text_token_capacity(n, n_bytes) if token_capacity is None else int(token_capacity)
-    need = int(load().thr_text_tokens_workspace_bytes(n, n_bytes, cap))
-    ws = workspace
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=text_bytes.device)
     dev = text_bytes.device
+    ws, nbytes = _workspace(workspace, text_tokens_workspace_bytes(n, n_bytes, cap), dev)
     out = dict(doc=torch.empty(cap, dtype=torch.int32, device=dev), term=torch.empty(cap, dtype=torch.int32, device=dev),
                n_tokens=torch.empty(n, dtype=torch.int32, device=dev), flags=torch.empty(n, dtype=torch.int32, device=dev),
                n_total=torch.empty(1, dtype=torch.int32, device=dev),
@@ -1205,7 +1172,7 @@ def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, te
                                   out["doc"].data_ptr(), out["term"].data_ptr(), out["n_tokens"].data_ptr(),
                                   out["flags"].data_ptr(), out["n_total"].data_ptr(), out["unknown_off"].data_ptr(),
                                   out["unknown_len"].data_ptr(), out["n_unknown"].data_ptr(), ws.data_ptr(),
-                                  ws.numel(), _stream()), "thr_text_tokens")
+                                  nbytes, _stream()), "thr_text_tokens")
     return out
 
 
@@ -1214,17 +1181,14 @@ def query_terms(rows: dict, workspace=None):
     [nq, THR_BM25_MAX_TERMS] padded with -1, n_distinct i32 [nq], flags i32 [nq]).  No host read-back."""
     nq = rows["n_tokens"].shape[0]
     dev = rows["term"].device
-    need = int(load().thr_query_terms_workspace_bytes(nq))
-    ws = workspace
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(workspace, query_terms_workspace_bytes(nq), dev)
     terms = torch.empty((nq, THR_BM25_MAX_TERMS), dtype=torch.int32, device=dev)
     nd = torch.empty(nq, dtype=torch.int32, device=dev)
     fl = torch.empty(nq, dtype=torch.int32, device=dev)
     _check(load().thr_query_terms(_dev(rows["term"], torch.int32, "term", 1), _dev(rows["n_tokens"], torch.int32, "n_tokens", 1),
                                   _dev(rows["flags"], torch.int32, "flags", 1), _dev(rows["n_total"], torch.int32, "n_total", 1),
                                   rows["capacity"], nq, terms.data_ptr(), nd.data_ptr(), fl.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), _stream()), "thr_query_terms")
+                                  nbytes, _stream()), "thr_query_terms")
     return terms, nd, fl
 
 
@@ -1257,10 +1221,7 @@ def vocab_grow(text_bytes, text_ptr, n_bytes: int, table, rows: dict, n_unknown:
         raise NativeError("vocab_grow: hash_mask is a non-zero 64-bit mask")
     dev = text_bytes.device
     cap_b = max(int(new_bytes_capacity if new_bytes_capacity is not None else 16 * n_unknown), 0)
-    need = int(load().thr_vocab_grow_workspace_bytes(n_unknown))
-    ws = workspace
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(workspace, vocab_grow_workspace_bytes(n_unknown), dev)
     ptk = pnt = None
     tcap = 0
     if term is not None:
@@ -1277,7 +1238,7 @@ def vocab_grow(text_bytes, text_ptr, n_bytes: int, table, rows: dict, n_unknown:
     _check(load().thr_vocab_grow(pb, pp, n, n_bytes, pt, pf, po, pl, pn, n_unknown, n_vocab, hash_mask, ptk, pnt, tcap,
                                  out["unknown_term"].data_ptr(), out["new_bytes"].data_ptr(), cap_b,
                                  out["new_ptr"].data_ptr(), out["n_new"].data_ptr(), out["n_new_bytes"].data_ptr(),
-                                 out["status"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "thr_vocab_grow")
+                                 out["status"].data_ptr(), ws.data_ptr(), nbytes, _stream()), "thr_vocab_grow")
     return out
 
 
@@ -1309,37 +1270,21 @@ def rrf_check_top_k(what: str, top_k: int) -> None:
 
 def rrf_fuse(lex_ids, sem_ids, graph_ids, top_k: int, w_lex: float = 0.7, w_sem: float = 0.8,
              w_graph: float = 1.0, rrf_k: int = 60, want_ranks: bool = False):
-    rrf_check_top_k("rrf_fuse", top_k)
-    chans = [lex_ids, sem_ids, graph_ids]
-    ref = next(c for c in chans if c is not None)
-    nq = ref.shape[0]
-    ptrs, widths = [], []
-    for name, c in zip(("lex_ids", "sem_ids", "graph_ids"), chans):
-        if c is None:
-            ptrs.append(0)
-            widths.append(0)
-            continue
-        ptrs.append(_dev(c, torch.int64, name, 2))
-        if c.shape[0] != nq or c.shape[1] > THR_RRF_MAX_PER_CHANNEL:
-            raise NativeError(f"rrf: bad shape for {name}")
-        widths.append(c.shape[1])
-    dev = ref.device
-    out_ids = torch.empty((nq, top_k), dtype=torch.int64, device=dev)
-    out_sc = torch.empty((nq, top_k), dtype=torch.float64, device=dev)
-    out_rk = torch.empty((nq, top_k, 3), dtype=torch.int32, device=dev) if want_ranks else None
-    cnt = torch.empty(nq, dtype=torch.int32, device=dev)
-    _check(load().thr_rrf_fuse(ptrs[0], widths[0], ptrs[1], widths[1], ptrs[2], widths[2], nq,
-                               w_lex, w_sem, w_graph, rrf_k, top_k, out_ids.data_ptr(),
-                               out_sc.data_ptr(), out_rk.data_ptr() if want_ranks else 0,
-                               cnt.data_ptr(), _stream()), "thr_rrf_fuse")
-    return out_ids, out_sc, out_rk, cnt
+    return _rrf_call("thr_rrf_fuse", lex_ids, sem_ids, graph_ids, top_k, w_lex, w_sem, w_graph, rrf_k, want_ranks)
 
 
 def rrf_fuse_standalone(lex_ids, sem_ids, graph_ids, top_k: int, w_lex: float = 0.7, w_sem: float = 0.8,
                         w_graph: float = 1.0, two_channels: bool = False, want_ranks: bool = True):
     """The standalone package's RRFFusion.fuse / fuse_two_channels on id lists [nq, n_c] (-1
     padded) -> (ids i64 [nq, top_k], scores f64, ranks i32 [nq, top_k, 3] or None, counts)."""
-    rrf_check_top_k("rrf_fuse_standalone", top_k)
+    return _rrf_call("thr_rrf_fuse_standalone", lex_ids, sem_ids, graph_ids, top_k, w_lex, w_sem, w_graph,
+                     1 if two_channels else 0, want_ranks)
+
+
+def _rrf_call(entry: str, lex_ids, sem_ids, graph_ids, top_k: int, w_lex, w_sem, w_graph, scalar: int, want_ranks: bool):
+    """``entry`` (thr_rrf_fuse / thr_rrf_fuse_standalone) over the three id lists; ``scalar`` is the one
+    argument in which the two differ (rrf_k / the two_channels flag), in the same position."""
+    rrf_check_top_k(entry[4:], top_k)
     chans = [lex_ids, sem_ids, graph_ids]
     ref = next(c for c in chans if c is not None)
     nq = ref.shape[0]
@@ -1358,11 +1303,11 @@ def rrf_fuse_standalone(lex_ids, sem_ids, graph_ids, top_k: int, w_lex: float = 
     out_sc = torch.empty((nq, top_k), dtype=torch.float64, device=dev)
     out_rk = torch.empty((nq, top_k, 3), dtype=torch.int32, device=dev) if want_ranks else None
     cnt = torch.empty(nq, dtype=torch.int32, device=dev)
-    _check(load().thr_rrf_fuse_standalone(ptrs[0], widths[0], ptrs[1], widths[1], ptrs[2], widths[2], nq,
-                                          w_lex, w_sem, w_graph, 1 if two_channels else 0, top_k,
+    _check(getattr(load(), entry)(ptrs[0], widths[0], ptrs[1], widths[1], ptrs[2], widths[2], nq,
+                                          w_lex, w_sem, w_graph, scalar, top_k,
                                           out_ids.data_ptr(), out_sc.data_ptr(),
                                           out_rk.data_ptr() if want_ranks else 0, cnt.data_ptr(),
-                                          _stream()), "thr_rrf_fuse_standalone")
+                                          _stream()), entry)
     return out_ids, out_sc, out_rk, cnt
 
 
@@ -1421,35 +1366,30 @@ def maxsim_pack(dtok: torch.Tensor) -> torch.Tensor:
 def maxsim(qtok: torch.Tensor, dtok: torch.Tensor, cand: torch.Tensor,
            packed: bool = False) -> torch.Tensor:
     """cand holds LOCAL doc indices; negative or out-of-range entries score -inf."""
-    pq = _dev(qtok, torch.float16, "qtok", 3)
-    pdt = _dev(dtok, torch.float16, "dtok", 3)
-    pc = _dev(cand, torch.int32, "cand", 2)
-    nq, qt, td = qtok.shape
-    nd, dt, td2 = dtok.shape
-    if td != td2 or cand.shape[0] != nq:
-        raise NativeError("maxsim: shape mismatch")
-    maxsim_check_tokens("maxsim", td, qt, dt)
-    out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
-    _check(load().thr_maxsim(pq, nq, qt, pdt, nd, dt, td, pc, cand.shape[1], out.data_ptr(),
-                             1 if packed else 0, _stream()), "thr_maxsim")
-    return out
+    return _maxsim_call("thr_maxsim", qtok, dtok, cand, torch.int32, "cand", (), packed)
 
 
 def maxsim_ids(qtok: torch.Tensor, dtok: torch.Tensor, cand_ids: torch.Tensor, id_base: int,
                packed: bool = False) -> torch.Tensor:
     """cand_ids holds GLOBAL doc ids (int64) of a shard starting at ``id_base``; negative ids and
     ids outside the shard score -inf."""
+    return _maxsim_call("thr_maxsim_ids", qtok, dtok, cand_ids, torch.int64, "cand_ids", (int(id_base),), packed)
+
+
+def _maxsim_call(entry: str, qtok, dtok, cand, cand_dtype, cand_name: str, id_base: tuple, packed: bool):
+    """``entry`` (thr_maxsim / thr_maxsim_ids) over candidates of ``cand_dtype``; ``id_base``: the
+    argument thr_maxsim_ids takes behind the candidates, () for thr_maxsim."""
     pq = _dev(qtok, torch.float16, "qtok", 3)
     pdt = _dev(dtok, torch.float16, "dtok", 3)
-    pc = _dev(cand_ids, torch.int64, "cand_ids", 2)
+    pc = _dev(cand, cand_dtype, cand_name, 2)
     nq, qt, td = qtok.shape
     nd, dt, td2 = dtok.shape
-    if td != td2 or cand_ids.shape[0] != nq:
+    if td != td2 or cand.shape[0] != nq:
         raise NativeError("maxsim: shape mismatch")
-    maxsim_check_tokens("maxsim_ids", td, qt, dt)
-    out = torch.empty(cand_ids.shape, dtype=torch.float32, device=qtok.device)
-    _check(load().thr_maxsim_ids(pq, nq, qt, pdt, nd, dt, td, pc, int(id_base), cand_ids.shape[1],
-                                 out.data_ptr(), 1 if packed else 0, _stream()), "thr_maxsim_ids")
+    maxsim_check_tokens(entry[4:], td, qt, dt)
+    out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
+    _check(getattr(load(), entry)(pq, nq, qt, pdt, nd, dt, td, pc, *id_base, cand.shape[1], out.data_ptr(),
+                                  1 if packed else 0, _stream()), entry)
     return out
 
 

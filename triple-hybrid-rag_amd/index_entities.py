@@ -132,12 +132,12 @@ class EntitySearch:
             counts = torch.zeros(nq, dtype=torch.int32, device=self.device)
         else:
             Ent = self.entities
-            need = N.load().thr_entity_match_workspace_bytes(Ent["n"], plan.needles.shape[0], nq)
+            need = N.entity_match_workspace_bytes(Ent["n"], plan.needles.shape[0], nq)
             seeds, counts = N.entity_match(Ent["name_bytes"], Ent["name_ptr"], self._t(plan.needles, torch.uint8),
                                            self._t(plan.needle_len, torch.int32),
                                            self._t(plan.query_needles, torch.int32),
                                            self._t(plan.query_per, torch.int32),
-                                           workspace=self._scratch("_ws_entity", int(need)))
+                                           workspace=self._scratch("_ws_entity", need))
         if plan.long_rows:
             rows = np.full((len(plan.long_rows), N.THR_GRAPH_MAX_SEEDS), -1, dtype=np.int32)
             cnt = np.zeros(len(plan.long_rows), dtype=np.int32)

@@ -363,7 +363,7 @@ class TextSearch:
         n_bytes = int(rows["ptr"][-1])
         room = min(3 * n_bytes // 2 + 16, 16 * n_unknown)
         mask = (1 << 64) - 1 if hash_mask is None else int(hash_mask)
-        need = int(N.load().thr_vocab_grow_workspace_bytes(n_unknown))
+        need = N.vocab_grow_workspace_bytes(n_unknown)
         patch = term
         while True:
             out = N.vocab_grow(rows["bytes_dev"], rows["ptr_dev"], n_bytes, X["table_dev"], rows, n_unknown, n_before,
@@ -414,7 +414,7 @@ class TextSearch:
         blob, ptr = packed if packed is not None else pack_texts(texts)
         n_bytes = int(ptr[-1])
         cap = N.text_token_capacity(len(texts), n_bytes)
-        need = int(N.load().thr_text_tokens_workspace_bytes(len(texts), n_bytes, cap))
+        need = N.text_tokens_workspace_bytes(len(texts), n_bytes, cap)
         bytes_dev, ptr_dev = self._t(blob, torch.uint8), self._t(ptr, torch.int64)
         rows = N.text_tokens(bytes_dev, ptr_dev, n_bytes, X["table_dev"], X["slots"],
                              X["term_bytes"], X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)))
@@ -439,7 +439,7 @@ class TextSearch:
                     torch.empty(0, dtype=torch.int32, device=self.device))
         X = self.text
         rows = self._text_tokens(texts)
-        need = int(N.load().thr_query_terms_workspace_bytes(nq))
+        need = N.query_terms_workspace_bytes(nq)
         terms, _, flags = N.query_terms(rows, workspace=self._scratch("_ws_qterms", max(need, 8)))
         redo = X["table"].exceptional_among(texts)
         if redo:
