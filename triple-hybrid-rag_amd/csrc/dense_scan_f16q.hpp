@@ -43,6 +43,7 @@
 // (cand_cnt[q * nseg + s] entries each).
 #pragma once
 #include "dense_common.hpp"
+#include "dense_tile_schedule.hpp"
 
 namespace thr {
 
@@ -400,6 +401,21 @@ __device__ __forceinline__ void qsx_steps_pe(f32x4 (&a)[RING], const f32x4 (&bq)
         qsx_steps_pe<S + 1, HS, K0, KS, PER, SHAPE, HF, RING, NBQ, COLL>(a, bq, acc, abase, issue_piece, em, prv, row_prv, lane);
     }
 }
+// The k-loop of a WHOLE row tile (dense_scan_f16qs): qsx_steps over all KS pieces, with the PB row
+// pieces an issuing wave sends threaded into its first steps (tsched::issue_step; PB = 0: none).
+template <int S, int KS, int PB, int SHAPE, int RING, int NBQ, typename Issue>
+__device__ __forceinline__ void qst_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
+                                          uint32_t abase, Issue& issue_piece) {
+    if constexpr (S < KS) {
+        constexpr int left = KS - S - 1 < RING - 1 ? KS - S - 1 : RING - 1;
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[S % RING]) : "n"(left) : "memory");
+        qsx_mfma<S, 0, KS, SHAPE>(a[S % RING], bq, acc);
+        if constexpr (S + RING < KS) QS_RD(a[S % RING], S + RING);
+        constexpr int p = (S - 1) / 2;
+        if constexpr (S >= 1 && p < PB && tsched::issue_step(p) == S) issue_piece(std::integral_constant<int, p>{});
+        qst_steps<S + 1, KS, PB, SHAPE, RING, NBQ>(a, bq, acc, abase, issue_piece);
+    }
+}
 #undef QS_RD
 
 // PROF: diagnostic build (thr_dense_scan_stamps_f16): s_memtime stamps around the phases of the
@@ -663,36 +679,43 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
 
 // ---------------------------------------------------------------------------------------------
 // dense_scan_f16qs: the same scan with ONE 8-wave block per CU (256 queries) whose two wave groups
-// run STAGGERED by half a tile -- the default at dim <= 768.
+// run STAGGERED inside one interval per row tile -- the default at dim <= 768.
 //
 // What the counters of the two-blocks-per-CU kernel above said (profiles/r2_scan_v2_*.json): pipe
 // 64 % busy; the older block of a CU wins the matrix pipe and retires when 3/4 of the launch is
 // over, so the pipe is half empty for the last quarter; every CU pulls each tile twice; and the
-// chip drops its clock to 1.5-1.7 GHz under the load.  Here the 8 waves share each half tile
-// (half the DMA pieces and L2 bytes per flop) and are kept in step by one barrier per half tile,
-// but group B (waves 4-7, the younger wave of each SIMD) works one half tile behind group A:
+// chip drops its clock to 1.5-1.7 GHz under the load.  Here the 8 waves share each row tile
+// (half the DMA pieces and L2 bytes per flop) and are kept in step by ONE barrier per tile; both
+// groups multiply the same tile, and the stagger is the order inside the interval:
 //
-//     interval k       A (waves 0-3)                        B (waves 4-7)
-//     k = 2i           MFMA half 2i   (k-steps 0..HS)       MFMA half 2i-1 (second half of tile i-1)
-//     k = 2i+1         MFMA half 2i+1, then EMIT tile i     EMIT tile i-1, then MFMA half 2i
+//     interval t       A (waves 0-3)                        B (waves 4-7)
+//                      MFMA tile t, then EMIT tile t        EMIT tile t-1, then MFMA tile t
 //
 // so an emit always runs under the other group's MFMAs (A is the older wave of the SIMD and gets
 // the pipe first: its MFMAs cover B's emit at the start of the interval, B's cover A's at the
-// end), and B -- whose half tile was published one barrier earlier -- has its first fragments in
-// registers before the barrier opens, which covers A's LDS latency after it.
-// Barrier k: every wave has waited for its own pieces of half tile k (3 younger half tiles'
-// pieces stay in flight); afterwards A is done with half k-1 and B with half k-2, so half k-2's
-// buffer takes the pieces of half k+4: ring of 6 half-tile buffers (144 KiB at dim 768).
+// end).  B keeps tile t-1's accumulators across the barrier: there is one accumulator set.
+// The index arithmetic -- ring of whole-tile buffers, who issues what into which buffer, what the
+// counted wait leaves in flight, barriers per role -- is tsched:: (dense_tile_schedule.hpp), which
+// tests/native/dense_tile_schedule_host_check.cpp replays on the host.
+//
+// Only group B issues row pieces, and only group B waits before a barrier.  vmcnt counts loads,
+// stores and LDS-DMA in issue order.  B's emit stores of interval t are issued BEFORE its pieces
+// of interval t, so at the wait before barrier t+1 -- s_waitcnt vmcnt((nbuf-2) * PB) -- the PB
+// youngest operations per tile left in flight are pieces, never that interval's stores: the wait
+// retires tile t+1's pieces (older than the stores) and the stores themselves, which were issued
+// a whole multiply earlier.  A's stores are never waited for inside the loop: A issues no piece,
+// so it has nothing to wait for, and its LDS reads have all returned into its MFMAs by then.
 // ---------------------------------------------------------------------------------------------
-constexpr int QS_NW = 8;
-constexpr int QS_NBUF = 6;
+constexpr int QS_NW = tsched::N_WAVES;
 
 template <int DIM>
 struct QStag {
-    static constexpr int KS = DIM / 16, HS = KS / 2, HALF_BYTES = HS * 1024;
-    static constexpr int PER = HS / QS_NW;               // pieces a wave issues per half tile
-    static constexpr int LDS_BYTES = QS_NBUF * HALF_BYTES;
-    static_assert(HS % QS_NW == 0 && LDS_BYTES <= 160 * 1024, "dim 512 / 768 only");
+    static constexpr int KS = tsched::pieces_per_tile(DIM), TILE_BYTES = tsched::tile_bytes(DIM);
+    static constexpr int NBUF = tsched::nbuf(DIM);
+    static constexpr int PB = tsched::pieces_issued(tsched::ROLE_B, DIM);   // pieces an issuing wave sends per tile
+    static constexpr int LDS_BYTES = NBUF * TILE_BYTES;
+    static_assert(KS % tsched::N_ISSUERS == 0 && NBUF >= 3 && LDS_BYTES <= tsched::LDS_BUDGET, "dim 512 / 768 only");
+    static_assert(tsched::wait_leaves(tsched::ROLE_B, DIM) < 64 && tsched::issue_step(PB - 1) < KS, "vmcnt is 6 bits");
 };
 
 template <int DIM, int MODE, int SHAPE = 32, bool COLL = true>
@@ -704,8 +727,8 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries) {
     using C = QStag<DIM>;
     using A = QAcc<SHAPE>;
-    constexpr int KS = C::KS, HS = C::HS, PER = C::PER, NBUF = QS_NBUF, NQL = A::NQL;
-    extern __shared__ f32x4 lds_rows[];  // 6 half-tile buffers
+    constexpr int KS = C::KS, PB = C::PB, NQL = A::NQL;
+    extern __shared__ f32x4 lds_rows[];  // NBUF whole-tile buffers
 
     const ScanSlot slot = scan_slot(n_qtiles);
     const int lane = threadIdx.x & 63;
@@ -740,20 +763,22 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // retire these loads visibly to hipcc (see dense_scan_f16q)
 
+    namespace ts = tsched;
     const int64_t first = slot.slice, step = slot.nslices;
     const int64_t n_mine = first < n_tiles ? (n_tiles - first + step - 1) / step : 0;
-    const int64_t n_half = 2 * n_mine;
     const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)lds_rows;
+    const ts::Role role = ts::role_of(wave, (int64_t)q32 * 32 >= n_queries);
+    const int iw = wave & (ts::N_ISSUERS - 1);   // an issuing wave's place among the issuers
+    // this wave's pieces of the block's j-th tile (past the end: the last tile again, never read)
     auto piece_src = [&](int64_t j) -> const f32x4* {
-        const int64_t jc = j < n_half ? j : n_half - 1;  // past the end: the last half again (never read)
-        const int64_t t = first + (jc >> 1) * step;
-        return packed + ((t * tile_stride * KS + (jc & 1) * HS + wave) * 64 + lane);
+        const int64_t t = first + ts::source_tile(j, n_mine) * step;
+        return packed + ((t * tile_stride * KS + iw) * 64 + lane);
     };
     auto dma = [&](const f32x4* src, int buf, int p) {
         __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(src + p * QS_NW * 64),
-            (__attribute__((address_space(3))) void*)(size_t)(lds_base + buf * C::HALF_BYTES +
-                                                              (wave + p * QS_NW) * 1024),
+            (const __attribute__((address_space(1))) void*)(src + (ts::piece_index(iw, p) - iw) * 64),
+            (__attribute__((address_space(3))) void*)(size_t)(lds_base + buf * C::TILE_BYTES +
+                                                              ts::piece_index(iw, p) * 1024),
             16, 0, 0);
     };
 #define QS_EMIT(i_)                                                                                \
@@ -762,119 +787,84 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     } else {                                                                                       \
         em.template all<0>(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32), lane);       \
     }
-    // barrier k: own pieces of half k have landed (3 younger halves' pieces may stay in flight)
-#define QS_SYNC()                                                      \
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory");     \
+    // barrier t of an issuing wave: its own pieces of tile t have landed; the pieces of the
+    // nbuf - 2 younger tiles stay in flight, and the emit stores of the interval that ends here
+    // are older than the youngest of them (see above), so they are not what the count leaves out
+    constexpr int WAIT_B = ts::wait_leaves(ts::ROLE_B, DIM);
+    static_assert(WAIT_B == ts::wait_leaves(ts::ROLE_PAD_B, DIM) && ts::pieces_issued(ts::ROLE_PAD_B, DIM) == PB &&
+                  ts::pieces_issued(ts::ROLE_A, DIM) == 0 && ts::pieces_issued(ts::ROLE_PAD_A, DIM) == 0,
+                  "a padding wave moves what a working wave of its group moves");
+#define QS_SYNC_B()                                                    \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_B) : "memory");      \
     __builtin_amdgcn_s_barrier();
 
-    if (n_half > 0) {
+    if (ts::issues(role) && n_mine > 0) {
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
+        for (int b = 0; b < ts::prologue_tiles(DIM); ++b) {
             const f32x4* src = piece_src(b);
 #pragma unroll
-            for (int p = 0; p < PER; ++p) dma(src, b, p);
+            for (int p = 0; p < PB; ++p) dma(src, ts::buffer_of(b, DIM), p);
         }
     }
     A acc;
     f32x4 a[Q_RING];
-    if ((int64_t)q32 * 32 >= n_queries) {
+    auto no_piece = [](auto) {};
+    if (!ts::multiplies(role)) {
         // ---- a wave whose 32 queries are all padding (small batches: one query keeps 7 of the 8
-        // waves here): it only moves its share of the row pieces -- same barriers, same DMA order
-        // and wait counts as a working wave, no LDS reads, no MFMAs, nothing to emit.  A launch
-        // with one live wave per CU is bound by the row stream alone. ----
-        int buf = wave < 4 ? 4 : 5;   // buffer of the next half this wave issues
-        int64_t j = wave < 4 ? 4 : 5;
-        if (wave >= 4) {
-            QS_SYNC()  // barrier 0
-            if (n_half > 0) {
-                const f32x4* src = piece_src(4);
-#pragma unroll
-                for (int p = 0; p < PER; ++p) dma(src, 4, p);
-            }
-        }
+        // waves here): same barriers as a working wave of its group, and for an issuer the same
+        // DMA order and wait counts; no LDS reads, no MFMAs, nothing to emit.  A launch with one
+        // live wave per CU is bound by the row stream alone. ----
+        if (ts::issues(role)) {
+            int ibuf = ts::buffer_of(ts::issue_tile(0, DIM), DIM);
 #pragma unroll 1
-        for (int64_t k = 0; k < n_half; ++k, ++j) {
-            QS_SYNC()   // A: barrier k, then half k + 4;  B: barrier k + 1, then half k + 5
-            const f32x4* src = piece_src(j);
+            for (int64_t t = 0; t < ts::barriers(ts::ROLE_PAD_B, n_mine); ++t) {
+                QS_SYNC_B()   // barrier t, then tile t + nbuf - 1 into tile t - 1's buffer
+                const f32x4* src = piece_src(ts::issue_tile(t, DIM));
 #pragma unroll
-            for (int p = 0; p < PER; ++p) dma(src, buf, p);
-            buf = buf + 1 == NBUF ? 0 : buf + 1;
-        }
-        if (wave < 4) {
-            QS_SYNC()  // barrier 2n
-        }
-    } else if (wave < 4) {
-        // ---- group A: half k in interval k ----
-        int buf = 0;
+                for (int p = 0; p < PB; ++p) dma(src, ibuf, p);
+                ibuf = ts::next_buffer(ibuf, DIM);
+            }
+        } else {
 #pragma unroll 1
-        for (int64_t i = 0; i < n_mine; ++i) {
-            {
-                QS_SYNC()  // barrier 2i
-                const int nbuf = buf + 4 >= NBUF ? buf + 4 - NBUF : buf + 4;
-                const f32x4* src = piece_src(2 * i + 4);
-                auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };
-                const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;
-                qs_fill<0, HS>(a, abase);
-                acc.zero();
-                qsx_steps<0, HS, 0, KS, PER, SHAPE>(a, bq, acc, abase, issue_piece);
-                buf = buf + 1 == NBUF ? 0 : buf + 1;
-            }
-            {
-                QS_SYNC()  // barrier 2i+1
-                const int nbuf = buf + 4 >= NBUF ? buf + 4 - NBUF : buf + 4;
-                const f32x4* src = piece_src(2 * i + 5);
-                auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };
-                const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;
-                qs_fill<0, HS>(a, abase);
-                qsx_steps<0, HS, HS, KS, PER, SHAPE>(a, bq, acc, abase, issue_piece);
-                buf = buf + 1 == NBUF ? 0 : buf + 1;
-            }
+            for (int64_t t = 0; t < ts::barriers(ts::ROLE_PAD_A, n_mine); ++t) __builtin_amdgcn_s_barrier();
+        }
+    } else if (role == ts::ROLE_A) {
+        // ---- group A: multiply tile t, then emit it (under B's MFMAs) ----
+        int buf = 0;   // buffer of tile i
+#pragma unroll 1
+        for (int64_t i = 0; i < ts::barriers(ts::ROLE_A, n_mine); ++i) {
+            __builtin_amdgcn_s_barrier();   // barrier i
+            const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
+            qs_fill<0, KS>(a, abase);
+            acc.zero();
+            qst_steps<0, KS, 0, SHAPE>(a, bq, acc, abase, no_piece);
+            buf = ts::next_buffer(buf, DIM);
             QS_EMIT(i)
         }
-        QS_SYNC()  // barrier 2n: B's last interval
     } else {
-        // ---- group B: half k-1 in interval k ----
-        QS_SYNC()  // barrier 0: nothing to multiply yet
-        if (n_half > 0) {
-            const f32x4* src = piece_src(4);
-#pragma unroll
-            for (int p = 0; p < PER; ++p) dma(src, 4, p);
-        }
-        int buf = 0;  // buffer of half 2i
+        // ---- group B: emit tile t - 1 (under A's MFMAs), then multiply tile t and request tile
+        // t + nbuf - 1 in the first steps of it ----
+        int buf = 0;   // buffer of tile i
 #pragma unroll 1
-        for (int64_t i = 0; i < n_mine; ++i) {
-            const int buf1 = buf + 1 == NBUF ? 0 : buf + 1;       // half 2i+1
-            const int buf2 = buf1 + 1 == NBUF ? 0 : buf1 + 1;     // half 2i+2
-            {
-                QS_SYNC()  // barrier 2i+1
-                if (i > 0) {
-                    QS_EMIT(i - 1)
-                }
-                const int nbuf = buf + 5 >= NBUF ? buf + 5 - NBUF : buf + 5;   // half 2i+5
-                const f32x4* src = piece_src(2 * i + 5);
-                auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };
-                const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;
-                if (i == 0) qs_fill<0, HS>(a, abase);   // later trips: filled before the barrier
-                acc.zero();
-                qsx_steps<0, HS, 0, KS, PER, SHAPE>(a, bq, acc, abase, issue_piece);
-                qs_fill<0, HS>(a, lds_base + buf1 * C::HALF_BYTES + lane * 16);   // half 2i+1: published at this barrier
+        for (int64_t i = 0; i < ts::barriers(ts::ROLE_B, n_mine); ++i) {
+            QS_SYNC_B()   // barrier i
+            if (i > 0) {
+                QS_EMIT(i - 1)
             }
-            {
-                QS_SYNC()  // barrier 2i+2
-                const f32x4* src = piece_src(2 * i + 6);   // into half 2i's buffer, which this group just left
-                auto issue_piece = [&](auto P) { dma(src, buf, decltype(P)::value); };
-                const uint32_t abase = lds_base + buf1 * C::HALF_BYTES + lane * 16;
-                qsx_steps<0, HS, HS, KS, PER, SHAPE>(a, bq, acc, abase, issue_piece);
-                if (i + 1 < n_mine)
-                    qs_fill<0, HS>(a, lds_base + buf2 * C::HALF_BYTES + lane * 16);   // half 2i+2: published at this barrier
-            }
-            buf = buf2;
+            const int ibuf = ts::prev_buffer(buf, DIM);   // tile i - 1's buffer
+            const f32x4* src = piece_src(ts::issue_tile(i, DIM));
+            auto issue_piece = [&](auto P) { dma(src, ibuf, decltype(P)::value); };
+            const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
+            qs_fill<0, KS>(a, abase);
+            acc.zero();
+            qst_steps<0, KS, PB, SHAPE>(a, bq, acc, abase, issue_piece);
+            buf = ts::next_buffer(buf, DIM);
         }
         if (n_mine > 0) {
             QS_EMIT(n_mine - 1)
         }
     }
-#undef QS_SYNC
+#undef QS_SYNC_B
 #undef QS_EMIT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing may still be landing in LDS
     if constexpr (MODE == MODE_FILTER) {
