@@ -29,7 +29,7 @@
 // Accumulation: one fp32 accumulator per (row, query) through all dim / 32 steps -- a dim-long fp32
 // chain and nothing narrower, which is what scan_eps(dim) bounds.
 #pragma once
-#include "dense_common.hpp"
+#include "dense_scan_tilelist.hpp"
 
 namespace thr {
 
@@ -59,6 +59,8 @@ __global__ __launch_bounds__(AD_THREADS) void dense_scan_anydim(
     f32x4* lds_v = reinterpret_cast<f32x4*>(lds_q);
     Cand* wbuf = reinterpret_cast<Cand*>(lds_q + (size_t)cpr * QT) + wave * WBUF;
     int wcnt = 0;
+    // (tilelist_flush<false> of dense_scan_tilelist.hpp written out: through the function the
+    // MODE_FILTER kernels gain two instructions.  No drain after the copy: see there.)
     auto flush = [&]() {
         int base = 0;
         if (lane == 0) base = atomicAdd(&tile_cnt[qtile], wcnt);
@@ -88,12 +90,12 @@ __global__ __launch_bounds__(AD_THREADS) void dense_scan_anydim(
     if (wave_id >= n_tiles) return;   // (wave-uniform; no barrier follows)
 
     float my_tau[NB];
-    int my_qc[NB];   // collection filter of the lane's queries (-1: none), applied as rows pass tau
+    int my_qc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int qg = qtile * QT + 16 * nb + fr;
-        my_tau[nb] = MODE == MODE_FILTER ? tau[qg] : 0.f;
-        my_qc[nb] = (MODE == MODE_FILTER && query_coll && qg < n_queries) ? query_coll[qg] : -1;
+        my_tau[nb] = lane_tau<MODE>(tau, qg);
+        my_qc[nb] = lane_coll<MODE>(query_coll, qg, n_queries);
     }
 
     const f32x4* docs4 = reinterpret_cast<const f32x4*>(docs);
@@ -176,15 +178,7 @@ __global__ __launch_bounds__(AD_THREADS) void dense_scan_anydim(
                         const float sc = acc[af][nb][j] * inv[j];
                         bool pass = ok[j] && sc >= my_tau[nb];
                         if (pass && my_qc[nb] != -1 && doc_coll[row0 + row] != my_qc[nb]) pass = false;
-                        const uint64_t m = __ballot(pass);
-                        if (m) {
-                            const int pos = wcnt + __popcll(m & ((1ull << lane) - 1ull));
-                            if (pass)
-                                wbuf[pos] = Cand{sc, ((uint32_t)(16 * nb + fr) << ROW_BITS_F16) |
-                                                         (uint32_t)(row0 + row)};
-                            wcnt += __popcll(m);
-                            if (wcnt > WBUF - WAVE) flush();
-                        }
+                        THR_TILELIST_PUSH(pass, sc, ((uint32_t)(16 * nb + fr) << ROW_BITS_F16) | (uint32_t)(row0 + row))
                     }
                 }
             }

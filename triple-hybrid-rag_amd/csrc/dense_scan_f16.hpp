@@ -1,11 +1,11 @@
 // Shortlist scan on the f16 matrix cores over the float32 rows themselves
 // (thr_dense_topk_f16 with docs16 == NULL): the rows are rounded to float16 in registers on the
-// way into the LDS transpose tile -- no second copy of the corpus.  (The flavour that streams a
-// float16 copy is dense_scan_f16p.hpp: fragment-major copy, no LDS transpose.)
+// way into the LDS transpose tile -- no second copy of the corpus.  (The flavours that stream a
+// float16 copy are in dense_scan_f16q.hpp: fragment-major copy, no LDS transpose.)
 //
 // The float32 corpus stays the source of truth: every returned score is the float64
 // rescoring of float32 rows, and the top-k is certified with an error bound that also covers
-// the quantisation of rows and queries (see select_rescore / DESIGN.md 4.1):
+// the quantisation of rows and queries (see select_band / DESIGN.md 4.1):
 //     |fp16-scan score - true cosine| <= ea*(1+eq) + eq + eps32        (relative to 1)
 //   ea = max over rows of ||d16 - d|| / ||d||   (measured at index build, thr_dense_quantize_f16)
 //   eq = ||q16 - q|| / ||q||                    (measured per query in kth_select)
@@ -16,7 +16,7 @@
 // 64 dims and ONE v_mfma_f32_32x32x16_f16 per 16-byte fragment pair; 64 queries per pass (96 KiB
 // of LDS as f16) at dim <= 768, 32 at dim 1024.
 #pragma once
-#include "dense_common.hpp"
+#include "dense_scan_tilelist.hpp"
 
 namespace thr {
 
@@ -55,15 +55,7 @@ __global__ __launch_bounds__(H_THREADS) void dense_scan_f16(
     f32x4* stage = lds_v + QT * CPR + wave * MF2_STAGE_F4;
     Cand* wbuf = reinterpret_cast<Cand*>(lds_q + QT * CPR + H_WAVES * MF2_STAGE_F4) + wave * WBUF;
     int wcnt = 0;
-    auto flush = [&]() {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&tile_cnt[qtile], wcnt);
-        base = __shfl(base, 0, WAVE);
-        for (int i = lane; i < wcnt; i += WAVE)
-            if (base + i < tile_cap) tile_list[(int64_t)qtile * tile_cap + base + i] = wbuf[i];
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        wcnt = 0;
-    };
+    auto flush = [&]() { tilelist_flush<true>(wbuf, wcnt, lane, qtile, tile_cnt, tile_list, tile_cap); };
 
     // query tile: float32 -> float16 (round to nearest even), swizzled like the f32 kernels
     for (int i = threadIdx.x; i < QT * CPR; i += H_THREADS) {
@@ -87,25 +79,19 @@ __global__ __launch_bounds__(H_THREADS) void dense_scan_f16(
     __syncthreads();
 
     float my_tau[NQ];
-    int my_qc[NQ];   // collection filter of the lane's queries (-1: none), applied as rows pass tau
+    int my_qc[NQ];
 #pragma unroll
     for (int s = 0; s < NQ; ++s) {
-        my_tau[s] = MODE == MODE_FILTER ? tau[qtile * QT + 32 * s + r] : 0.f;
-        my_qc[s] = (MODE == MODE_FILTER && query_coll && qtile * QT + 32 * s + r < n_queries)
-                       ? query_coll[qtile * QT + 32 * s + r] : -1;
+        my_tau[s] = lane_tau<MODE>(tau, qtile * QT + 32 * s + r);
+        my_qc[s] = lane_coll<MODE>(query_coll, qtile * QT + 32 * s + r, n_queries);
     }
     const int64_t wave_id = (int64_t)slot.slice * H_WAVES + wave;
     const int64_t wave_stride = (int64_t)slot.nslices * H_WAVES;
     const f32x4* docs4 = reinterpret_cast<const f32x4*>(docs16);
 
-    const int lrow = lane >> 3, lchunk = lane & 7;
-    auto load_off = [&](int64_t t, int i) -> int64_t {
-        int64_t row = t * tile_stride * MF_ROWS + lrow + 8 * i;
-        row = row < n_docs ? row : n_docs - 1;
-        return row * GPR + lchunk;
-    };
-    int wslot0 = mf2_slot(lrow, lchunk), wslot1 = mf2_slot(lrow + 8, lchunk);
-    int wslot2 = mf2_slot(lrow + 16, lchunk), wslot3 = mf2_slot(lrow + 24, lchunk);
+    auto load_off = [&](int64_t t, int i) -> int64_t { return loader_off(t, i, lane, tile_stride, n_docs, GPR); };
+    int wslot0 = loader_wslot(lane, 0), wslot1 = loader_wslot(lane, 1);
+    int wslot2 = loader_wslot(lane, 2), wslot3 = loader_wslot(lane, 3);
     const uint32_t q_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)lds_v;
     const uint32_t st_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)stage;
     // byte addresses: A fragment of quad j in the stage tile; query row bases of the sub-tiles
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(H_THREADS) void dense_scan_f16(
     for (int s = 0; s < NQ; ++s) qrow[s] = q_lds + (uint32_t)((32 * s + r) * CPR) * 16u;
     int qlow[8];
 #pragma unroll
-    for (int x = 0; x < 8; ++x) qlow[x] = (((x >> 2) * 8 + 2 * (x & 3) + h) ^ r) & 15;
+    for (int x = 0; x < 8; ++x) qlow[x] = query_low_chunk(x, r, h);
 
 #define THR_PIN(x) asm volatile("" : "+v"(x))
 #define HS_LD(ptr) (nt_loads ? __builtin_nontemporal_load(&docs4[ptr]) : docs4[ptr])
@@ -241,15 +227,7 @@ __global__ __launch_bounds__(H_THREADS) void dense_scan_f16(
                 } else {
                     bool pass = ok && inv > 0.f && sc >= my_tau[s];
                     if (pass && my_qc[s] != -1 && doc_coll[row0 + row] != my_qc[s]) pass = false;
-                    const uint64_t m = __ballot(pass);
-                    if (m) {
-                        const int pos = wcnt + __popcll(m & ((1ull << lane) - 1ull));
-                        if (pass)
-                            wbuf[pos] = Cand{sc, ((uint32_t)(32 * s + r) << ROW_BITS_F16) |
-                                                     (uint32_t)(row0 + row)};
-                        wcnt += __popcll(m);
-                        if (wcnt > WBUF - WAVE) flush();
-                    }
+                    THR_TILELIST_PUSH(pass, sc, ((uint32_t)(32 * s + r) << ROW_BITS_F16) | (uint32_t)(row0 + row))
                 }
             }
         }

@@ -1,7 +1,8 @@
 // Dense scan over the normalised float16 copy, queries in registers (the default): dense_scan_f16qs
 // and dense_scan_f16q (dense_scan_f16q.hpp) with their launcher, and the kernels that write what
-// they read -- pack_queries_f16 (the query image), quantize_f16_norm / measure_f16_error (the copy
-// and its rounding error).
+// they read (dense_f16_image.hpp) -- pack_queries_f16 (the query image), quantize_f16_norm /
+// measure_f16_error (the copy and its rounding error).
+#include "dense_f16_image.hpp"
 #include "dense_scan_f16q.hpp"
 
 namespace thr {
@@ -16,7 +17,7 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
     bool shared_rows = false;
     const bool stag = qreg_staggered(dim);
     // a lane's candidate segment is (row slice, row half): at most 256 slices (512 segments, two
-    // per thread of select_rescore) -- enough for one block per CU when the batch is a single
+    // per thread of select_band) -- enough for one block per CU when the batch is a single
     // workgroup tile of queries
     const dim3 grid = scan_grid(n_qtiles, n_row_tiles, 1, &shared_rows, (!stag && dim <= 768) ? 2 : 1, 32);
     const int shape = qreg_shape(dim);

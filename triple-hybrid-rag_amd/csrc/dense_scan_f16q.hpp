@@ -1,9 +1,9 @@
 // Shortlist scan with the QUERIES in registers and the ROWS shared through LDS
 // (thr_dense_topk_f16 over the fragment-major float16 copy; the default f16 scan since round 2).
-// Two kernels share the pieces below (QAcc / qsx_steps / QEmit: the MFMA shape, the k-loop of a
-// half tile, the per-lane segment emit): dense_scan_f16q, described first -- 4-wave blocks, the
-// kernel of dim 1024 -- and dense_scan_f16qs further down, the staggered 8-wave block that is
-// the default at dim <= 768.
+// Two kernels share the pieces below (QAcc / qs_steps / QEmit / QTop / QS_WAVE_*: the MFMA shape, the
+// k-loop, the per-lane segment emit, the sample keep, the wave's set-up and write-out):
+// dense_scan_f16q, described first -- 4-wave blocks, the kernel of dim 1024 -- and
+// dense_scan_f16qs further down, the staggered 8-wave block that is the default at dim <= 768.
 //
 // Why (profiles/README.md, round 2): the round-1 kernel (dense_scan_f16p) kept 96 queries in
 // LDS and let every wave stream its own rows from L2 -- 8 KiB of row fragments per 24 MFMAs and
@@ -71,94 +71,6 @@ struct QScan {
 #endif
     static_assert(HS % Q_NW == 0 && NB >= 3, "half tile must split evenly over the waves; >= 3 buffers");
 };
-
-// queries float32 [n, DIM] -> fragment-major float16 image [qpad/32][KS][64 lanes][8 halves]
-// (lane (c, h) of k-step s holds dims 16 s + 8 h .. + 8 of query 32 tile + c: the B operand of
-// v_mfma_f32_32x32x16_f16), zeros for padding queries, plus
-// qerr[q] = ||fp16(q) - q|| / ||q|| rounded up (the query-side term of the f16 certificate).
-// One wave per 32 queries.
-template <int DIM, int SHAPE>
-__global__ __launch_bounds__(256) void pack_queries_f16(const float* __restrict__ queries,
-                                                        int n_queries, f32x4* __restrict__ qfrag,
-                                                        float* __restrict__ qerr) {
-    constexpr int KS = DIM / 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ double red[4][4][32];   // [wave][e, n of query half 0 | e, n of half 1][c]
-    double e = 0.0, nn = 0.0, e_hi = 0.0, n_hi = 0.0;
-    // SHAPE 32: lane (c, h) of fragment s holds dims 16 s + 8 h .. + 8 of query 32 tile + c.
-    // SHAPE 16: fragment qb * KS/2 + k32, lane (c, g) holds dims 32 k32 + 8 g .. + 8 of query
-    //           32 tile + 16 qb + c (the B operand of v_mfma_f32_16x16x32_f16).
-    // The 4 waves of the block take every fourth fragment.
-#pragma unroll 4
-    for (int s = wave; s < KS; s += 4) {
-        int q, d0;
-        if constexpr (SHAPE == 32) {
-            q = blockIdx.x * 32 + (lane & 31);
-            d0 = 16 * s + 8 * (lane >> 5);
-        } else {
-            q = blockIdx.x * 32 + 16 * (s / (KS / 2)) + (lane & 15);
-            d0 = 32 * (s % (KS / 2)) + 8 * (lane >> 4);
-        }
-        f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
-        if (q < n_queries) {
-            const f32x4* src = reinterpret_cast<const f32x4*>(queries + (int64_t)q * DIM + d0);
-            lo = src[0];
-            hi = src[1];
-        }
-        const f32x4 packed = pack_f16x8(lo, hi);
-        qfrag[((int64_t)blockIdx.x * KS + s) * 64 + lane] = packed;
-        const half8 hv = __builtin_bit_cast(half8, packed);
-        double e1 = 0.0, n1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = j < 4 ? lo[j] : hi[j - 4];
-            const double d = (double)v - (double)(float)hv[j];
-            e1 += d * d;
-            n1 += (double)v * (double)v;
-        }
-        if (SHAPE == 32 || s < KS / 2) {
-            e += e1;
-            nn += n1;
-        } else {   // SHAPE 16, second query half (16 + c)
-            e_hi += e1;
-            n_hi += n1;
-        }
-    }
-    // eq = ||fp16(q) - q|| / ||q||, rounded up: lanes of one query first, then the 4 waves
-    if constexpr (SHAPE == 32) {
-        e += __shfl_xor(e, 32, WAVE);
-        nn += __shfl_xor(nn, 32, WAVE);
-        if (lane < 32) {
-            red[wave][0][lane] = e;
-            red[wave][1][lane] = nn;
-        }
-    } else {
-#pragma unroll
-        for (int m = 16; m <= 32; m <<= 1) {
-            e += __shfl_xor(e, m, WAVE);
-            nn += __shfl_xor(nn, m, WAVE);
-            e_hi += __shfl_xor(e_hi, m, WAVE);
-            n_hi += __shfl_xor(n_hi, m, WAVE);
-        }
-        if (lane < 16) {
-            red[wave][0][lane] = e;
-            red[wave][1][lane] = nn;
-            red[wave][0][16 + lane] = e_hi;
-            red[wave][1][16 + lane] = n_hi;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 32) {
-        double es = 0.0, ns = 0.0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            es += red[w][0][threadIdx.x];
-            ns += red[w][1][threadIdx.x];
-        }
-        const float rel = ns > 0.0 ? (float)sqrt(es / ns) : 0.f;
-        qerr[blockIdx.x * 32 + threadIdx.x] = __uint_as_float(__float_as_uint(rel) + 1u);
-    }
-}
 
 // The k-loop of one half tile, fully unrolled: wait for the A fragment of step S (the Q_RING - 1
 // younger reads stay in flight), multiply, refill the ring slot with step S + Q_RING, and after
@@ -258,19 +170,34 @@ __device__ __forceinline__ void qsx_mfma(const f32x4& a, const f32x4 (&bq)[NBQ],
         });
     }
 }
-template <int S, int HS, int K0, int KS, int PER, int SHAPE, int RING, int NBQ, typename Issue>
-__device__ __forceinline__ void qsx_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
-                                          uint32_t abase, Issue& issue_piece) {
-    if constexpr (S < HS) {
-        constexpr int left = HS - S - 1 < RING - 1 ? HS - S - 1 : RING - 1;
+// THE k-loop: steps S .. N - 1 of a buffer of N pieces (a half tile: N = HS, its first k-step K0; a
+// whole tile: N = KS, K0 = 0).  What a kernel threads between the MFMAs is Hook::after<S>(args...),
+// called once the ring slot of step S is refilled.  (A stateless policy and plain arguments, not a
+// closure: one that holds the emit state by reference keeps it in memory a pass longer, and hipcc
+// then numbers the B-operand registers differently.)
+template <int S, int N, int K0, int KS, typename Hook, int SHAPE, int RING, int NBQ, typename... Args>
+__device__ __forceinline__ void qs_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
+                                         uint32_t abase, Args&... args) {
+    if constexpr (S < N) {
+        constexpr int left = N - S - 1 < RING - 1 ? N - S - 1 : RING - 1;
         asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[S % RING]) : "n"(left) : "memory");
         qsx_mfma<S, K0, KS, SHAPE>(a[S % RING], bq, acc);
-        if constexpr (S + RING < HS) QS_RD(a[S % RING], S + RING);
-        constexpr int every = HS / PER;
-        if constexpr (S % every == 1 && S / every < PER) issue_piece(std::integral_constant<int, S / every>{});
-        qsx_steps<S + 1, HS, K0, KS, PER, SHAPE, RING, NBQ>(a, bq, acc, abase, issue_piece);
+        if constexpr (S + RING < N) QS_RD(a[S % RING], S + RING);
+        Hook::template after<S>(args...);
+        qs_steps<S + 1, N, K0, KS, Hook>(a, bq, acc, abase, args...);
     }
 }
+#undef QS_RD
+// after step S of a WHOLE row tile (dense_scan_f16qs): the PB row pieces an issuing wave sends go
+// into its first steps (tsched::issue_step; PB = 0: none)
+template <int PB>
+struct QTileHook {
+    template <int S, typename Issue>
+    static __device__ __forceinline__ void after(Issue& issue_piece) {
+        constexpr int p = (S - 1) / 2;
+        if constexpr (S >= 1 && p < PB && tsched::issue_step(p) == S) issue_piece(std::integral_constant<int, p>{});
+    }
+};
 
 // the emit of one accumulator register (a struct member, not a lambda: its store is inline asm).
 // A lane's candidate segment is addressed as a 32-bit byte offset from `cand` (one SGPR pair for
@@ -313,14 +240,12 @@ struct QEmit : QColl<QAcc<SHAPE>::NQL, COLL> {
             slot[qs] += 8;
         }
     }
-    template <int X>
-    __device__ __forceinline__ void all(const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
-        if constexpr (X < QAcc<SHAPE>::NREG) {
-            one<X>(acc, row0, lane);
-            all<X + 1>(acc, row0, lane);
-        }
-    }
 };
+// every accumulator register of a row tile through `one` of a QEmit or a QTop, in register order
+template <int SHAPE, typename Keep>
+__device__ __forceinline__ void q_all(Keep& keep, const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
+    static_for<0, QAcc<SHAPE>::NREG>([&](auto x) { keep.template one<decltype(x)::value>(acc, row0, lane); });
+}
 
 // MODE_ALL (the sample pass): what a lane keeps of the sample rows it scores -- for each of its NQL
 // queries the SAMPLE_TOP largest finite scores, in registers, sorted descending (a max / min pair per
@@ -362,13 +287,6 @@ struct QTop : QColl<QAcc<SHAPE>::NQL, COLL> {
             t[qs][j] = hi;
         }
     }
-    template <int X>
-    __device__ __forceinline__ void all(const QAcc<SHAPE>& acc, uint32_t row0, int lane) {
-        if constexpr (X < QAcc<SHAPE>::NREG) {
-            one<X>(acc, row0, lane);
-            all<X + 1>(acc, row0, lane);
-        }
-    }
     // the lane's values of query q (u-th of the lane), segment seg of nseg
     __device__ __forceinline__ void store(float* __restrict__ sample, int u, int64_t q, int nseg, int seg) const {
         float* dst = sample + (q * nseg + seg) * SAMPLE_TOP;
@@ -377,46 +295,91 @@ struct QTop : QColl<QAcc<SHAPE>::NQL, COLL> {
     }
 };
 
-// qsx_steps with the emit of the PREVIOUS row tile's accumulators threaded through it (the 4-wave
-// kernel below, MODE_FILTER): a block of that kernel has ONE wave per SIMD, so while a wave runs
-// its epilogue nothing feeds the SIMD's matrix pipe -- the stamps put that at a quarter of a half
-// tile.  Here the 16 accumulator registers of tile i - 1 are compared / stored one at a time
-// between the MFMAs of tile i (8 per half tile, evenly spaced): an MFMA occupies the pipe for
-// 16 cycles after it issues, which is what one register's compare-and-branch takes to issue.
-template <int S, int HS, int K0, int KS, int PER, int SHAPE, int HF, int RING, int NBQ, bool COLL, typename Issue>
-__device__ __forceinline__ void qsx_steps_pe(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
-                                             uint32_t abase, Issue& issue_piece, QEmit<SHAPE, COLL>& em,
-                                             const QAcc<SHAPE>& prv, uint32_t row_prv, int lane) {
-    if constexpr (S < HS) {
-        constexpr int left = HS - S - 1 < RING - 1 ? HS - S - 1 : RING - 1;
-        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[S % RING]) : "n"(left) : "memory");
-        qsx_mfma<S, K0, KS, SHAPE>(a[S % RING], bq, acc);
-        if constexpr (S + RING < HS) QS_RD(a[S % RING], S + RING);
+// after step S of half HF of a row tile, HS pieces (dense_scan_f16q): one of the wave's PER pieces
+// after every (HS / PER)-th MFMA.
+// With an emit state, also the emit of the PREVIOUS row tile's accumulators (MODE_FILTER at dim 1024):
+// a block of that kernel has ONE wave per SIMD, so while a wave runs its epilogue nothing feeds the
+// SIMD's matrix pipe -- the stamps put that at a quarter of a half tile.  Here the 16 accumulator
+// registers of tile i - 1 are compared / stored one at a time between the MFMAs of tile i (8 per
+// half tile, evenly spaced): an MFMA occupies the pipe for 16 cycles after it issues, which is what
+// one register's compare-and-branch takes to issue.
+template <int HS, int PER, int HF>
+struct QHalfHook {
+    template <int S, typename Issue>
+    static __device__ __forceinline__ void after(Issue& issue_piece) {
         constexpr int every = HS / PER;
         if constexpr (S % every == 1 && S / every < PER) issue_piece(std::integral_constant<int, S / every>{});
+    }
+    template <int S, typename Issue, int SHAPE, bool COLL>
+    static __device__ __forceinline__ void after(Issue& issue_piece, QEmit<SHAPE, COLL>& em,
+                                                 const QAcc<SHAPE>& prv, uint32_t row_prv, int lane) {
+        after<S>(issue_piece);
         // half the registers of the previous tile per half tile, evenly spaced: register j after the
         // step at which j = floor(S * NRH / HS) is about to change
         constexpr int NRH = QAcc<SHAPE>::NREG / 2, j = S * NRH / HS;
         if constexpr ((S + 1) * NRH / HS > j) em.template one<NRH * HF + j>(prv, row_prv, lane);
-        qsx_steps_pe<S + 1, HS, K0, KS, PER, SHAPE, HF, RING, NBQ, COLL>(a, bq, acc, abase, issue_piece, em, prv, row_prv, lane);
     }
-}
-// The k-loop of a WHOLE row tile (dense_scan_f16qs): qsx_steps over all KS pieces, with the PB row
-// pieces an issuing wave sends threaded into its first steps (tsched::issue_step; PB = 0: none).
-template <int S, int KS, int PB, int SHAPE, int RING, int NBQ, typename Issue>
-__device__ __forceinline__ void qst_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
-                                          uint32_t abase, Issue& issue_piece) {
-    if constexpr (S < KS) {
-        constexpr int left = KS - S - 1 < RING - 1 ? KS - S - 1 : RING - 1;
-        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[S % RING]) : "n"(left) : "memory");
-        qsx_mfma<S, 0, KS, SHAPE>(a[S % RING], bq, acc);
-        if constexpr (S + RING < KS) QS_RD(a[S % RING], S + RING);
-        constexpr int p = (S - 1) / 2;
-        if constexpr (S >= 1 && p < PB && tsched::issue_step(p) == S) issue_piece(std::integral_constant<int, p>{});
-        qst_steps<S + 1, KS, PB, SHAPE, RING, NBQ>(a, bq, acc, abase, issue_piece);
+};
+
+// What a wave holds for the whole launch besides its accumulators, and what it leaves behind, for
+// both kernels.  (Macros over the kernel's own names -- A, MODE, SHAPE, COLL, slot, lane, q32 = the
+// wave's tile of A::QW queries, and the kernel's arguments -- not functions: as functions over em /
+// top / start, or as one struct that holds them, hipcc numbers the kernels' registers differently,
+// DESIGN.md 4.1.)
+// QS_WAVE_SETUP: the B operands of the wave's queries, all k-steps, in registers for the whole launch
+// (bq: NBQ fragments of 1 KiB, image [tile of QW queries][NBQ][64 lanes]; a wave whose queries are all
+// padding only moves row pieces: no operands); the lane's private candidate segments (MODE_FILTER:
+// query q, segment my_seg = SEGS * slice + seg(lane) of nseg; start[u] = byte offset of the segment of
+// the lane's u-th query) and its sample keep (MODE_ALL).
+#define QS_WAVE_SETUP(NBQ_)                                                                             \
+    f32x4 bq[NBQ_];                                                                                     \
+    if ((int64_t)q32 * A::QW < n_queries)                                                               \
+        static_for<0, NBQ_>([&](auto s) {                                                               \
+            bq[s] = qfrag[((int64_t)q32 * NBQ_ + s) * 64 + lane];                                       \
+        });                                                                                             \
+    const int nseg = A::SEGS * slot.nslices;                                                            \
+    const int my_seg = A::SEGS * slot.slice + A::seg(lane);                                             \
+    QEmit<SHAPE, COLL> em;                                                                              \
+    em.cand = cand;                                                                                     \
+    QTop<SHAPE, COLL> top; /* MODE_ALL */                                                               \
+    if constexpr (COLL) em.doc_coll = top.doc_coll = doc_coll;                                          \
+    top.init();                                                                                         \
+    uint32_t start[A::NQL];                                                                             \
+    _Pragma("unroll")                                                                                   \
+    for (int u = 0; u < A::NQL; ++u) {                                                                  \
+        const int q = q32 * A::QW + A::query(lane, u);                                                  \
+        em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;                                                 \
+        /* collection filter of this lane's query (-1: none): checked only for rows that pass tau      \
+           (MODE_ALL: for the sample rows with a finite score) */                                       \
+        if constexpr (COLL) em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;  \
+        start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));      \
+        em.slot[u] = start[u];                                                                          \
+        em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));                                      \
+    }                                                                                                   \
+    /* Retire these loads HERE, visibly to hipcc: left pending, their first use (the first MFMA of     \
+       the tile loop) gets an s_waitcnt vmcnt(0) on every trip, which would drain the DMA of the       \
+       next (half) tiles each time. */                                                                  \
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+// QS_WAVE_TILE: a row tile's accumulators into the candidate segments, or into the sample keep
+#define QS_WAVE_TILE(acc_, row0_)                                \
+    if constexpr (MODE == MODE_ALL) {                            \
+        q_all(top, acc_, row0_, lane);                           \
+    } else {                                                     \
+        q_all(em, acc_, row0_, lane);                            \
     }
-}
-#undef QS_RD
+// QS_WAVE_WRITE_OUT, the end of the launch: the fill of the lane's segments, or its kept sample scores
+// (the waves of padding queries too: -inf)
+#define QS_WAVE_WRITE_OUT()                                                                             \
+    if constexpr (MODE == MODE_FILTER) {                                                                \
+        _Pragma("unroll")                                                                               \
+        for (int u = 0; u < A::NQL; ++u)                                                                \
+            seg_cnt[(int64_t)(q32 * A::QW + A::query(lane, u)) * nseg + my_seg] =                       \
+                (int)((em.slot[u] - start[u]) / sizeof(Cand));                                          \
+    } else {                                                                                            \
+        _Pragma("unroll")                                                                               \
+        for (int u = 0; u < A::NQL; ++u)                                                                \
+            top.store(sample, u, (int64_t)q32 * A::QW + A::query(lane, u), nseg, my_seg);               \
+    }
 
 // PROF: diagnostic build (thr_dense_scan_stamps_f16): s_memtime stamps around the phases of the
 // half-tile loop, summed per wave into stamps[(block * 4 + wave) * 8 + {0: wait for the own DMA
@@ -434,7 +397,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
     unsigned long long* __restrict__ stamps = nullptr) {
     using C = QScan<DIM>;
     using A = QAcc<SHAPE>;
-    constexpr int KS = C::KS, HS = C::HS, NB = C::NB, PER = C::PER, NQL = A::NQL, QW = A::QW;
+    constexpr int KS = C::KS, HS = C::HS, NB = C::NB, PER = C::PER, QW = A::QW;
     constexpr int NBQ = SHAPE == 32 ? KS : A::NQB * KS / 2;   // B fragments of the wave's queries
     extern __shared__ f32x4 lds_rows[];  // NB half-tile buffers
 
@@ -444,36 +407,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
     const int q32 = slot.qtile * Q_NW + wave;  // this wave's tile of QW (32, or 48) queries
     const bool idle = (int64_t)q32 * QW >= n_queries;   // all padding: only moves row pieces
 
-    // B operands: the wave's 32 queries, all k-steps, in registers for the whole launch
-    f32x4 bq[NBQ];
-    if (!idle)
-        static_for<0, NBQ>([&](auto s) {
-            bq[s] = qfrag[((int64_t)q32 * NBQ + s) * 64 + lane];
-        });
-    // the lane's private candidate segments (MODE_FILTER): query q, segment SEGS * slice + seg(lane)
-    const int nseg = A::SEGS * slot.nslices;
-    const int my_seg = A::SEGS * slot.slice + A::seg(lane);
-    QEmit<SHAPE, COLL> em;
-    em.cand = cand;
-    QTop<SHAPE, COLL> top;   // MODE_ALL
-    if constexpr (COLL) em.doc_coll = top.doc_coll = doc_coll;
-    top.init();
-    uint32_t start[NQL];
-#pragma unroll
-    for (int u = 0; u < NQL; ++u) {
-        const int q = q32 * QW + A::query(lane, u);
-        em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
-        // collection filter of this lane's query (-1: none): checked only for rows that pass tau
-        // (MODE_ALL: for the sample rows with a finite score)
-        if constexpr (COLL) em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
-        start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
-        em.slot[u] = start[u];
-        em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
-    }
-    // Retire these loads HERE, visibly to hipcc: left pending, their first use (the first MFMA
-    // of the tile loop) gets an s_waitcnt vmcnt(0) on every trip, which would drain the DMA
-    // of the next half tiles each time.
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    QS_WAVE_SETUP(NBQ)
 
     // this block's row tiles: slice, slice + nslices, ...; half tile j = (tile j/2, dims half j&1)
     const int64_t first = slot.slice, step = slot.nslices;
@@ -551,7 +485,37 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
             buf = buf + 1 == NB ? 0 : buf + 1;
         }
     }
-    // MODE_FILTER: the emit of a row tile runs between the MFMAs of the NEXT one (qsx_steps_pe), out
+    // One half tile, hf of row tile i, into the accumulators ACC (a macro, not a lambda: asm operands
+    // do not capture).  After ACC come the arguments of QHalfHook::after: issue_piece (defined in
+    // here), then nothing or the emit state.
+#define QS_HALF(hf, ACC, ...)                                                                      \
+    {                                                                                              \
+        stamp(-1);                                                                                 \
+        /* own pieces of half tile 2i+hf done (the NB-2 younger half tiles' pieces -- and the      \
+           emit's few stores among them, which are over-waited for -- may stay in flight) */       \
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PER * C::VM_PER_PIECE) : "memory");    \
+        stamp(0);                                                                                  \
+        __builtin_amdgcn_s_barrier();                                                              \
+        stamp(1);                                                                                  \
+        const int nbuf = buf == 0 ? NB - 1 : buf - 1; /* half tile j-1's buffer */                 \
+        const f32x4* src = piece_src(2 * i + (hf) + NB - 1);                                       \
+        auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };                    \
+        const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;                         \
+        f32x4 a[C::RING];                                                                          \
+        qs_fill<0, HS>(a, abase);                                                                  \
+        stamp(2);                                                                                  \
+        qs_steps<0, HS, (hf) * HS, KS, QHalfHook<HS, PER, (hf)>>(a, bq, ACC, abase, __VA_ARGS__);  \
+        if constexpr (PROF) {                                                                      \
+            if constexpr (SHAPE == 32) asm volatile("" : "+v"(ACC.v));                             \
+            else {                                                                                 \
+                asm volatile("" : "+v"(ACC.t[0]), "+v"(ACC.t[1]), "+v"(ACC.t[2]), "+v"(ACC.t[3])); \
+                if constexpr (A::NQB == 3) asm volatile("" : "+v"(ACC.t[4]), "+v"(ACC.t[5]));      \
+            }                                                                                      \
+        }                                                                                          \
+        stamp(3);                                                                                  \
+        buf = buf + 1 == NB ? 0 : buf + 1;                                                         \
+    }
+    // MODE_FILTER: the emit of a row tile runs between the MFMAs of the NEXT one (QHalfHook), out
     // of the other of two accumulator sets; the first tile "emits" a set of -inf (a compare and a
     // branch per register), the last tile's set is emitted after the loop.  Same barriers, same
     // DMA order and wait counts per half tile as below.
@@ -572,20 +536,7 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
             else acc2[1].t[x >> 2][x & 3] = -INFINITY;
         }
         uint32_t row_of[2] = {0u, 0u};
-#define QS_HALF_PE(hf, CUR, PRV)                                                                   \
-    {                                                                                              \
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PER * C::VM_PER_PIECE) : "memory");                      \
-        __builtin_amdgcn_s_barrier();                                                              \
-        const int nbuf = buf == 0 ? NB - 1 : buf - 1; /* half tile j-1's buffer */                 \
-        const f32x4* src = piece_src(2 * i + (hf) + NB - 1);                                       \
-        auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };                    \
-        const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;                         \
-        f32x4 a[C::RING];                                                                           \
-        qs_fill<0, HS>(a, abase);                                                                  \
-        qsx_steps_pe<0, HS, (hf) * HS, KS, PER, SHAPE, (hf)>(a, bq, acc2[CUR], abase, issue_piece, \
-                                                            em, acc2[PRV], row_of[PRV], lane);     \
-        buf = buf + 1 == NB ? 0 : buf + 1;                                                         \
-    }
+#define QS_HALF_PE(hf, CUR, PRV) QS_HALF(hf, acc2[CUR], issue_piece, em, acc2[PRV], row_of[PRV], lane)
         const int64_t n_it = idle ? 0 : n_mine;
         int64_t i = 0;
 #pragma unroll 1
@@ -605,67 +556,28 @@ __global__ __launch_bounds__(Q_NW * 64, QScan<DIM>::PER_CU) void dense_scan_f16q
             acc2[0].zero();
             QS_HALF_PE(0, 0, 1)
             QS_HALF_PE(1, 0, 1)
-            em.template all<0>(acc2[0], (uint32_t)((first + i * step) * tile_stride * 32), lane);
+            QS_WAVE_TILE(acc2[0], (uint32_t)((first + i * step) * tile_stride * 32))
         } else if (n_it > 0) {
-            em.template all<0>(acc2[1], row_of[1], lane);
+            QS_WAVE_TILE(acc2[1], row_of[1])
         }
 #undef QS_HALF_PE
     } else {
     // one trip = one row tile = two half tiles (the accumulators run through both)
 #pragma unroll 1
     for (int64_t i = 0; i < (idle ? 0 : n_mine); ++i) {
-        // (a macro, not a lambda: asm operands do not capture)
-#define QS_HALF(hf)                                                                                \
-    {                                                                                              \
-        stamp(-1);                                                                                 \
-        /* own pieces of half tile 2i+hf done (the NB-2 younger half tiles' pieces -- and the      \
-           emit's few stores among them, which are over-waited for -- may stay in flight) */       \
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 2) * PER * C::VM_PER_PIECE) : "memory");                      \
-        stamp(0);                                                                                  \
-        __builtin_amdgcn_s_barrier();                                                              \
-        stamp(1);                                                                                  \
-        const int nbuf = buf == 0 ? NB - 1 : buf - 1; /* half tile j-1's buffer */                 \
-        const f32x4* src = piece_src(2 * i + (hf) + NB - 1);                                       \
-        auto issue_piece = [&](auto P) { dma(src, nbuf, decltype(P)::value); };                    \
-        const uint32_t abase = lds_base + buf * C::HALF_BYTES + lane * 16;                         \
-        f32x4 a[C::RING];                                                                           \
-        qs_fill<0, HS>(a, abase);                                                                  \
-        stamp(2);                                                                                  \
-        qsx_steps<0, HS, (hf) * HS, KS, PER, SHAPE>(a, bq, acc, abase, issue_piece);                \
-        if constexpr (PROF) {                                                                      \
-            if constexpr (SHAPE == 32) asm volatile("" : "+v"(acc.v));                               \
-            else {                                                                                 \
-                asm volatile("" : "+v"(acc.t[0]), "+v"(acc.t[1]), "+v"(acc.t[2]), "+v"(acc.t[3]));   \
-                if constexpr (A::NQB == 3) asm volatile("" : "+v"(acc.t[4]), "+v"(acc.t[5]));       \
-            }                                                                                      \
-        }                                                                                          \
-        stamp(3);                                                                                  \
-        buf = buf + 1 == NB ? 0 : buf + 1;                                                         \
-    }
         acc.zero();
-        QS_HALF(0)
-        QS_HALF(1)
-#undef QS_HALF
+        QS_HALF(0, acc, issue_piece)
+        QS_HALF(1, acc, issue_piece)
 
         const int64_t t = first + i * step;
-        if constexpr (MODE == MODE_ALL) {
-            top.template all<0>(acc, (uint32_t)(t * tile_stride * 32), lane);
-        } else {
-            em.template all<0>(acc, (uint32_t)(t * tile_stride * 32), lane);
-        }
+        QS_WAVE_TILE(acc, (uint32_t)(t * tile_stride * 32))
         stamp(4);
     }
     }
+#undef QS_HALF
     // nothing may still be landing in LDS when the block retires
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (MODE == MODE_FILTER) {
-#pragma unroll
-        for (int u = 0; u < NQL; ++u)
-            seg_cnt[(int64_t)(q32 * QW + A::query(lane, u)) * nseg + my_seg] = (int)((em.slot[u] - start[u]) / sizeof(Cand));
-    } else {   // (idle waves too: -inf for their padding queries)
-#pragma unroll
-        for (int u = 0; u < NQL; ++u) top.store(sample, u, (int64_t)q32 * QW + A::query(lane, u), nseg, my_seg);
-    }
+    QS_WAVE_WRITE_OUT()
     if constexpr (PROF) {
         if (lane == 0) {
             unsigned long long* o = stamps + ((int64_t)blockIdx.x * Q_NW + wave) * 8;
@@ -727,7 +639,8 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries) {
     using C = QStag<DIM>;
     using A = QAcc<SHAPE>;
-    constexpr int KS = C::KS, PB = C::PB, NQL = A::NQL;
+    constexpr int KS = C::KS, PB = C::PB;
+    static_assert(A::QW == 32 && A::NQB * KS / 2 == KS, "32 queries per wave: KS fragments in both shapes");
     extern __shared__ f32x4 lds_rows[];  // NBUF whole-tile buffers
 
     const ScanSlot slot = scan_slot(n_qtiles);
@@ -735,33 +648,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int q32 = slot.qtile * QS_NW + wave;   // this wave's 32 queries
 
-    // B operands: the wave's 32 queries, every k-step, in registers for the whole launch
-    // (both shapes: KS fragments of 1 KiB, image [q32 tile][KS][64 lanes])
-    f32x4 bq[KS];
-    if ((int64_t)q32 * 32 < n_queries)
-        static_for<0, KS>([&](auto s) {
-            bq[s] = qfrag[((int64_t)q32 * KS + s) * 64 + lane];
-        });
-    const int nseg = A::SEGS * slot.nslices;
-    const int my_seg = A::SEGS * slot.slice + A::seg(lane);
-    QEmit<SHAPE, COLL> em;
-    em.cand = cand;
-    QTop<SHAPE, COLL> top;   // MODE_ALL
-    if constexpr (COLL) em.doc_coll = top.doc_coll = doc_coll;
-    top.init();
-    uint32_t start[NQL];
-#pragma unroll
-    for (int u = 0; u < NQL; ++u) {
-        const int q = q32 * 32 + A::query(lane, u);
-        em.tau[u] = MODE == MODE_FILTER ? tau[q] : 0.f;
-        // collection filter of this lane's query (-1: none): checked only for rows that pass tau
-        // (MODE_ALL: for the sample rows with a finite score)
-        if constexpr (COLL) em.qc[u] = top.qc[u] = (query_coll && q < n_queries) ? query_coll[q] : -1;
-        start[u] = (uint32_t)(((int64_t)q * CAND_CAP + (int64_t)my_seg * seg_cap) * sizeof(Cand));
-        em.slot[u] = start[u];
-        em.end[u] = start[u] + (uint32_t)(seg_cap * sizeof(Cand));
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // retire these loads visibly to hipcc (see dense_scan_f16q)
+    QS_WAVE_SETUP(KS)   // (both shapes: KS fragments)
 
     namespace ts = tsched;
     const int64_t first = slot.slice, step = slot.nslices;
@@ -781,12 +668,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
                                                               ts::piece_index(iw, p) * 1024),
             16, 0, 0);
     };
-#define QS_EMIT(i_)                                                                                \
-    if constexpr (MODE == MODE_ALL) {                                                              \
-        top.template all<0>(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32), lane);      \
-    } else {                                                                                       \
-        em.template all<0>(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32), lane);       \
-    }
+#define QS_EMIT(i_) QS_WAVE_TILE(acc, (uint32_t)((first + (i_) * step) * tile_stride * 32))
     // barrier t of an issuing wave: its own pieces of tile t have landed; the pieces of the
     // nbuf - 2 younger tiles stay in flight, and the emit stores of the interval that ends here
     // are older than the youngest of them (see above), so they are not what the count leaves out
@@ -837,7 +719,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
             const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
             qs_fill<0, KS>(a, abase);
             acc.zero();
-            qst_steps<0, KS, 0, SHAPE>(a, bq, acc, abase, no_piece);
+            qs_steps<0, KS, 0, KS, QTileHook<0>>(a, bq, acc, abase, no_piece);
             buf = ts::next_buffer(buf, DIM);
             QS_EMIT(i)
         }
@@ -857,7 +739,7 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
             const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
             qs_fill<0, KS>(a, abase);
             acc.zero();
-            qst_steps<0, KS, PB, SHAPE>(a, bq, acc, abase, issue_piece);
+            qs_steps<0, KS, 0, KS, QTileHook<PB>>(a, bq, acc, abase, issue_piece);
             buf = ts::next_buffer(buf, DIM);
         }
         if (n_mine > 0) {
@@ -867,89 +749,11 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
 #undef QS_SYNC_B
 #undef QS_EMIT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing may still be landing in LDS
-    if constexpr (MODE == MODE_FILTER) {
-#pragma unroll
-        for (int u = 0; u < NQL; ++u)
-            seg_cnt[(int64_t)(q32 * 32 + A::query(lane, u)) * nseg + my_seg] = (int)((em.slot[u] - start[u]) / sizeof(Cand));
-    } else {   // (the waves of padding queries too: -inf)
-#pragma unroll
-        for (int u = 0; u < NQL; ++u) top.store(sample, u, (int64_t)q32 * 32 + A::query(lane, u), nseg, my_seg);
-    }
+    QS_WAVE_WRITE_OUT()
 }
 
-// float32 corpus -> fragment-major float16 copy of the NORMALISED rows (d * (1/||d||), round to
-// nearest even); rows with ||d|| = 0 and the padding rows of the last tile are NaN.  Also
-// max over rows of ||d16 - d/||d|| || (float64, against the exactly normalised row), rounded up,
-// via atomicMax on the float bits.  packed == nullptr: measure only.  One wave per row (rows of
-// the padded tail included).
-__global__ __launch_bounds__(256) void quantize_f16_norm(const float* __restrict__ docs,
-                                                         int64_t n_docs, int dim, int shape,
-                                                         _Float16* __restrict__ packed,
-                                                         unsigned int* __restrict__ max_err_bits) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
-    const int64_t n_pad = (n_docs + 31) / 32 * 32;
-    if (row >= n_pad) return;
-    const int64_t tile = row >> 5;
-    const int r = (int)(row & 31), ks = dim / 16;
-    const float* x = docs + row * dim;
-    double nn = 0.0;
-    if (row < n_docs)
-        for (int i = lane; i < dim; i += WAVE) nn += (double)x[i] * (double)x[i];
-    for (int m = 32; m >= 1; m >>= 1) nn += __shfl_xor(nn, m, WAVE);
-    const double dn = sqrt(nn);
-    const bool live = dn > 0.0;  // same rows thr_doc_norms gives inv_norm = 0 ("no embedding")
-    double err = 0.0;
-    for (int i = lane; i < dim; i += WAVE) {
-        const float v = live ? x[i] : 0.f;
-        const _Float16 hv = live ? (_Float16)(float)((double)v / dn) : (_Float16)__builtin_nanf("");
-        if (packed) {
-            if (shape == 32) {   // piece s = 32 rows x dims [16 s, +16): lane r + 32 hh, hh = dim half
-                const int s = i >> 4, hh = (i >> 3) & 1, e = i & 7;
-                packed[(((tile * ks + s) * 64) + r + 32 * hh) * 8 + e] = hv;
-            } else {             // piece 2 k32 + ra = rows [16 ra, +16) x dims [32 k32, +32): lane (r & 15) + 16 g
-                const int k32 = i >> 5, g = (i >> 3) & 3, e = i & 7, ra = r >> 4;
-                packed[(((tile * ks + 2 * k32 + ra) * 64) + (r & 15) + 16 * g) * 8 + e] = hv;
-            }
-        }
-        if (live) {
-            const double d = (double)v / dn - (double)(float)hv;
-            err += d * d;
-        }
-    }
-    for (int m = 32; m >= 1; m >>= 1) err += __shfl_xor(err, m, WAVE);
-    if (lane == 0 && live) {
-        float rel = (float)sqrt(err);
-        rel = __uint_as_float(__float_as_uint(rel) + 1u);
-        atomicMax(max_err_bits, __float_as_uint(rel));
-    }
-}
-
-// The in-flight-rounding scan (dense_scan_f16) rounds the float32 rows AS THEY ARE: its row error
-// term is max_d ||fp16(d) - d|| / ||d|| (+inf when a value leaves the float16 range), rounded up,
-// accumulated as ordered float bits with atomicMax.  One wave per row.
-__global__ __launch_bounds__(256) void measure_f16_error(const float* __restrict__ docs, int64_t n_docs,
-                                                         int dim, unsigned int* __restrict__ max_rel_bits) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * (blockDim.x / WAVE) + (threadIdx.x >> 6);
-    if (row >= n_docs) return;
-    const float* x = docs + row * dim;
-    double err = 0.0, nrm = 0.0;
-    for (int i = lane; i < dim; i += WAVE) {
-        const float v = x[i];
-        const double d = (double)v - (double)(float)(_Float16)v;
-        err += d * d;
-        nrm += (double)v * (double)v;
-    }
-    for (int m = 32; m >= 1; m >>= 1) {
-        err += __shfl_xor(err, m, WAVE);
-        nrm += __shfl_xor(nrm, m, WAVE);
-    }
-    if (lane == 0 && nrm > 0.0) {
-        float rel = (float)sqrt(err / nrm);
-        rel = __uint_as_float(__float_as_uint(rel) + 1u);
-        atomicMax(max_rel_bits, __float_as_uint(rel));  // positive floats order like their bits
-    }
-}
+#undef QS_WAVE_WRITE_OUT
+#undef QS_WAVE_TILE
+#undef QS_WAVE_SETUP
 
 }  // namespace thr

@@ -19,7 +19,7 @@
 // so that the 32 lanes of a ds_read_b128 (one query row each, stride 3 KiB) hit
 // distinct bank groups.
 #pragma once
-#include "dense_common.hpp"
+#include "dense_scan_tilelist.hpp"
 
 namespace thr {
 
@@ -47,15 +47,7 @@ __global__ __launch_bounds__(MF_THREADS) void dense_scan_mfma(
     const int r = lane & 31, h = lane >> 5;
     Cand* wbuf = reinterpret_cast<Cand*>(lds_q + MF_QT * CPR) + wave * WBUF;
     int wcnt = 0;
-    auto flush = [&]() {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&tile_cnt[qtile], wcnt);
-        base = __shfl(base, 0, WAVE);
-        for (int i = lane; i < wcnt; i += WAVE)
-            if (base + i < tile_cap) tile_list[(int64_t)qtile * tile_cap + base + i] = wbuf[i];
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): only loads pending afterwards
-        wcnt = 0;
-    };
+    auto flush = [&]() { tilelist_flush<true>(wbuf, wcnt, lane, qtile, tile_cnt, tile_list, tile_cap); };
 
     for (int i = threadIdx.x; i < MF_QT * CPR; i += MF_THREADS) {
         const int q = i / CPR, c = i % CPR;
@@ -66,10 +58,9 @@ __global__ __launch_bounds__(MF_THREADS) void dense_scan_mfma(
     }
     __syncthreads();
 
+    // (lane_tau / lane_coll of dense_scan_tilelist.hpp, which says why the filter is applied here,
+    // written out: through the functions this kernel's registers come out differently)
     const float my_tau = MODE == MODE_FILTER ? tau[qtile * MF_QT + r] : 0.f;
-    // collection filter of this lane's query (-1: none), applied as rows pass tau: tau was taken
-    // from the sample rows of THAT collection, so without the filter here a collection of 1/c of
-    // the corpus lets c times the aimed candidates through and overflows the tile list
     const int my_qc = (MODE == MODE_FILTER && query_coll && qtile * MF_QT + r < n_queries)
                           ? query_coll[qtile * MF_QT + r] : -1;
     const int64_t wave_id = (int64_t)slot.slice * MF_WAVES + wave;
@@ -151,14 +142,7 @@ __global__ __launch_bounds__(MF_THREADS) void dense_scan_mfma(
             } else {
                 bool pass = ok && inv > 0.f && sc >= my_tau;
                 if (pass && my_qc != -1 && doc_coll[row0 + row] != my_qc) pass = false;
-                const uint64_t m = __ballot(pass);
-                if (m) {
-                    const int pos = wcnt + __popcll(m & ((1ull << lane) - 1ull));
-                    if (pass)
-                        wbuf[pos] = Cand{sc, ((uint32_t)r << ROW_BITS) | (uint32_t)(row0 + row)};
-                    wcnt += __popcll(m);
-                    if (wcnt > WBUF - WAVE) flush();  // the next ballot can add 64 more
-                }
+                THR_TILELIST_PUSH(pass, sc, ((uint32_t)r << ROW_BITS) | (uint32_t)(row0 + row))
             }
         }
     }
@@ -210,15 +194,7 @@ __global__ __launch_bounds__(NW * WAVE) void dense_scan_mfma2(
     f32x4* stage = lds_v + MF_QT * CPR + wave * MF2_STAGE_F4;
     Cand* wbuf = reinterpret_cast<Cand*>(lds_q + MF_QT * CPR + NW * MF2_STAGE_F4) + wave * WBUF;
     int wcnt = 0;
-    auto flush = [&]() {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&tile_cnt[qtile], wcnt);
-        base = __shfl(base, 0, WAVE);
-        for (int i = lane; i < wcnt; i += WAVE)
-            if (base + i < tile_cap) tile_list[(int64_t)qtile * tile_cap + base + i] = wbuf[i];
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        wcnt = 0;
-    };
+    auto flush = [&]() { tilelist_flush<true>(wbuf, wcnt, lane, qtile, tile_cnt, tile_list, tile_cap); };
 
     for (int i = threadIdx.x; i < MF_QT * CPR; i += (NW * WAVE)) {
         const int q = i / CPR, c = i % CPR;
@@ -229,10 +205,9 @@ __global__ __launch_bounds__(NW * WAVE) void dense_scan_mfma2(
     }
     __syncthreads();
 
+    // (lane_tau / lane_coll of dense_scan_tilelist.hpp, which says why the filter is applied here,
+    // written out: through the functions this kernel's registers come out differently)
     const float my_tau = MODE == MODE_FILTER ? tau[qtile * MF_QT + r] : 0.f;
-    // collection filter of this lane's query (-1: none), applied as rows pass tau: tau was taken
-    // from the sample rows of THAT collection, so without the filter here a collection of 1/c of
-    // the corpus lets c times the aimed candidates through and overflows the tile list
     const int my_qc = (MODE == MODE_FILTER && query_coll && qtile * MF_QT + r < n_queries)
                           ? query_coll[qtile * MF_QT + r] : -1;
     const int64_t wave_id = (int64_t)slot.slice * NW + wave;
@@ -240,21 +215,16 @@ __global__ __launch_bounds__(NW * WAVE) void dense_scan_mfma2(
     const f32x4* docs4 = reinterpret_cast<const f32x4*>(docs);
 
     // loader role of this lane: row (lane >> 3) + 8*i of the tile, 16-byte chunk (lane & 7)
-    const int lrow = lane >> 3, lchunk = lane & 7;
-    auto load_off = [&](int64_t t, int i) -> int64_t {
-        int64_t row = t * tile_stride * MF_ROWS + lrow + 8 * i;
-        row = row < n_docs ? row : n_docs - 1;
-        return row * CPR + lchunk;
-    };
+    auto load_off = [&](int64_t t, int i) -> int64_t { return loader_off(t, i, lane, tile_stride, n_docs, CPR); };
     // LDS slots this lane writes (one per i) / reads as A fragment (one per quad); and the
     // swizzled low part of the query-chunk index for (stage parity, quad)
-    int wslot0 = mf2_slot(lrow, lchunk), wslot1 = mf2_slot(lrow + 8, lchunk);
-    int wslot2 = mf2_slot(lrow + 16, lchunk), wslot3 = mf2_slot(lrow + 24, lchunk);
+    int wslot0 = loader_wslot(lane, 0), wslot1 = loader_wslot(lane, 1);
+    int wslot2 = loader_wslot(lane, 2), wslot3 = loader_wslot(lane, 3);
     int rslot0 = mf2_slot(r, h), rslot1 = mf2_slot(r, 2 + h), rslot2 = mf2_slot(r, 4 + h),
         rslot3 = mf2_slot(r, 6 + h);
     int qlow[8];
 #pragma unroll
-    for (int x = 0; x < 8; ++x) qlow[x] = (((x >> 2) * 8 + 2 * (x & 3) + h) ^ r) & 15;
+    for (int x = 0; x < 8; ++x) qlow[x] = query_low_chunk(x, r, h);
 
 #define THR_PIN(x) asm volatile("" : "+v"(x))
     // request chunk-stage data of the 4 loader rows at the running pointers, then advance them
@@ -380,14 +350,7 @@ __global__ __launch_bounds__(NW * WAVE) void dense_scan_mfma2(
                 const float sc = acc[i] * inv;
                 bool pass = ok && inv > 0.f && sc >= my_tau;
                 if (pass && my_qc != -1 && doc_coll[row0 + row] != my_qc) pass = false;
-                const uint64_t m = __ballot(pass);
-                if (m) {
-                    const int pos = wcnt + __popcll(m & ((1ull << lane) - 1ull));
-                    if (pass)
-                        wbuf[pos] = Cand{sc, ((uint32_t)r << ROW_BITS) | (uint32_t)(row0 + row)};
-                    wcnt += __popcll(m);
-                    if (wcnt > WBUF - WAVE) flush();
-                }
+                THR_TILELIST_PUSH(pass, sc, ((uint32_t)r << ROW_BITS) | (uint32_t)(row0 + row))
             }
         }
     }
