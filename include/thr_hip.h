@@ -239,7 +239,15 @@ int thr_dense_scan_probe_f16(const float *docs, const uint16_t *docs16 /* or NUL
  * of its tile loop into stamps[wave * 8 + {0 wait for own DMA pieces, 1 barrier, 2 DMA issue,
  * 3 k-loop, 4 emit, 5 tiles, 6 whole loop, 7 HW_ID}] (device, uint64).  stamps == NULL: only
  * *h_n_waves (host) is set, to size the buffer.  Not a timing: the stamps drain the wave's
- * queues; it says where the time goes (profiles/README.md). */
+ * queues; it says where the time goes (profiles/README.md).
+ * That is the 4-wave-block kernel (dim 1024, or THR_DENSE_F16=q).  At dim <= 768 the staggered
+ * 8-wave kernel is stamped instead and a wave takes SIXTEEN words: *h_n_waves is then twice the
+ * number of waves (the buffer is still *h_n_waves * 8 words) and wave w of the launch owns
+ * stamps[w * 16 + {0 counted vmcnt wait (group B), 1 barrier arrival to release, 2 fill: release
+ * (group B: the end of its emit) to the first A fragment in a register, 3..6 the k-loop in quarters
+ * of its steps, 7 emit, 8 intervals (= row tiles), 9 whole loop, 10 HW_ID, 11..15 zero}]; waves
+ * 0-3 of a block are group A, 4-7 group B; a wave of padding queries stamps nothing.  These stamps
+ * are consumed once per interval and drain nothing inside it (dense_scan_f16q.hpp, QsClock). */
 int thr_dense_scan_stamps_f16(const uint16_t *docs16, int64_t n_docs, int dim, int n_queries,
                               void *workspace, size_t workspace_bytes,
                               unsigned long long *stamps, int *h_n_waves, thr_stream_t stream);

@@ -491,8 +491,6 @@ extern "C" int thr_dense_scan_stamps_f16(const uint16_t* docs16, int64_t n_docs,
     THR_RETURN_IF(!docs16 || !workspace || !h_n_waves, THR_ERR_INVALID);
     THR_RETURN_IF(dim != 512 && dim != 768 && dim != 1024, THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(n_docs <= 0 || n_queries <= 0, THR_ERR_INVALID);
-    // (only the 4-wave-block kernel has a stamped build: THR_DENSE_F16=q, or dim 1024)
-    THR_RETURN_IF(qreg_staggered(dim), THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(n_queries > qreg_max_queries(dim), THR_ERR_UNSUPPORTED);
     const DensePlan P = make_plan(workspace, n_docs, n_queries, 128, KIND_F16, dim, true);
     THR_RETURN_IF(workspace_bytes < P.total, THR_ERR_WORKSPACE);
@@ -500,6 +498,7 @@ extern "C" int thr_dense_scan_stamps_f16(const uint16_t* docs16, int64_t n_docs,
     int rc = launch_scan_f16q<MODE_FILTER, true>(
         dim, reinterpret_cast<const _Float16*>(docs16), P.qfrag, P.ntiles, P.groups, 1, P.tau, P.cnt,
         P.cand, nullptr, (hipStream_t)stream, nullptr, nullptr, nullptr, n_queries, stamps, &blocks);
-    *h_n_waves = blocks * qreg_waves(dim);
+    // rows of 8 words: one per wave of the 4-wave-block kernel, two per wave of the staggered one
+    *h_n_waves = blocks * qreg_waves(dim) * (qreg_staggered(dim) ? 2 : 1);
     return rc;
 }

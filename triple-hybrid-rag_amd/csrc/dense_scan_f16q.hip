@@ -29,10 +29,16 @@ int launch_scan_f16q(int dim, const _Float16* rows16, const _Float16* qfrag, int
     // instantiation that has no gather and no test for one compiled in
     const bool coll = doc_coll != nullptr && query_coll != nullptr;
 #define THR_QS_LAUNCH_(DIM, SHAPE, COLL)                                                          \
-    return launch_lds(dense_scan_f16qs<DIM, MODE, SHAPE, COLL>, grid, dim3(QS_NW * 64),           \
-                      QStag<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,       \
-                      n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,    \
-                      sample, doc_coll, query_coll, n_queries);
+    {if constexpr (PROF)                                                                          \
+        return launch_lds(dense_scan_f16qs_stamps<DIM, SHAPE, COLL>, grid, dim3(QS_NW * 64),      \
+                          QStag<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,   \
+                          n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,\
+                          doc_coll, query_coll, n_queries, stamps);                               \
+    else                                                                                          \
+        return launch_lds(dense_scan_f16qs<DIM, MODE, SHAPE, COLL>, grid, dim3(QS_NW * 64),       \
+                          QStag<DIM>::LDS_BYTES, st, (const f32x4*)rows16, (const f32x4*)qfrag,   \
+                          n_qtiles, n_row_tiles, tile_stride, tau, seg_cnt, cand, CAND_CAP / nseg,\
+                          sample, doc_coll, query_coll, n_queries);}
 #define THR_QS_LAUNCH(DIM, SHAPE)                                                                 \
     {                                                                                             \
         if (coll) THR_QS_LAUNCH_(DIM, SHAPE, true)                                                \

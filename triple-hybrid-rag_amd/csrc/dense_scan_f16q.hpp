@@ -187,6 +187,52 @@ __device__ __forceinline__ void qs_steps(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ
         qs_steps<S + 1, N, K0, KS, Hook>(a, bq, acc, abase, args...);
     }
 }
+// The k-loop of dense_scan_f16qs.  A wave that has its SIMD's matrix pipe to itself (the other group
+// is in its emit or at the barrier: most of an interval) paced 41 cycles per step through qs_steps
+// against the 32 its MFMAs take -- with four and with six reads in flight (the stamp tables of
+// profiles/dense_scan_ring.md): what does not
+// overlap is the wave's own issue of refill, wait and the next MFMA, all of them between the LAST MFMA of
+// one step and the first of the next.  Here they sit between the two MFMAs of ONE step (SHAPE 16), under
+// the first one's 16 pipe cycles, and the next step's first MFMA follows the second back to back:
+//     mfma(S, query block 0) | refill the slot of step S - 1 | wait for step S + 1 | mfma(S, block 1)
+// The slot refilled is the one read a step ago, so RING slots keep RING - 1 reads in flight.  Same
+// MFMAs in the same order per accumulator as qs_steps: same bits.
+template <int S, int N, int KS, typename Hook, int SHAPE, int RING, int NBQ, typename... Args>
+__device__ __forceinline__ void qs_steps_il(f32x4 (&a)[RING], const f32x4 (&bq)[NBQ], QAcc<SHAPE>& acc,
+                                            uint32_t abase, Args&... args) {
+    if constexpr (S < N) {
+        constexpr int NQB = QAcc<SHAPE>::NQB, k32 = S / 2, ra = S & 1;
+        if constexpr (S == 0) {
+            constexpr int left0 = N - 1 < RING - 1 ? N - 1 : RING - 1;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[0]) : "n"(left0) : "memory");
+        }
+        if constexpr (SHAPE == 32) {
+            acc.v = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a[S % RING]),
+                                                           __builtin_bit_cast(half8, bq[S]), acc.v, 0, 0, 0);
+        } else {
+            acc.t[NQB * ra] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                __builtin_bit_cast(half8, a[S % RING]), __builtin_bit_cast(half8, bq[k32]), acc.t[NQB * ra], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (S >= 1 && S - 1 + RING < N) QS_RD(a[(S - 1) % RING], S - 1 + RING);
+        if constexpr (S + 1 < N) {
+            // reads issued after the one of step S + 1: up to step min(S - 1 + RING, N - 1)
+            constexpr int left = N - 2 - S < RING - 2 ? N - 2 - S : RING - 2;
+            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[(S + 1) % RING]) : "n"(left) : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SHAPE != 32) {
+            static_for<1, NQB>([&](auto qb) {
+                acc.t[NQB * ra + qb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                    __builtin_bit_cast(half8, a[S % RING]), __builtin_bit_cast(half8, bq[qb * (KS / 2) + k32]),
+                    acc.t[NQB * ra + qb], 0, 0, 0);
+            });
+        }
+        Hook::template after<S>(args...);
+        __builtin_amdgcn_sched_barrier(0);
+        qs_steps_il<S + 1, N, KS, Hook>(a, bq, acc, abase, args...);
+    }
+}
 #undef QS_RD
 // after step S of a WHOLE row tile (dense_scan_f16qs): the PB row pieces an issuing wave sends go
 // into its first steps (tsched::issue_step; PB = 0: none)
@@ -628,18 +674,111 @@ struct QStag {
     static constexpr int LDS_BYTES = NBUF * TILE_BYTES;
     static_assert(KS % tsched::N_ISSUERS == 0 && NBUF >= 3 && LDS_BYTES <= tsched::LDS_BUDGET, "dim 512 / 768 only");
     static_assert(tsched::wait_leaves(tsched::ROLE_B, DIM) < 64 && tsched::issue_step(PB - 1) < KS, "vmcnt is 6 bits");
+    // Slots of the wave's ring of A fragments (qs_steps_il keeps RING - 1 reads in flight).  Measured
+    // (profiles/dense_scan_ring.md): with the old k-loop four and six reads in flight gave the same step
+    // time and the same pace of a wave that runs alone, so depth is not what the k-loop waits for; 5 / 6
+    // slots keep the four reads in flight the kernel had, and one more at dim 512 where registers are free.
+    // Every instantiation of a row length compiles without scratch at this depth (<768, *, 16, true>: 254
+    // VGPRs); deeper rings under qs_steps_il were not measured.
+    static constexpr int RING = DIM == 512 ? 6 : 5;
 };
 
+// The stamped build of dense_scan_f16qs (PROF; thr_dense_scan_stamps_f16 without THR_DENSE_F16=q at
+// dim <= 768): every wave takes s_memtime at the points QS_T_* of each interval and folds the
+// differences at the interval's end into sums, written as 16 words per wave to
+// stamps[(block * 8 + wave) * 16 + QS_PH_*].  The values are consumed only at the fold, so no stamp
+// drains the fragment ring inside the interval (a pending s_memtime makes a counted lgkmcnt wait reach
+// one slot further at the most).  Group A has no counted wait (0); group B's emit of the previous
+// tile is QS_PH_EMIT and its fill latency -- what of barrier release .. first fragment in a register
+// is not its emit -- QS_PH_FILL; the emit of B's last tile, after the loop, is not counted.
+enum { QS_T_START, QS_T_WAIT, QS_T_BAR, QS_T_EMIT_B, QS_T_FILL, QS_T_Q1, QS_T_Q2, QS_T_Q3, QS_T_K, QS_T_END, QS_T_N };
+enum { QS_PH_WAIT = 0,    // counted vmcnt wait for the wave's own pieces (B)
+       QS_PH_BARRIER = 1, // s_barrier, arrival to release
+       QS_PH_FILL = 2,    // release (B: end of its emit) to the first A fragment in a register
+       QS_PH_Q0 = 3,      // k-loop, quarters of KS steps: QS_PH_Q0 .. QS_PH_Q0 + 3
+       QS_PH_EMIT = 7,
+       QS_PH_INTERVALS = 8, QS_PH_LOOP = 9, QS_PH_HW_ID = 10, QS_PH_N = 16 };
+template <bool PROF>
+struct QsClock {
+    __device__ __forceinline__ void init() {}
+    template <int J> __device__ __forceinline__ void at() {}
+    template <int J, int K> __device__ __forceinline__ void same() {}
+    __device__ __forceinline__ void fold() {}
+    __device__ __forceinline__ void write(unsigned long long*, int, int64_t) const {}
+};
+template <>
+struct QsClock<true> {
+    unsigned long long t[QS_T_N], sum[QS_PH_INTERVALS], t0;
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int j = 0; j < QS_PH_INTERVALS; ++j) sum[j] = 0;
+        t[QS_T_END] = t0 = __builtin_amdgcn_s_memtime();
+    }
+    template <int J> __device__ __forceinline__ void at() { t[J] = __builtin_amdgcn_s_memtime(); }
+    template <int J, int K> __device__ __forceinline__ void same() { t[J] = t[K]; }   // point J not taken: = K
+    // end of an interval (t[QS_T_END] taken): the phases, and the next interval's start
+    __device__ __forceinline__ void fold() {
+        sum[QS_PH_WAIT] += t[QS_T_WAIT] - t[QS_T_START];
+        sum[QS_PH_BARRIER] += t[QS_T_BAR] - t[QS_T_WAIT];
+        sum[QS_PH_FILL] += t[QS_T_FILL] - t[QS_T_EMIT_B];
+        sum[QS_PH_Q0 + 0] += t[QS_T_Q1] - t[QS_T_FILL];
+        sum[QS_PH_Q0 + 1] += t[QS_T_Q2] - t[QS_T_Q1];
+        sum[QS_PH_Q0 + 2] += t[QS_T_Q3] - t[QS_T_Q2];
+        sum[QS_PH_Q0 + 3] += t[QS_T_K] - t[QS_T_Q3];
+        sum[QS_PH_EMIT] += (t[QS_T_EMIT_B] - t[QS_T_BAR]) + (t[QS_T_END] - t[QS_T_K]);
+    }
+    // one lane of the wave, at the end of the launch
+    __device__ __forceinline__ void write(unsigned long long* stamps, int wave_of_launch, int64_t intervals) const {
+        unsigned long long* o = stamps + (int64_t)wave_of_launch * QS_PH_N;
+        for (int j = 0; j < QS_PH_INTERVALS; ++j) o[j] = sum[j];
+        o[QS_PH_INTERVALS] = (unsigned long long)intervals;
+        o[QS_PH_LOOP] = __builtin_amdgcn_s_memtime() - t0;
+        o[QS_PH_HW_ID] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_REG_HW_ID
+        for (int j = QS_PH_HW_ID + 1; j < QS_PH_N; ++j) o[j] = 0;
+    }
+};
+// every MFMA issued so far stays in front of what follows (a stamp)
+template <int SHAPE>
+__device__ __forceinline__ void qs_pin(QAcc<SHAPE>& acc) {
+    if constexpr (SHAPE == 32) asm volatile("" : "+v"(acc.v));
+    else asm volatile("" : "+v"(acc.t[0]), "+v"(acc.t[1]), "+v"(acc.t[2]), "+v"(acc.t[3]));
+}
+// QTileHook with the quarter stamps of the stamped build
+template <int PB, int KS>
+struct QTileStampHook {
+    template <int S, typename Issue, int SHAPE>
+    static __device__ __forceinline__ void after(Issue& issue_piece, QAcc<SHAPE>& acc, QsClock<true>& clk) {
+        QTileHook<PB>::template after<S>(issue_piece);
+        if constexpr ((S + 1) % (KS / 4) == 0 && S + 1 < KS) {
+            qs_pin(acc);
+            clk.template at<QS_T_Q1 + (S + 1) / (KS / 4) - 1>();
+        }
+    }
+};
+
+// The two kernels -- the product one and its stamped build (PROF; MODE_FILTER; see QsClock) -- are
+// defined behind their common body, qs_scan.
 template <int DIM, int MODE, int SHAPE = 32, bool COLL = true>
 __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
     const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
     int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
     int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
     float* __restrict__ sample,
-    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries) {
+    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries);
+
+template <int DIM, int MODE, int SHAPE, bool COLL, bool PROF>
+__device__ __forceinline__ void qs_scan(
+    const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
+    int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
+    int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
+    float* __restrict__ sample,
+    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries,
+    unsigned long long* __restrict__ stamps) {
+    static_assert(!PROF || MODE == MODE_FILTER, "the stamped build is the filter scan");
     using C = QStag<DIM>;
     using A = QAcc<SHAPE>;
-    constexpr int KS = C::KS, PB = C::PB;
+    constexpr int KS = C::KS, PB = C::PB, RING = C::RING;
+    static_assert(KS % 4 == 0 && RING >= 3 && RING <= KS, "quarter stamps; qs_steps_il refills the slot read a step ago");
     static_assert(A::QW == 32 && A::NQB * KS / 2 == KS, "32 queries per wave: KS fragments in both shapes");
     extern __shared__ f32x4 lds_rows[];  // NBUF whole-tile buffers
 
@@ -689,8 +828,16 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
         }
     }
     A acc;
-    f32x4 a[Q_RING];
+    f32x4 a[RING];
     auto no_piece = [](auto) {};
+    QsClock<PROF> clk;
+    clk.init();
+    // the first A fragment is in a register (the stamped build only: the k-loop waits for it anyway)
+#define QS_STAMP_FILL()                                                             \
+    if constexpr (PROF) {                                                           \
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(RING - 1) : "memory");          \
+        clk.template at<QS_T_FILL>();                                               \
+    }
     if (!ts::multiplies(role)) {
         // ---- a wave whose 32 queries are all padding (small batches: one query keeps 7 of the 8
         // waves here): same barriers as a working wave of its group, and for an issuer the same
@@ -715,13 +862,26 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
         int buf = 0;   // buffer of tile i
 #pragma unroll 1
         for (int64_t i = 0; i < ts::barriers(ts::ROLE_A, n_mine); ++i) {
+            clk.template same<QS_T_START, QS_T_END>();
+            clk.template same<QS_T_WAIT, QS_T_END>();
             __builtin_amdgcn_s_barrier();   // barrier i
+            clk.template at<QS_T_BAR>();
+            clk.template same<QS_T_EMIT_B, QS_T_BAR>();
             const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
             qs_fill<0, KS>(a, abase);
             acc.zero();
-            qs_steps<0, KS, 0, KS, QTileHook<0>>(a, bq, acc, abase, no_piece);
+            QS_STAMP_FILL()
+            if constexpr (PROF) {
+                qs_steps_il<0, KS, KS, QTileStampHook<0, KS>>(a, bq, acc, abase, no_piece, acc, clk);
+                qs_pin(acc);
+            } else {
+                qs_steps_il<0, KS, KS, QTileHook<0>>(a, bq, acc, abase, no_piece);
+            }
+            clk.template at<QS_T_K>();
             buf = ts::next_buffer(buf, DIM);
             QS_EMIT(i)
+            clk.template at<QS_T_END>();
+            clk.fold();
         }
     } else {
         // ---- group B: emit tile t - 1 (under A's MFMAs), then multiply tile t and request tile
@@ -729,27 +889,66 @@ __global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
         int buf = 0;   // buffer of tile i
 #pragma unroll 1
         for (int64_t i = 0; i < ts::barriers(ts::ROLE_B, n_mine); ++i) {
+            clk.template same<QS_T_START, QS_T_END>();
+            if constexpr (PROF) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_B) : "memory");
+                clk.template at<QS_T_WAIT>();
+            }
             QS_SYNC_B()   // barrier i
+            clk.template at<QS_T_BAR>();
             if (i > 0) {
                 QS_EMIT(i - 1)
             }
+            clk.template at<QS_T_EMIT_B>();
             const int ibuf = ts::prev_buffer(buf, DIM);   // tile i - 1's buffer
             const f32x4* src = piece_src(ts::issue_tile(i, DIM));
             auto issue_piece = [&](auto P) { dma(src, ibuf, decltype(P)::value); };
             const uint32_t abase = lds_base + buf * C::TILE_BYTES + lane * 16;
             qs_fill<0, KS>(a, abase);
             acc.zero();
-            qs_steps<0, KS, 0, KS, QTileHook<PB>>(a, bq, acc, abase, issue_piece);
+            QS_STAMP_FILL()
+            if constexpr (PROF) {
+                qs_steps_il<0, KS, KS, QTileStampHook<PB, KS>>(a, bq, acc, abase, issue_piece, acc, clk);
+                qs_pin(acc);
+            } else {
+                qs_steps_il<0, KS, KS, QTileHook<PB>>(a, bq, acc, abase, issue_piece);
+            }
+            clk.template at<QS_T_K>();
+            clk.template same<QS_T_END, QS_T_K>();
+            clk.fold();
             buf = ts::next_buffer(buf, DIM);
         }
         if (n_mine > 0) {
             QS_EMIT(n_mine - 1)
         }
     }
+#undef QS_STAMP_FILL
 #undef QS_SYNC_B
 #undef QS_EMIT
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // nothing may still be landing in LDS
     QS_WAVE_WRITE_OUT()
+    if (lane == 0) clk.write(stamps, blockIdx.x * QS_NW + wave, n_mine);
+}
+
+template <int DIM, int MODE, int SHAPE, bool COLL>
+__global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs(
+    const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
+    int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
+    int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
+    float* __restrict__ sample,
+    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries) {
+    qs_scan<DIM, MODE, SHAPE, COLL, false>(packed, qfrag, n_qtiles, n_tiles, tile_stride, tau, seg_cnt, cand, seg_cap,
+                                           sample, doc_coll, query_coll, n_queries, nullptr);
+}
+template <int DIM, int SHAPE, bool COLL>
+__global__ __launch_bounds__(QS_NW * 64) void dense_scan_f16qs_stamps(
+    const f32x4* __restrict__ packed, const f32x4* __restrict__ qfrag, int n_qtiles,
+    int64_t n_tiles, int64_t tile_stride, const float* __restrict__ tau,
+    int* __restrict__ seg_cnt, Cand* __restrict__ cand, int seg_cap,
+    const int32_t* __restrict__ doc_coll, const int32_t* __restrict__ query_coll, int n_queries,
+    unsigned long long* __restrict__ stamps) {
+    qs_scan<DIM, MODE_FILTER, SHAPE, COLL, true>(packed, qfrag, n_qtiles, n_tiles, tile_stride, tau, seg_cnt, cand, seg_cap,
+                                                 nullptr, doc_coll, query_coll, n_queries, stamps);
 }
 
 #undef QS_WAVE_WRITE_OUT
