@@ -17,6 +17,25 @@
  *   - doc / chunk / entity ids are indices into the caller's arrays; outputs
  *     add ``id_base`` so a document-sharded index reports global ids;
  *   - total order of every ranked output: (score descending, id ascending).
+ *
+ * WORKSPACES.  An entry point that takes ``workspace`` / ``workspace_bytes`` carves the first
+ * thr_*_workspace_bytes(...) bytes of it (the size function declared with the entry, called with the
+ * same shape) into areas whose offsets follow from the shape of the call.  The workspace's contents on
+ * entry are never read: every area is either cleared by the entry point itself or written by one of
+ * its kernels before another reads it, on every path (pruned slices, skipped sweeps, padding queries,
+ * empty scopes, overflowed lists), so a caller may hand in memory that holds anything -- zeros, 0xFF,
+ * what an earlier call of any shape left there -- and gets the same bits.  Nothing outside
+ * [workspace, workspace + thr_*_workspace_bytes(...)) is written, however large workspace_bytes is.
+ * Two deliberate exceptions, both of the dense channel: thr_dense_finish_f16 reads what
+ * thr_dense_shortlist_f16 left in the same workspace (the candidate lists, the thresholds, the query
+ * image: the pair is one search), and the scan probes / stamps (thr_dense_scan_probe,
+ * thr_dense_scan_probe_f16, thr_dense_scan_stamps_f16) read the previous call's tau and query image.
+ * DESIGN.md ("Workspace contract") lists every area with the memset or kernel that writes it.
+ * OUTPUTS.  Every output element an entry point documents is written by it.  Where a call reports
+ * how much of an output array it used, the elements behind that length are not written and stay as
+ * the caller left them: ids_out / pay_out behind *nnz_out, ``rows`` behind min(rowptr[n_preds], cap),
+ * tok_doc / tok_term behind *n_total, unknown_off / unknown_len / unknown_term behind *n_unknown,
+ * new_ptr behind entry *n_new, new_bytes behind min(*n_new_bytes, new_bytes_capacity).
  */
 #ifndef THR_HIP_H
 #define THR_HIP_H

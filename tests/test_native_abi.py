@@ -302,3 +302,78 @@ def test_workspace_size_accessors_forward_their_arguments(monkeypatch):
     for f in sorted(os.listdir(pkg)):
         if f.endswith(".py") and f != "_native.py":
             assert not re.search(r"\.thr_[a-z0-9_]+\(", open(os.path.join(pkg, f)).read()), f
+
+
+# ----------------------------------------------------------- every entry with a workspace takes the caller's
+def workspace_takers():
+    """The thr_* entry points whose prototype in thr_hip.h has ``void *workspace, size_t workspace_bytes``."""
+    text, _ = header_text()
+    out = []
+    for m in re.finditer(r"\b(thr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text):
+        params = " ".join(m.group(2).split())
+        if re.search(r"void \*\s*workspace, size_t workspace_bytes", params):
+            out.append(m.group(1))
+    return sorted(out)
+
+
+def test_every_binding_of_an_entry_with_a_workspace_has_a_workspace_parameter():
+    """thr_hip.h gives 22 entry points a workspace; the binding of each (same name without thr_) takes
+    ``workspace``: none allocates behind the caller's back without a way to hand one in."""
+    import inspect
+    N = T._native
+    takers = workspace_takers()
+    assert len(takers) == 22 and "thr_dense_topk_exact" in takers and "thr_csr_compact" in takers
+    for entry in takers:
+        fn = getattr(N, entry[4:], None)
+        assert fn is not None, f"_native has no binding named {entry[4:]}"
+        assert "workspace" in inspect.signature(fn).parameters, f"_native.{entry[4:]} takes no workspace"
+
+
+class SizedLibrary(RecordingLibrary):
+    """RecordingLibrary whose size functions answer 4096 bytes."""
+
+    def __getattr__(self, name):
+        if name.endswith("_workspace_bytes"):
+            return lambda *args: 4096
+        return super().__getattr__(name)
+
+
+def test_the_six_bindings_that_allocated_inside_hand_the_callers_workspace_through(monkeypatch):
+    """dense_topk_exact, dense_topk_rows, scope_resolve, scope_resolve_clauses, lexical_build and csr_compact:
+    with ``workspace`` of at least the size function's bytes the library gets that pointer and its byte count
+    (the last two arguments in front of the stream, as the header orders them); a smaller one or None is
+    replaced by a fresh allocation of the size -- the behaviour before, and _workspace's rule for every call."""
+    torch = pytest.importorskip("torch")
+    np = pytest.importorskip("numpy")
+    N = T._native
+    lib = SizedLibrary()
+    monkeypatch.setattr(N, "load", lambda build_if_missing=True: lib)
+    monkeypatch.setattr(N, "_dev", lambda t, dtype, name, ndim=None: 0 if t is None else t.data_ptr())   # (host tensors)
+    monkeypatch.setattr(N, "_stream", lambda: 77)
+    f32, f64, i32, i64 = torch.float32, torch.float64, torch.int32, torch.int64
+    docs, dn, q = torch.zeros((6, 8), dtype=f32), torch.ones(6, dtype=f64), torch.zeros((2, 8), dtype=f32)
+    cols = [torch.zeros(6, dtype=i32)]
+    calls = {
+        "thr_dense_topk_exact": lambda ws: N.dense_topk_exact(docs, dn, q, 3, workspace=ws),
+        "thr_dense_topk_rows": lambda ws: N.dense_topk_rows(docs, dn, q, 3, torch.zeros(2, dtype=i64), torch.zeros(4, dtype=i32),
+                                                            torch.zeros(2, dtype=i32), workspace=ws),
+        "thr_scope_resolve": lambda ws: N.scope_resolve(cols, torch.zeros((2, 1), dtype=i32), workspace=ws),
+        "thr_scope_resolve_clauses": lambda ws: N.scope_resolve_clauses(cols, np.zeros((2, 1, 4), dtype=np.int32), workspace=ws),
+        "thr_lexical_build": lambda ws: N.lexical_build(torch.zeros(5, dtype=i32), torch.zeros(5, dtype=i32), None, 6, 4,
+                                                        workspace=ws),
+        "thr_csr_compact": lambda ws: N.csr_compact(torch.zeros(3, dtype=i64), torch.zeros(5, dtype=i32), None,
+                                                    torch.zeros(4, dtype=i32), workspace=ws),
+    }
+    assert sorted(calls) == sorted(set(calls) & set(workspace_takers()))
+    for entry, call in calls.items():
+        for ws, mine in ((torch.empty(4096 + 512, dtype=torch.uint8), True), (torch.empty(1024, dtype=torch.int32), True),
+                         (torch.empty(4095, dtype=torch.uint8), False), (None, False)):
+            lib.calls.clear()
+            call(ws)
+            (name, a), = [c for c in lib.calls if not c[0].endswith("_workspace_bytes")]
+            assert name == entry and a[-1] == 77
+            if mine:
+                assert a[-3:-1] == (ws.data_ptr(), ws.numel() * ws.element_size()), f"{entry}: the caller's workspace did not arrive"
+            else:
+                assert a[-2] == 4096 and a[-3] != 0 and (ws is None or a[-3] != ws.data_ptr()), \
+                    f"{entry}: a workspace that is too small (or none) is replaced by one of the size function's bytes"

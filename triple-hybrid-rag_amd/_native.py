@@ -308,9 +308,12 @@ def dense_topk(docs, dnorm, inv_norm, queries, k: int, kprime: int, id_base: int
     return S, I, cnt, flg
 
 
-def dense_topk_exact(docs, dnorm, queries, k: int, id_base: int = 0, doc_coll=None, query_coll=None):
+def dense_topk_exact(docs, dnorm, queries, k: int, id_base: int = 0, doc_coll=None, query_coll=None,
+                     workspace: Optional[torch.Tensor] = None):
+    """thr_dense_topk_exact -> (scores, ids, counts, flags); ``workspace``: reused when it holds
+    thr_dense_exact_workspace_bytes(n_docs, nq) bytes (_workspace), whatever it holds."""
     pd, pq, pn, _, _, n, d, nq = _dense_operands(docs, queries, dnorm)
-    ws, nbytes = _workspace(None, int(load().thr_dense_exact_workspace_bytes(n, nq)), docs.device)
+    ws, nbytes = _workspace(workspace, int(load().thr_dense_exact_workspace_bytes(n, nq)), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     pdc, pqc = _coll(doc_coll, query_coll, n, nq)
     _check(load().thr_dense_topk_exact(pd, pn, n, d, id_base, pq, nq, k, pdc, pqc, S.data_ptr(),
@@ -534,11 +537,11 @@ def dense_scan_stamps_f16(docs16, n_docs: int, queries_n: int, workspace: torch.
 
 # --------------------------------------------------------------------- f1
 def lexical_build(doc: torch.Tensor, term: torch.Tensor, tf: Optional[torch.Tensor], n_docs: int,
-                  n_vocab: int):
+                  n_vocab: int, workspace: Optional[torch.Tensor] = None):
     """Tokenised rows on the device -> (rowptr i64 [V+1], post_doc i32 [nnz], post_tf i32 [nnz],
     doclen f32 [n_docs], df i64 [V]): the CSR inverted index of this shard.  ``tf`` None: one
     entry per token occurrence.  One host read-back at the end (the number of postings, to cut
-    the posting arrays to size)."""
+    the posting arrays to size).  ``workspace``: reused when large enough (_workspace)."""
     pdoc = _dev(doc, torch.int32, "doc", 1)
     pterm = _dev(term, torch.int32, "term", 1)
     ptf = _dev(tf, torch.int32, "tf", 1) if tf is not None else None
@@ -554,7 +557,7 @@ def lexical_build(doc: torch.Tensor, term: torch.Tensor, tf: Optional[torch.Tens
     nnz = torch.zeros(1, dtype=torch.int64, device=dev)
     if n == 0:
         return rowptr.zero_(), post_doc[:0], post_tf[:0], doclen.zero_(), df.zero_()
-    ws, nbytes = _workspace(None, int(load().thr_lexical_build_workspace_bytes(n, n_vocab)), dev)
+    ws, nbytes = _workspace(workspace, int(load().thr_lexical_build_workspace_bytes(n, n_vocab)), dev)
     _check(load().thr_lexical_build(pdoc, pterm, ptf, n, n_docs, n_vocab, rowptr.data_ptr(),
                                     post_doc.data_ptr(), post_tf.data_ptr(), doclen.data_ptr(),
                                     df.data_ptr(), nnz.data_ptr(), ws.data_ptr(), nbytes, _stream()),
@@ -608,7 +611,7 @@ def csr_append(rowptr_a, a0, a1, rowptr_b, b0, b1, out0=None, out1=None):
     return rowptr_out, out0, (out1 if b1 is not None else None), nnz
 
 
-def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out=None):
+def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out=None, workspace=None):
     """Order-preserving removal of entries from a CSR, with renumbering (thr_csr_compact): entry p
     is kept iff ``remap[ids[p] - id_base] >= 0`` (ids outside [id_base, id_base + len(remap)) are
     dropped) and is written as ``remap[...] + id_base``.  ``rowptr`` int64 [rows + 1], ``ids`` int32
@@ -616,7 +619,8 @@ def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out
     the survivors).  ``ids_out`` / ``pay_out``: capacity-reserved 1-d destinations of the payloads'
     dtypes with room for all nnz entries (the kept count is not known before the call; allocated
     when None) -- only the kept entries are written.  One host read-back at the end (the kept
-    count).  -> (rowptr_out, ids_out, pay_out or None, nnz_kept)."""
+    count).  ``workspace``: reused when large enough (_workspace).
+    -> (rowptr_out, ids_out, pay_out or None, nnz_kept)."""
     # (shapes and dtypes first: they are refused on any device, before a pointer is taken)
     rows, nnz = rowptr.shape[0] - 1, ids.shape[0]
     if rows < 1:
@@ -640,7 +644,7 @@ def csr_compact(rowptr, ids, pay, remap, id_base: int = 0, ids_out=None, pay_out
         pay_out = torch.empty(nnz, dtype=pay.dtype, device=dev)
     rowptr_out = torch.empty(rows + 1, dtype=torch.int64, device=dev)
     kept = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws, nbytes = _workspace(None, int(load().thr_csr_compact_workspace_bytes(rows, nnz)), dev)
+    ws, nbytes = _workspace(workspace, int(load().thr_csr_compact_workspace_bytes(rows, nnz)), dev)
     cap = ids_out.shape[0] if pay is None else min(ids_out.shape[0], pay_out.shape[0])
     _check(load().thr_csr_compact(prp, rows, nnz, pid if nnz else None,
                                   _dev(pay, pay.dtype, "pay", 1) if nnz and pay is not None else None,
@@ -729,13 +733,14 @@ def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool
 
 
 # --------------------------------------------------------------------- f4
-def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = True, rows_out=None):
+def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = True, rows_out=None, workspace=None):
     """thr_scope_resolve: ``cols`` a sequence of C int32 [n_docs] device columns, ``preds`` int32
     [P, C] (-1 = any value, below -1 = no row).  -> (rowptr i64 [P + 1], rows i32 [cap], labels i32
     [n_docs] or None, overlap i32 [1] or None).  ``cap`` (default n_docs; 0 = counts and labels only)
     is the room for the lists: rowptr is complete either way and the caller compares rowptr[P] with
     cap before it reads ``rows``.  ``rows_out``: an int32 buffer of at least cap entries to write the
-    lists into (returned as ``rows``; nothing behind cap is written).  No host read-back."""
+    lists into (returned as ``rows``; nothing behind cap is written).  ``workspace``: reused when large
+    enough (_workspace).  No host read-back."""
     cols, n = _scope_columns("scope_resolve", cols)
     if preds.dim() != 2 or preds.shape[1] != len(cols):
         raise NativeError(f"scope_resolve: preds must be [P, {len(cols)}]")
@@ -745,7 +750,8 @@ def scope_resolve(cols, preds, cap: Optional[int] = None, want_labels: bool = Tr
     cap = _scope_cap("scope_resolve", cap, n)
     lib = load()
     return _scope_call("scope_resolve", lib.thr_scope_resolve, lib.thr_scope_resolve_workspace_bytes, cols, n,
-                       lambda: (_dev(preds, torch.int32, "preds", 2), P), P, cap, want_labels, preds.device, rows_out)
+                       lambda: (_dev(preds, torch.int32, "preds", 2), P), P, cap, want_labels, preds.device, rows_out,
+                       workspace)
 
 
 def _scope_columns(what: str, cols):
@@ -768,7 +774,7 @@ def _scope_cap(what: str, cap: Optional[int], n: int) -> int:
 
 
 def _scope_call(what: str, entry, workspace_bytes, cols, n: int, table, P: int, cap: int, want_labels: bool, dev,
-                rows_out=None):
+                rows_out=None, workspace=None):
     """The device half the two scope calls share: column pointers, outputs, workspace and the call of
     ``entry`` (thr_<what>; ``workspace_bytes`` its size function).  ``table()`` -> the entry's
     predicate-table arguments (pointers of device tensors and counts), taken behind the columns'."""
@@ -782,7 +788,7 @@ def _scope_call(what: str, entry, workspace_bytes, cols, n: int, table, P: int, 
     rows = torch.empty(cap, dtype=torch.int32, device=dev) if rows_out is None else rows_out
     labels = torch.empty(n, dtype=torch.int32, device=dev) if want_labels else None
     overlap = torch.empty(1, dtype=torch.int32, device=dev) if want_labels else None
-    ws, nbytes = _workspace(None, workspace_bytes(n, P), dev)
+    ws, nbytes = _workspace(workspace, workspace_bytes(n, P), dev)
     _check(entry(ptrs, len(cols), n, *table, rowptr.data_ptr(), rows.data_ptr() if cap else None, cap,
                  labels.data_ptr() if want_labels else None, overlap.data_ptr() if want_labels else None,
                  ws.data_ptr(), nbytes, _stream()), f"thr_{what}")
@@ -825,10 +831,12 @@ def scope_check_clauses(clauses, set_values, n_cols: int):
     return tab, sv
 
 
-def scope_resolve_clauses(cols, clauses, set_values=None, cap: Optional[int] = None, want_labels: bool = True):
+def scope_resolve_clauses(cols, clauses, set_values=None, cap: Optional[int] = None, want_labels: bool = True,
+                          workspace=None):
     """thr_scope_resolve_clauses: scope_resolve over predicates of CLAUSES.  ``clauses`` int32 [P, C, 4]
     and ``set_values`` int32 [n] are HOST numpy arrays: they are validated here (scope_check_clauses:
-    the device cannot be asked) and uploaded.  -> scope_resolve's (rowptr, rows, labels, overlap)."""
+    the device cannot be asked) and uploaded.  ``workspace``: as scope_resolve's.
+    -> scope_resolve's (rowptr, rows, labels, overlap)."""
     cols, n = _scope_columns("scope_resolve_clauses", cols)
     if isinstance(clauses, torch.Tensor) or isinstance(set_values, torch.Tensor):
         raise NativeError("scope_resolve_clauses: the clause table and the set values are host numpy arrays")
@@ -842,13 +850,15 @@ def scope_resolve_clauses(cols, clauses, set_values=None, cap: Optional[int] = N
     return _scope_call("scope_resolve_clauses", lib.thr_scope_resolve_clauses,
                        lib.thr_scope_resolve_clauses_workspace_bytes, cols, n,
                        lambda: (dtab.data_ptr(), P, dsv.data_ptr() if dsv is not None else None, sv.shape[0]), P, cap,
-                       want_labels, dev)
+                       want_labels, dev, None, workspace)
 
 
-def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_base: int = 0):
+def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_base: int = 0,
+                    workspace: Optional[torch.Tensor] = None):
     """thr_dense_topk_rows: exact cosine top-k of every query over the row list of its scope
     (rowptr i64 [P + 1] / rows i32 of scope_resolve, query_scope i32 [nq] in [0, P), anything else =
-    no rows).  -> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
+    no rows).  ``workspace``: reused when large enough (_workspace).
+    -> (scores f64 [nq,k], ids i64 [nq,k], counts i32 [nq], flags i32 [nq])."""
     pd, pq, pn, _, _, n, d, nq = _dense_operands(docs, queries, dnorm)
     P = rowptr.shape[0] - 1
     if not 1 <= P <= THR_SCOPE_MAX_PREDS:
@@ -860,7 +870,7 @@ def dense_topk_rows(docs, dnorm, queries, k: int, rowptr, rows, query_scope, id_
     prp = _dev(rowptr, torch.int64, "rowptr", 1)
     prw = _dev(rows, torch.int32, "rows", 1)
     pqs = _dev(query_scope, torch.int32, "query_scope", 1)
-    ws, nbytes = _workspace(None, int(load().thr_dense_topk_rows_workspace_bytes(nq, P, k)), docs.device)
+    ws, nbytes = _workspace(workspace, int(load().thr_dense_topk_rows_workspace_bytes(nq, P, k)), docs.device)
     S, I, cnt, flg = _alloc_out(nq, k, docs.device)
     _check(load().thr_dense_topk_rows(pd, pn, n, d, int(id_base), pq, nq, k, prp, prw if rows.shape[0] else None,
                                       rows.shape[0], P, pqs, S.data_ptr(), I.data_ptr(), cnt.data_ptr(),
