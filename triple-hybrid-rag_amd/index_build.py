@@ -29,7 +29,8 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
-from .backend import CorpusStore, tokenize
+from .index_text import tokenize
+from .store import CorpusStore
 
 K1, B = 1.2, 0.75
 

@@ -2,8 +2,8 @@
 
 The reference looks a query's keywords up one at a time (``rag_entities ... ILIKE '%kw%' LIMIT limit //
 len(keywords)``, first 5 keywords, src/voice_agent/rag2/graph_search.py:151-176); the per-query host
-restatement is ``GpuIndexClient.find_entities``.  ``EntitySearch`` is the part of ``GpuIndex`` that
-holds a device copy of the lower-cased entity names (``set_entity_names``: index set-up) and resolves
+restatement is ``match_names`` (``GpuIndexClient.find_entities``).  ``EntitySearch`` is the part of
+``GpuIndex`` that holds a device copy of the lower-cased entity names (``set_entity_names``) and resolves
 the keyword lists of a batch with one thr_entity_match call (``find_entities``) into the int32
 [nq, 16] seed table ``graph_search`` / ``retrieve_batch(query_seeds=)`` take.
 
@@ -82,6 +82,51 @@ def plan_needles(keyword_lists: Sequence[Sequence[str]], limit: int = 20) -> Nee
         needles[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
         lens[i] = len(b)
     return NeedlePlan(needles, lens, qn, per, long_rows)
+
+
+def name_trigrams(entity_names: Sequence[str]):
+    """-> (sorted trigram codes, entity of each, lowered names): a keyword intersects lists, no scan of 2.5M names."""
+    names = [nm.lower() for nm in entity_names]
+    cp = np.frombuffer("\x00".join(names).encode("utf-32-le"), dtype=np.uint32).astype(np.int64)
+    ent = np.repeat(np.arange(len(names), dtype=np.int64),
+                    np.fromiter((len(nm) + 1 for nm in names), dtype=np.int64, count=len(names)))[:len(cp)]
+    ok = np.ones(max(len(cp) - 2, 0), dtype=bool)
+    for off in range(3):   # a trigram must not straddle the separator between two names
+        ok &= cp[off:len(cp) - 2 + off] != 0
+    code = (cp[:-2] * 1114112 + cp[1:-1]) * 1114112 + cp[2:] if len(cp) > 2 else cp[:0]
+    code, e3 = code[ok], ent[:len(ok)][ok]
+    order = np.argsort(code, kind="stable")      # (entities stay ascending inside a trigram)
+    return code[order], e3[order], names
+
+
+def match_names(trigrams, keywords: Sequence[str], limit: int = 20) -> List[int]:
+    """``GpuIndexClient.find_entities`` over ``name_trigrams``' index (a keyword under 3 characters: the plain scan)."""
+    codes, ents, names = trigrams
+    per = max(1, limit // len(keywords))
+    found: List[int] = []
+    for kw in keywords[:5]:
+        needle, hits = kw.lower(), 0
+        if len(needle) >= 3:
+            cp = np.frombuffer(needle.encode("utf-32-le"), dtype=np.uint32).astype(np.int64)
+            tri = np.unique((cp[:-2] * 1114112 + cp[1:-1]) * 1114112 + cp[2:])
+            lo, hi = np.searchsorted(codes, tri, "left"), np.searchsorted(codes, tri, "right")
+            cand = None
+            for j in np.argsort(hi - lo):            # rarest trigram first
+                part = np.unique(ents[lo[j]:hi[j]])
+                cand = part if cand is None else cand[np.isin(cand, part, assume_unique=True)]
+                if len(cand) == 0:
+                    break
+            pool = cand.tolist() if cand is not None else []
+        else:
+            pool = range(len(names))                 # too short for a trigram: the plain scan
+        for e in pool:
+            if needle in names[e]:
+                if e not in found:
+                    found.append(e)
+                hits += 1
+                if hits == per:
+                    break
+    return found[: N.THR_GRAPH_MAX_SEEDS]
 
 
 class EntitySearch:

@@ -2,7 +2,7 @@
 
 The lexical channel takes term ids; the reference hands text to PostgreSQL (``plainto_tsquery(p_query)`` in
 rag2_lexical_search, the text column of ingest.py's child-chunk insert) and the host restatement is
-``backend.tokenize`` (``\\w+`` over ``text.lower()``), a lookup in ``store.vocab`` and
+``tokenize`` below (``\\w+`` over ``text.lower()``; re-exported as ``backend.tokenize``), a lookup in ``store.vocab`` and
 ``GpuIndexClient._query_terms``.  ``TextSearch`` is the part of ``GpuIndex`` that holds a device copy of the
 vocabulary (``set_vocabulary`` / ``grow_vocabulary``: an open-addressing hash table beside the keys' bytes)
 and turns the texts of a batch into token rows (``text_rows``: thr_text_tokens) or into the int32 [nq, 32]
@@ -38,13 +38,16 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .store import number_tokens  # noqa: F401 (the one host numbering; the store needs it without a device)
 
-_TOKEN = re.compile(r"[\w]+", re.UNICODE)       # backend.tokenize's
+_TOKEN = re.compile(r"[\w]+", re.UNICODE)
 _WORD = re.compile(r"\w", re.UNICODE)
 CONTEXTS = ("a{}a", " {} ", "a{}", "{}a")       # between letters, between spaces, letter-left, letter-right
 
 
-def _lower_words(text: str) -> List[str]:
+def tokenize(text: str) -> List[str]:
+    """Lower-cased word tokens (the reference leaves tokenisation to PostgreSQL's 'portuguese' text-search configuration,
+    which is not reproduced: no stemming).  ``backend.tokenize`` is this object; ``TextTable.default()`` is built from it."""
     return _TOKEN.findall(text.lower())
 
 
@@ -107,16 +110,16 @@ class TextTable:
                 entries[cp] = cp | N.THR_TEXT_EXC
                 continue
             entries[cp] = ord(low) | (N.THR_TEXT_WORD if _WORD.fullmatch(low) else 0)
-        table = TextTable(entries, _lower_words)
+        table = TextTable(entries, tokenize)
         # context-dependent lowerings cannot be seen per character: a code point for which the restatement
         # disagrees with the tokenizer in some context is exceptional too
         for cp in range(65536):
             if entries[cp] & N.THR_TEXT_EXC:
                 continue
             c = chr(cp)
-            if any(table.restate(ctx.format(c)) != _lower_words(ctx.format(c)) for ctx in CONTEXTS):
+            if any(table.restate(ctx.format(c)) != tokenize(ctx.format(c)) for ctx in CONTEXTS):
                 entries[cp] |= N.THR_TEXT_EXC
-        return TextTable(entries, _lower_words)
+        return TextTable(entries, tokenize)
 
     @staticmethod
     def from_char_map(fn: Callable[[str], str]) -> "TextTable":
@@ -142,7 +145,6 @@ def is_table_tokenizer(tokenizer) -> Optional[TextTable]:
 def tokenizer_table(tokenizer, needs: str) -> TextTable:
     """The analysis table a tokenizer stands for: ``backend.tokenize`` is ``TextTable.default()``, a table's
     ``.tokenize`` that table.  Any other is refused by name; ``needs`` begins the message (the caller's option)."""
-    from .backend import tokenize
     table = TextTable.default() if tokenizer is tokenize else is_table_tokenizer(tokenizer)
     if table is None:
         name = getattr(tokenizer, "__qualname__", None) or repr(tokenizer)
@@ -163,22 +165,6 @@ def pack_encoded(enc: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     if enc:
         np.cumsum(np.fromiter((len(b) for b in enc), dtype=np.int64, count=len(enc)), out=ptr[1:])
     return np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8), ptr
-
-
-def number_tokens(per_text_tokens, vocab: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray, List[str]]:
-    """THE host numbering: the token lists of a batch, one per text -> (doc int32 [T], term int32 [T], the new
-    terms in id order).  A token outside ``vocab`` gets the next id at its first sighting, in text order
-    (build_lexical's numbering; thr_vocab_grow's on the device); ``vocab`` itself is not changed."""
-    grown: Dict[str, int] = {}
-    doc, term = [], []
-    for d, tokens in enumerate(per_text_tokens):
-        for tok in tokens:
-            t = vocab.get(tok)
-            if t is None:
-                t = grown.setdefault(tok, len(vocab) + len(grown))
-            doc.append(d)
-            term.append(t)
-    return np.asarray(doc, dtype=np.int32), np.asarray(term, dtype=np.int32), list(grown)
 
 
 def vocab_capacity(n_terms: int) -> int:

@@ -41,8 +41,9 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .backend import CorpusStore, GpuIndexClient
+from .backend import GpuIndexClient
 from .distributed import gather_rows, gather_topk
+from .store import CorpusStore
 
 log = logging.getLogger(__name__)
 
