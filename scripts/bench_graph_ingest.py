@@ -9,6 +9,11 @@ the graph over all rows -- a lower bound of index_build.build_graph, which walks
 run-to-run spread of the "before" side.  Needs the GPU; prints one JSON line per measurement.
 
     python3 scripts/bench_graph_ingest.py [--n 1000000] [--queries 2048] [--batches 1,256,16384]
+    python3 scripts/bench_graph_ingest.py --delete [--n 1000000] [--queries 2048] [--share 0.01]
+
+--delete measures graph delete instead: --share of the entities removed with their cascade (relations in both
+directions, mentions, names) by GpuIndex.delete_graph, thr_csr_prune alone on both CSRs by device events, the
+same change by a rebuild over the surviving rows, and graph_search before and after.
 
 synth.build_graph draws its edges at random and keeps the few repeated ones; the index is built
 from the de-duplicated edge list (index_build.build_graph's canonical form), which the merge needs.
@@ -82,8 +87,103 @@ def search_ms(idx, seeds, reps):
     return [timed(lambda: idx.graph_search(seeds, 50, 2), 5)[2] for _ in range(reps)]
 
 
+HBM_PEAK_GBPS = 8000.0      # MI355X: 8 TB/s
+
+
+def prune_alone(lib, st, rowptr, ids, pay, remap, n_new, with_ids: bool):
+    """thr_csr_prune by device events on one CSR of the index -> (ms, bytes the three kernels move, kept)."""
+    rows, nnz = int(rowptr.shape[0]) - 1, int(ids.shape[0])
+    out = torch.empty(nnz, dtype=torch.int32, device="cuda")
+    pout = None if pay is None else torch.empty(nnz, dtype=pay.dtype, device="cuda")
+    rp_out = torch.empty(n_new + 1, dtype=torch.int64, device="cuda")
+    tail = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ws = torch.empty(max(N.csr_prune_workspace_bytes(rows, nnz), 8), dtype=torch.uint8, device="cuda")
+
+    def prune():
+        rc = lib.thr_csr_prune(rowptr.data_ptr(), rows, nnz, ids.data_ptr(), None if pay is None else pay.data_ptr(),
+                               remap.data_ptr(), n_new, remap.data_ptr() if with_ids else None, rows if with_ids else 0, 0,
+                               None, 0, None, rp_out.data_ptr(), out.data_ptr(), None if pout is None else pout.data_ptr(),
+                               nnz, None, tail.data_ptr(), tail.data_ptr() + 8, ws.data_ptr(), ws.numel(), st)
+        assert rc == 0, rc
+    prune()
+    _, _, ms = timed(prune, 20)
+    kept, status = (int(v) for v in tail.tolist())
+    assert status == 0
+    # count: ids in, keep words out; scatter: keep words and ids in, kept ids (and payload in and out) out;
+    # row pointers in and out, the row remap (the id remap is gathered: at least once per entry)
+    moved = nnz * 4 * 4 + kept * 4 * (1 + (2 if pay is not None else 0)) + rows * (8 + 4) + n_new * 8 + \
+        (nnz * 4 * 2 if with_ids else 0)
+    return ms, moved, kept
+
+
+def delete_main(a):
+    sg = synth.build_graph(a.n)
+    n_ent = synth.n_entities(a.n)
+    src, dst = edge_list((sg.ent_rowptr, sg.ent_col))
+    me, mc, mw = mention_list((None, None, sg.men_rowptr, sg.men_chunk, sg.men_conf))
+    g = host_graph(n_ent, src, dst, me, mc, mw)
+    names = [f"entity{e}" for e in range(n_ent)]
+    idx = T.GpuIndex()
+    idx.n_docs = a.n
+    idx.set_graph(*g).set_entity_names(names)
+    seeds_h = synth.graph_queries(a.queries, a.n)
+    before = search_ms(idx, torch.from_numpy(seeds_h).cuda(), a.repeats)
+    print(json.dumps({"n": a.n, "entities": n_ent, "edges": int(len(g[1])), "mentions": int(len(g[3])),
+                      "graph_search_ms_before": [round(t, 3) for t in before]}), flush=True)
+    rng = np.random.default_rng(7)
+    gone = rng.choice(n_ent, max(1, int(n_ent * a.share)), replace=False)
+    keep = np.ones(n_ent, dtype=bool)
+    keep[gone] = False
+    remap_h = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+    remap, n_new = torch.from_numpy(remap_h).cuda(), int(keep.sum())
+    lib, st = N.load(), torch.cuda.current_stream().cuda_stream
+    G = idx.graph
+    t_ent, b_ent, k_ent = prune_alone(lib, st, G["ent_rowptr"], G["ent_col"], None, remap, n_new, True)
+    t_men, b_men, k_men = prune_alone(lib, st, G["men_rowptr"], G["men_chunk"], G["men_conf"], remap, n_new, False)
+    # the torch ops of the call have run once at this size before anything is timed (a throw-away index)
+    warm = T.GpuIndex()
+    warm.n_docs = a.n
+    warm.set_graph(*g).set_entity_names(names)
+    warm.delete_graph(entities=gone)
+    del warm
+    _, wall_d, dev_d = timed(lambda: idx.delete_graph(entities=gone))
+    # the same change as the parent commit offers it: a host build over the surviving rows + set_graph + set_entity_names
+    t0 = time.perf_counter()
+    es, em = keep[src] & keep[dst], keep[me]
+    g2 = host_graph(n_new, remap_h[src[es]].astype(np.int64), remap_h[dst[es]].astype(np.int64),
+                    remap_h[me[em]].astype(np.int64), mc[em], mw[em])
+    names2 = [nm for nm, k in zip(names, keep) if k]
+    t_host = (time.perf_counter() - t0) * 1e3
+    fresh = T.GpuIndex()
+    fresh.n_docs = a.n
+    _, wall_up, _ = timed(lambda: fresh.set_graph(*g2).set_entity_names(names2))
+    same = all(torch.equal(idx.graph[k], fresh.graph[k]) for k in ("ent_rowptr", "ent_col", "men_rowptr", "men_chunk", "men_conf"))
+    same = same and torch.equal(idx.entities["name_bytes"], fresh.entities["name_bytes"]) and \
+        torch.equal(idx.entities["name_ptr"], fresh.entities["name_ptr"])
+    print(json.dumps({"deleted_entities": int(len(gone)), "delete_graph_wall_ms": round(wall_d, 3),
+                      "delete_graph_device_ms": round(dev_d, 3),
+                      "csr_prune_entities_ms": round(t_ent, 4), "csr_prune_entities_GBps": round(b_ent / t_ent / 1e6, 1),
+                      "csr_prune_entities_share_of_hbm_peak": round(b_ent / t_ent / 1e6 / HBM_PEAK_GBPS, 4),
+                      "csr_prune_mentions_ms": round(t_men, 4), "csr_prune_mentions_GBps": round(b_men / t_men / 1e6, 1),
+                      "csr_prune_mentions_share_of_hbm_peak": round(b_men / t_men / 1e6 / HBM_PEAK_GBPS, 4),
+                      "edges_kept": k_ent, "mentions_kept": k_men, "rebuild_host_ms": round(t_host, 1),
+                      "rebuild_upload_ms": round(wall_up, 1), "equal_to_rebuild": bool(same), "entities": n_new}), flush=True)
+    # the same queries, their seeds renumbered with the remap (a removed seed leaves its slot)
+    s2 = np.where(seeds_h >= 0, remap_h[np.maximum(seeds_h, 0)], -1).astype(np.int32)
+    s2 = np.stack([np.concatenate([r[r >= 0], r[r < 0]]) for r in s2])
+    seeds2 = torch.from_numpy(s2).cuda()
+    after, after_fresh = search_ms(idx, seeds2, a.repeats), search_ms(fresh, seeds2, a.repeats)
+    print(json.dumps({"graph_search_ms_after": [round(t, 3) for t in after],
+                      "graph_search_ms_fresh_build": [round(t, 3) for t in after_fresh],
+                      "before_spread_ms": round(max(before) - min(before), 3),
+                      "after_minus_before_median_ms": round(float(np.median(after) - np.median(before)), 3),
+                      "after_minus_fresh_median_ms": round(float(np.median(after) - np.median(after_fresh)), 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--delete", action="store_true", help="measure graph delete instead of graph ingest")
+    ap.add_argument("--share", type=float, default=0.01, help="--delete: the share of the entities that is removed")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=2048)
     ap.add_argument("--batches", default="1,256,16384")
@@ -92,6 +192,10 @@ def main():
     batches = [int(b) for b in a.batches.split(",")]
     if a.n < 64 or a.queries < 1 or not batches or min(batches) < 1:
         ap.error("--n >= 64, --queries >= 1, --batches positive")
+    if a.delete:
+        if not 0 < a.share < 1:
+            ap.error("--share inside (0, 1)")
+        return delete_main(a)
     sg = synth.build_graph(a.n)
     n_ent = synth.n_entities(a.n)
     src, dst = edge_list((sg.ent_rowptr, sg.ent_col))

@@ -29,8 +29,9 @@ def sources():
 
 
 def _headers():
+    include = os.path.join(os.path.dirname(PKG_DIR), "include")
     return sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + \
-        [os.path.join(os.path.dirname(PKG_DIR), "include", "thr_hip.h")]
+        [os.path.join(include, "thr_hip.h"), os.path.join(include, "thr_hip_graph.h")]
 
 
 def _obj(src: str) -> str:

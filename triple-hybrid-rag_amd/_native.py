@@ -149,6 +149,17 @@ _SIGNATURES = {
     "thr_merge_topk": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# include/thr_hip_graph.h: the entry points that came after ABI version 9 (additive: the version stays)
+_SIGNATURES_GRAPH = {
+    "thr_csr_prune_slice": (_i32, []),
+    "thr_csr_prune_workspace_bytes": (_sz, [_i64, _i64]),
+    "thr_csr_prune": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64,
+                             _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+# thr_hip_graph.h's #defines (THR_CSR_PRUNE_*): positions a workgroup of thr_csr_prune owns; the bits of its
+# status word -- a row of B not strictly ascending, the result exceeds out_capacity, a row destination >= rows_out
+CSR_PRUNE_SLICE = 1024
+CSR_PRUNE_UNSORTED_B, CSR_PRUNE_OVERFLOW, CSR_PRUNE_BAD_ROW = 1, 2, 4
 
 
 def lib_path() -> str:
@@ -169,7 +180,7 @@ def load(build_if_missing: bool = True):
         lib = C.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise NativeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -730,6 +741,105 @@ def csr_merge(rowptr_a, ids_a, pay_a, rowptr_b, ids_b, pay_b, drop_present: bool
     if check and status:
         raise NativeError("csr_merge: " + csr_merge_status_message(status))
     return rowptr_out, ids_out, (pay_out if has else None), nnz_out, status
+
+
+def csr_prune_workspace_bytes(rows_a: int, nnz_a: int) -> int:
+    return int(load().thr_csr_prune_workspace_bytes(int(rows_a), int(nnz_a)))
+
+
+def csr_prune_status_message(status: int) -> Optional[str]:
+    """What a non-zero status word of thr_csr_prune says, or None."""
+    if not status:
+        return None
+    said = []
+    if status & CSR_PRUNE_UNSORTED_B:
+        said.append("B (the pairs to drop) is not strictly ascending within a row")
+    if status & CSR_PRUNE_OVERFLOW:
+        said.append("the result does not fit the destination (out_capacity)")
+    if status & CSR_PRUNE_BAD_ROW:
+        said.append("row_remap names a row outside the result (rows_out)")
+    return "; ".join(said)
+
+
+def csr_prune(rowptr_a, ids_a, pay_a=None, row_remap=None, rows_out: Optional[int] = None, id_remap=None,
+              id_base: int = 0, rowptr_b=None, ids_b=None, ids_out=None, pay_out=None, want_keep: bool = False,
+              workspace=None, check: bool = True):
+    """One order-preserving pass over a CSR that drops rows, entries by id and (row, id) pairs
+    (thr_csr_prune).  ``rowptr_a`` int64 [rows_a + 1], ``ids_a`` int32 [nnz_a], ``pay_a`` a 4-byte tensor
+    [nnz_a] or None.  ``row_remap`` int32 [rows_a] or None: the new row of old row t, -1 = removed with
+    everything in it, ascending over the survivors 0 .. rows_out - 1 (``rows_out`` is required with it;
+    without it every row stays).  ``id_remap`` int32 [n_ids] or None with ``id_base``: as csr_compact;
+    None: ids pass through untouched and unchecked.  ``rowptr_b`` / ``ids_b``: a CSR over A's rows,
+    strictly ascending within a row, in A's old numbering -- an entry of A's row t whose id is in B's
+    row t is dropped -- or None.  ``ids_out`` / ``pay_out``: capacity-reserved 1-d destinations (allocated
+    for nnz_a when None); ``want_keep``: also return the uint8 [nnz_a] keep mask; ``workspace``: reused when
+    large enough (_workspace).  One host read-back at the end (the count and the status word).  ``check``:
+    raise NativeError on a non-zero status instead of returning it.
+    -> (rowptr_out, ids_out, pay_out or None, nnz_out, status, keep or None)."""
+    rows_a, nnz_a = rowptr_a.shape[0] - 1, ids_a.shape[0]
+    if rows_a < 0:
+        raise NativeError("csr_prune: rowptr_a has no entry")
+    if row_remap is None:
+        if rows_out is not None and int(rows_out) != rows_a:
+            raise NativeError("csr_prune: rows_out differs from A's row count, and no row_remap says which rows leave")
+        rows_out = rows_a
+    else:
+        if rows_out is None:
+            raise NativeError("csr_prune: row_remap needs rows_out")
+        if row_remap.dim() != 1 or row_remap.shape[0] != rows_a:
+            raise NativeError("csr_prune: row_remap holds one entry per row of A")
+    rows_out = int(rows_out)
+    if rows_out < 0 or rows_out > rows_a:
+        raise NativeError(f"csr_prune: rows_out is {rows_out}, A has {rows_a} rows")
+    if id_base < 0:
+        raise NativeError("csr_prune: id_base is negative")
+    if pay_a is not None and (pay_a.dtype.itemsize != 4 or pay_a.dim() != 1 or pay_a.shape[0] != nnz_a):
+        raise NativeError("csr_prune: the payload is a 1-d array of 4-byte elements, one per id")
+    if pay_a is None and pay_out is not None:
+        raise NativeError("csr_prune: pay_out without a payload")
+    if (rowptr_b is None) != (ids_b is None):
+        raise NativeError("csr_prune: B is row pointers and ids, or neither")
+    if rowptr_b is not None and (rowptr_b.dim() != 1 or rowptr_b.shape[0] != rows_a + 1):
+        raise NativeError("csr_prune: rowptr_b holds one entry per row of A and one more")
+    for out, like, name in ((ids_out, torch.int32, "ids_out"), (pay_out, None if pay_a is None else pay_a.dtype, "pay_out")):
+        if out is not None and (out.dtype != like or out.dim() != 1):
+            raise NativeError(f"csr_prune: {name} is a 1-d array of the source's dtype")
+    pra = _dev(rowptr_a, torch.int64, "rowptr_a", 1)
+    pia = _dev(ids_a, torch.int32, "ids_a", 1)
+    prr = _dev(row_remap, torch.int32, "row_remap", 1)
+    pir = _dev(id_remap, torch.int32, "id_remap", 1)
+    prb = _dev(rowptr_b, torch.int64, "rowptr_b", 1)
+    pib = _dev(ids_b, torch.int32, "ids_b", 1)
+    dev = rowptr_a.device
+    has = pay_a is not None
+    if ids_out is None:
+        ids_out = torch.empty(nnz_a, dtype=torch.int32, device=dev)
+    if pay_out is None and has:
+        pay_out = torch.empty(nnz_a, dtype=pay_a.dtype, device=dev)
+    rowptr_out = torch.empty(rows_out + 1, dtype=torch.int64, device=dev)
+    keep = torch.empty(nnz_a, dtype=torch.uint8, device=dev) if want_keep else None
+    tail = torch.zeros(2, dtype=torch.int64, device=dev)      # *nnz_out, *status_out
+    ws, nbytes = _workspace(workspace, csr_prune_workspace_bytes(rows_a, nnz_a), dev)
+    cap = ids_out.shape[0] if not has else min(ids_out.shape[0], pay_out.shape[0])
+    n_ids = 0 if id_remap is None else id_remap.shape[0]
+    nnz_b = 0 if ids_b is None else ids_b.shape[0]
+    if id_remap is not None and n_ids == 0:
+        raise NativeError("csr_prune: an empty id_remap (pass None to let every id through)")
+    _check(load().thr_csr_prune(pra if rows_a else None, rows_a, nnz_a, pia if nnz_a else None,
+                                _dev(pay_a, pay_a.dtype, "pay_a", 1) if has and nnz_a else None,
+                                prr if row_remap is not None and rows_a else None, rows_out,
+                                pir if n_ids else None, n_ids, int(id_base),
+                                prb if rowptr_b is not None else None, nnz_b, pib if nnz_b else None,
+                                rowptr_out.data_ptr(), _dev(ids_out, torch.int32, "ids_out", 1) if nnz_a else None,
+                                _dev(pay_out, pay_a.dtype, "pay_out", 1) if has and nnz_a else None, cap,
+                                keep.data_ptr() if want_keep and nnz_a else None,
+                                tail.data_ptr(), tail.data_ptr() + 8, ws.data_ptr(), nbytes, _stream()),
+           "thr_csr_prune")
+    nnz_out, status = (int(v) for v in tail.tolist())
+    status &= 0xFFFFFFFF
+    if check and status:
+        raise NativeError("csr_prune: " + csr_prune_status_message(status))
+    return rowptr_out, ids_out, (pay_out if has else None), nnz_out, status, keep
 
 
 # --------------------------------------------------------------------- f4

@@ -63,6 +63,7 @@ class GpuIndexClient(ClientIngest):
     defers_readback = True   # rag2_lexical_search honours ``_defer`` (see _lexical)
     sets_collections = True  # derives the index's per-doc collection ids from the store's rows
     multi_tenant = False     # set by __init__: no org_id of its own over a store with an org_ids column
+    graph_cascade = False    # set by __init__: a document delete also removes the entities first extracted from it
 
     # Derived state, made by __init__ (the class values serve a subclass with an __init__ of its own):
     #   attribute     derived from                                   filled by           dropped by (backend_ingest)
@@ -79,7 +80,7 @@ class GpuIndexClient(ClientIngest):
                  token_embedder: Any = None, lexical_and: bool = False,
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
                  collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
-                 tokenizer: Any = None, number_on_device: bool = False):
+                 tokenizer: Any = None, number_on_device: bool = False, graph_cascade: bool = False):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's ``plainto_tsquery`` does
         (rag2_schema.sql:365); default is BM25's OR form, the north star's and the oracle's.
         image_index / image_rows: the legacy image channel (``kb_chunks_image_search``,
@@ -101,7 +102,15 @@ class GpuIndexClient(ClientIngest):
         number_on_device: (with device_text) ``insert_children`` also numbers the batch's new terms on the device
         (GpuIndex.number_text_rows / commit_vocabulary): the unknown tokens are not decoded one occurrence at a time,
         the new keys stay on the device, and the store's vocabulary gets one string per distinct new term.  The ids are
-        the host loop's.  Without device_text it is refused by name."""
+        the host loop's.  Without device_text it is refused by name.
+        graph_cascade: ``table("rag_documents").delete()`` also removes the entities whose ``document_id`` is a deleted
+        document, with their relations and mentions, as the schema's ON DELETE CASCADE does (rag2_schema.sql:187,
+        217-220, 254, 258-259).  Needs the store's ``entity_documents`` column; default False: entities outlive their
+        document, the behaviour before the flag."""
+        if graph_cascade and getattr(store, "entity_documents", None) is None:
+            raise ValueError("graph_cascade=True needs the store's entity_documents column (rag_entities.document_id): "
+                             "no entity row of this store carries a document_id")
+        self.graph_cascade = bool(graph_cascade)
         if number_on_device and not device_text:
             raise ValueError("number_on_device=True needs device_text=True: the terms are numbered behind "
                              "the device tokenizer")

@@ -45,7 +45,7 @@ class ClientIngest:
         self._by_text = None        # (parent texts are in it, as "no chunk of this text")
 
     def _graph_changed(self) -> None:
-        self._tri = None            # (entities, relations or mentions were added: the index is over the old names)
+        self._tri = None            # (entities, relations or mentions were added or removed: the index is over the old names)
 
     # -------------------------------------------------------------- ingest
     def _check_foreign_org(self, rows: Sequence[Dict[str, Any]]) -> None:
@@ -294,16 +294,148 @@ class ClientIngest:
         """Documents by ``id`` -> [{"id": d}, ...] of those that had chunks; their children and
         the parents those reference go with them (schema :65, :107).  Multi-tenant, ``org_id``
         restricts the delete to that org's chunks (alone: every document of the org): a document
-        or parent that other orgs' chunks still name loses the org's chunks and stays."""
+        or parent that other orgs' chunks still name loses the org's chunks and stays.
+        With ``graph_cascade`` the entities whose ``document_id`` is a document that is gone afterwards
+        leave too, with their relations and mentions (schema :187, :217-220, :254, :258-259): after the
+        chunk cascade, in one ``GpuIndex.delete_graph`` call, refused before anything is touched when it
+        would leave no entity."""
         st = self.store
         docs, own = self._keys_where(filters, "rag_documents", st.document_ids, {"id": None})
         rows = [i for i, d in enumerate(st.document_ids) if d in docs and (own is None or i in own)]
         found = list(dict.fromkeys(st.document_ids[i] for i in rows))
         pids = {st.parent_ids[i] for i in rows}
+        ents: List[int] = []
+        if self.graph_cascade:
+            dead = set(rows)
+            left = {str(d) for i, d in enumerate(st.document_ids) if i not in dead}
+            gone = {str(d) for d in docs} - left
+            ents = [e for e, d in enumerate(st.entity_documents or ()) if d is not None and str(d) in gone]
+            if ents and len(ents) >= len(st.entity_names):
+                raise N.NativeError("delete refused: every entity of the index would be deleted with these documents "
+                                    "(graph_cascade): build a new index")
         self._delete_rows(rows)
+        self._delete_entities(ents)
         if own is not None:
             pids -= set(st.parent_ids)
             found = [d for d in found if d not in set(st.document_ids)]
         for p in pids:
             st.parents.pop(p, None)
         return [{"id": d} for d in found]
+
+    # -------------------------------------------------------------- graph delete
+    # What the reference's schema does by cascade (20260114_rag2_schema.sql:187, 217-220, 254, 258-259) and its
+    # entity extraction needs before it re-runs over an updated document: rag_entities / rag_relations /
+    # rag_entity_mentions rows out of the live index (``GpuIndex.delete_graph``), then out of the store.
+    def _delete_entities(self, indices: Sequence[int]) -> List[Dict[str, Any]]:
+        """Remove the entities ``indices`` (sorted, distinct) from the index, then from the store -> their rows."""
+        if not indices:
+            return []
+        self.index.delete_graph(entities=np.asarray(indices, dtype=np.int64))   # index first: a refusal leaves both untouched
+        deleted = self.store.delete_entities(indices)
+        self._graph_changed()
+        return deleted
+
+    def _entity_filter(self, values) -> set:
+        return {i for i in (self.store.entity_index(v) for v in values) if i is not None}
+
+    def _delete_entities_where(self, filters) -> List[Dict[str, Any]]:
+        """``table("rag_entities").delete()`` by ``id`` / ``canonical_name`` / ``document_id`` (the last only when the
+        store holds the column) -> the deleted entity rows in index order; each leaves with its relations and its
+        mentions.  Unknown ids delete nothing.  Entities carry no org in the store: ``org_id`` narrows nothing, and
+        alone it is no filter."""
+        st = self.store
+        served = ["id", "canonical_name"] + (["document_id"] if st.entity_documents is not None else [])
+        found = None
+        for column, values in filters:
+            if column == "org_id":
+                continue
+            if column not in served:
+                raise ValueError(f"delete: rag_entities rows are addressed by {' / '.join(served)}, not {column!r}")
+            if column == "id":
+                hit = self._entity_filter(values)
+            elif column == "canonical_name":
+                want = set(values)
+                hit = {i for i in range(len(st.entity_names)) if st.entity_row(i)["canonical_name"] in want}
+            else:
+                want = {str(v) for v in values}
+                hit = {i for i, d in enumerate(st.entity_documents) if d is not None and str(d) in want}
+            found = hit if found is None else found & hit
+        if found is None:
+            raise ValueError("DELETE requires a WHERE clause: a delete without a filter other than org_id is refused")
+        return self._delete_entities(sorted(found))
+
+    def _delete_relations_where(self, filters) -> List[Dict[str, Any]]:
+        """``table("rag_relations").delete()`` by ``subject_entity_id`` AND ``object_entity_id`` (``in_``: the cross
+        product of the known entities) -> one {"subject_entity_id", "object_entity_id"} per named pair whose edge
+        the index held.  The edge goes in both directions; relation rows as rows (types, ids) are not stored."""
+        ends: Dict[str, Optional[set]] = {"subject_entity_id": None, "object_entity_id": None}
+        for column, values in filters:
+            if column == "org_id":
+                continue
+            if column not in ends:
+                raise ValueError(f"delete: rag_relations rows are addressed by {' / '.join(ends)}, not {column!r}")
+            hit = self._entity_filter(values)
+            ends[column] = hit if ends[column] is None else ends[column] & hit
+        if ends["subject_entity_id"] is None or ends["object_entity_id"] is None:
+            raise ValueError("delete: rag_relations rows are addressed by subject_entity_id AND object_entity_id: the "
+                             "index keeps undirected edges (the set union of the relation rows) and cannot tell subject "
+                             "from object -- delete the entity to remove every relation it has")
+        subjects = sorted(ends["subject_entity_id"])
+        if not subjects or not ends["object_entity_id"]:
+            return []
+        rp, ids, _ = self.index.graph_rows_host("relations", subjects)
+        held = [(a, b) for j, a in enumerate(subjects) for b in sorted(ends["object_entity_id"])
+                if a != b and b in set(ids[rp[j]:rp[j + 1]].tolist())]
+        if not held:
+            return []
+        self.index.delete_graph(relations=(np.asarray([a for a, _ in held], dtype=np.int64),
+                                           np.asarray([b for _, b in held], dtype=np.int64)))
+        self._graph_changed()
+        eid = lambda i: self.store.entity_row(i)["id"]
+        return [{"subject_entity_id": eid(a), "object_entity_id": eid(b)} for a, b in held]
+
+    def _delete_mentions_where(self, filters) -> List[Dict[str, Any]]:
+        """``table("rag_entity_mentions").delete()`` by ``entity_id`` and / or ``child_chunk_id`` -> one {"entity_id",
+        "child_chunk_id", "confidence"} per removed mention, in (entity, chunk) order.  Multi-tenant, ``org_id``
+        restricts the delete to mentions of that org's chunks (a mention's tenant is its chunk's)."""
+        st = self.store
+        ents = chunks = own = None
+        for column, values in filters:
+            if column == "org_id":
+                if self.multi_tenant:
+                    rows = {i for i, o in enumerate(st.org_ids) if o in set(values)}
+                    own = rows if own is None else own & rows
+                continue
+            if column == "entity_id":
+                hit = self._entity_filter(values)
+                ents = hit if ents is None else ents & hit
+            elif column == "child_chunk_id":
+                hit = {i for i in (st.row_index(v) for v in values) if i is not None}
+                chunks = hit if chunks is None else chunks & hit
+            else:
+                raise ValueError(f"delete: rag_entity_mentions rows are addressed by entity_id / child_chunk_id, not {column!r}")
+        if ents is None and chunks is None:
+            raise ValueError("DELETE requires a WHERE clause: a delete without a filter other than org_id is refused")
+        if (ents is not None and not ents) or (chunks is not None and not chunks):
+            return []
+        which = None if ents is None else sorted(ents)
+        rp, ids, conf = self.index.graph_rows_host("mentions", which)
+        gone = []
+        for j in range(len(rp) - 1):
+            e = j if which is None else which[j]
+            for c, w in zip(ids[rp[j]:rp[j + 1]].tolist(), conf[rp[j]:rp[j + 1]].tolist()):
+                if (chunks is None or c in chunks) and (own is None or c in own):
+                    gone.append((e, c, w))
+        if not gone:
+            return []
+        if own is None and chunks is None:
+            named = (np.asarray(which, dtype=np.int64), np.full(len(which), -1, dtype=np.int64))
+        elif own is None and ents is None:
+            named = (np.full(len(chunks), -1, dtype=np.int64), np.asarray(sorted(chunks), dtype=np.int64))
+        else:
+            pairs = sorted({(e, c) for e, c, _ in gone})
+            named = (np.asarray([e for e, _ in pairs], dtype=np.int64), np.asarray([c for _, c in pairs], dtype=np.int64))
+        self.index.delete_graph(mentions=named)
+        self._graph_changed()
+        return [{"entity_id": st.entity_row(e)["id"], "child_chunk_id": st.child_ids[c], "confidence": float(w)}
+                for e, c, w in gone]

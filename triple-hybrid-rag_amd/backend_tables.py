@@ -128,9 +128,9 @@ TABLES: Dict[str, _Table] = {
     "rag_child_chunks": _Table(_children_by_id, by_hash=_children_by_hash, insert="insert_children",
                                delete="_delete_children_where"),
     "rag_parent_chunks": _Table(_parents_by_id, insert="insert_parents", delete="_delete_parents_where"),
-    "rag_entities": _Table(_entities_by_id, by_eq=_entities_by_eq, insert="insert_entities"),
-    "rag_relations": _Table(lambda _c, _ids, **_within: [], insert="insert_relations"),
-    "rag_entity_mentions": _Table(lambda _c, _ids, **_within: [], insert="insert_mentions"),
+    "rag_entities": _Table(_entities_by_id, by_eq=_entities_by_eq, insert="insert_entities", delete="_delete_entities_where"),
+    "rag_relations": _Table(lambda _c, _ids, **_within: [], insert="insert_relations", delete="_delete_relations_where"),
+    "rag_entity_mentions": _Table(lambda _c, _ids, **_within: [], insert="insert_mentions", delete="_delete_mentions_where"),
     "rag_documents": _Table(partial(_tenants, "org_id"), delete="_delete_documents_where"),
     "organizations": _Table(partial(_tenants, "id")),
 }

@@ -182,6 +182,12 @@ class ShardedIndex:
         raise N.NativeError("append_mentions is not supported on a ShardedIndex: rebuild the shards "
                             "(graph ingest into a document-sharded index is out of scope)")
 
+    def delete_graph(self, *_a, **_kw):
+        """Not supported, as append_graph: the entity ids every rank's seeds and names use would move
+        on all ranks at once (Graph delete)."""
+        raise N.NativeError("delete_graph is not supported on a ShardedIndex: rebuild the shards "
+                            "(graph deletes from a document-sharded index are out of scope)")
+
     def _floor_exchange(self):
         if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline", "f16-anydim"):
             return None

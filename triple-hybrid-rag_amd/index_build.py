@@ -288,7 +288,9 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
         org_ids=[r.get("org_id") for r in child_rows] if any("org_id" in r for r in child_rows) else None,
         entity_ids=[e["id"] for e in entity_rows] if entity_rows else None,
         entity_canonical=[e.get("canonical_name") for e in entity_rows]
-        if any(e.get("canonical_name") is not None for e in entity_rows) else None)
+        if any(e.get("canonical_name") is not None for e in entity_rows) else None,
+        entity_documents=[e.get("document_id") for e in entity_rows]     # (rag_entities.document_id, nullable)
+        if any(e.get("document_id") is not None for e in entity_rows) else None)
     hi = HostIndex(docs=docs, rowptr=rowptr, post_doc=pd, post_tf=ptf, doclen=dl, idf=idf,
                    avgdl=avgdl, store=store)
     if entity_rows:
@@ -303,7 +305,7 @@ _ARRAYS = ("docs", "rowptr", "post_doc", "post_tf", "doclen", "idf", "ent_rowptr
 _DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf")
 _DERIVED_SCALARS = ("doc_rel_err", "f16_layout", "lexical_tag", "dense_stride")
 _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modalities", "collections",
-                   "entity_names", "content_hashes", "org_ids", "entity_ids", "entity_canonical")
+                   "entity_names", "content_hashes", "org_ids", "entity_ids", "entity_canonical", "entity_documents")
 _NO_PAGE = np.iinfo(np.int32).min   # store_pages.npy: the SQL column is nullable (page INT)
 
 
@@ -444,6 +446,7 @@ def load(path: str, mmap: bool = True) -> HostIndex:
                                 entity_names=cols.get("entity_names", []), doc_base=ms["doc_base"],
                                 content_hashes=cols.get("content_hashes"),
                                 org_ids=cols.get("org_ids"),    # (None: a directory saved without the column)
-                                entity_ids=cols.get("entity_ids"), entity_canonical=cols.get("entity_canonical"))
+                                entity_ids=cols.get("entity_ids"), entity_canonical=cols.get("entity_canonical"),
+                                entity_documents=cols.get("entity_documents"))   # (None: saved without the column)
     attributes = {name: arr(f"attr_{i}") for i, name in enumerate(meta.get("attributes", []))} or None
     return HostIndex(avgdl=meta["avgdl"], store=store, derived=derived, attributes=attributes, **arrays)

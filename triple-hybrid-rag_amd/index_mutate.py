@@ -167,11 +167,12 @@ class MutableIndex:
         out["df"] = df
         return out
 
-    def _graph_with(self, men_rowptr, men_chunk, men_conf) -> dict:
-        """A new ``self.graph`` dict: the entity CSR as it is, the mentions given (the chunk-major
-        copy of the mentions is rebuilt on next use, as after set_graph)."""
+    def _graph_with(self, men_rowptr, men_chunk, men_conf, ent_rowptr=None, ent_col=None) -> dict:
+        """A new ``self.graph`` dict: the entity CSR as it is (or the one given), the mentions given
+        (the chunk-major copy of the mentions is rebuilt on next use, as after set_graph)."""
         G = self.graph
-        return dict(ent_rowptr=G["ent_rowptr"], ent_col=G["ent_col"], men_rowptr=men_rowptr,
+        return dict(ent_rowptr=G["ent_rowptr"] if ent_rowptr is None else ent_rowptr,
+                    ent_col=G["ent_col"] if ent_col is None else ent_col, men_rowptr=men_rowptr,
                     men_chunk=men_chunk, men_conf=men_conf)
 
     # ------------------------------------------------------------ storage
@@ -693,6 +694,184 @@ class MutableIndex:
         # (a fresh dict: the chunk-major copy cached in the old one is keyed on n_docs, which stays)
         new.graph = self._graph_with(rowptr, new.csr["men_chunk"][1], new.csr["men_conf"][1])
         self._commit(new)
+
+    # ------------------------------------------------------------ graph delete
+    # Entities, relations and mentions out of the live index (DESIGN.md "Graph delete"): what the
+    # reference's schema does by cascade when a document or an entity row is deleted
+    # (20260114_rag2_schema.sql:187, 217-220, 254, 258-259).  Afterwards every graph array and the
+    # name store are what index_build.build_graph over the surviving rows, set_graph and
+    # set_entity_names would hold: thr_csr_prune drops and renumbers in one order-preserving pass.
+    def _ids_part(self, a, name: str, who: str, lo: int, hi: int, what: str):
+        """``a`` flat, where the caller left it, every value in [lo, hi) (ValueError) -> the array or None (empty)."""
+        if a is None or not self._size(a):
+            return None
+        t = self._host_or_device(a, name, True, who).reshape(-1)
+        if int(t.min()) < lo or int(t.max()) >= hi:
+            raise ValueError(f"{who}: {name}: {what}")
+        return t
+
+    def _validate_delete_graph(self, entities, relations, mentions):
+        """What delete_graph refuses before any device work -> (entities, (subject, object), (entity, chunk)),
+        each flat where the caller left it, or None."""
+        E, who = N.NativeError, "delete_graph"
+        G = self._graph_or_refuse(who)
+        n_ent = int(G["men_rowptr"].shape[0]) - 1
+        ents = self._ids_part(entities, "entities", who, 0, n_ent, f"entity ids are 0 .. {n_ent - 1}")
+        pairs = []
+        for part, name, los, his, says in (
+                (relations, "relations", (0, 0), (n_ent, n_ent),
+                 (f"relation endpoints are entity ids, 0 .. {n_ent - 1}",) * 2),
+                (mentions, "mentions", (-1, -1), (n_ent, self.n_docs),
+                 (f"entity ids are 0 .. {n_ent - 1} (-1: every entity)",
+                  f"chunk ids are local doc ids, 0 .. {self.n_docs - 1} (-1: every chunk)"))):
+            if part is None:
+                pairs.append(None)
+                continue
+            if len(part) != 2:
+                raise E(f"{who}: {name} is a pair of id arrays")
+            if self._size(part[0]) != self._size(part[1]):
+                raise E(f"{who}: the two arrays of {name} are 1-d arrays of one length")
+            a = self._ids_part(part[0], f"{name}[0]", who, los[0], his[0], says[0])
+            b = self._ids_part(part[1], f"{name}[1]", who, los[1], his[1], says[1])
+            if name == "mentions" and a is not None and bool(((a < 0) & (b < 0)).any()):
+                raise ValueError(f"{who}: a mention names an entity, a chunk or both ((-1, -1) names nothing)")
+            pairs.append(None if a is None else (a, b))
+        if ents is not None:
+            uniq = int(torch.unique(ents).numel()) if isinstance(ents, torch.Tensor) else int(np.unique(ents).size)
+            if uniq >= n_ent:
+                raise E(f"{who}: every entity would be deleted: build a new index")
+        return ents, pairs[0], pairs[1]
+
+    def _pairs_csr(self, rows: torch.Tensor, ids: torch.Tensor, n_rows: int):
+        """(row, id) pairs, int64 on the device, ids in [0, 2^31) -> (rowptr, ids int32): sorted by
+        (row, id) without duplicates, thr_csr_prune's B."""
+        key = torch.unique((rows << 32) | ids)
+        rp = torch.zeros(n_rows + 1, dtype=torch.int64, device=self.device)
+        rp[1:] = torch.cumsum(torch.bincount(key >> 32, minlength=n_rows), 0)
+        return rp, (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+
+    def _prune_or_refuse(self, who: str, *a, **kw):
+        rowptr, ids, pay, nnz, status, _ = N.csr_prune(*a, check=False, **kw)
+        if status:
+            raise N.NativeError(f"{who}: thr_csr_prune: {N.csr_prune_status_message(status)}")
+        return rowptr, ids, pay, nnz
+
+    def _names_without(self, keep: torch.Tensor, n_new: int) -> dict:
+        """The name store without the removed entities' names: byte for byte pack_entity_names(surviving
+        names) -- each kept name's bytes with its 0xFF, in order, the padding moved to the new end -- by
+        device tensor operations; no name comes back to the host."""
+        Ent = self.entities
+        used = int(Ent["name_bytes"].shape[0]) - N.THR_ENTITY_MAX_NEEDLE      # = name_ptr[E]
+        lens = Ent["name_ptr"][1:] - Ent["name_ptr"][:-1]
+        of_kept = keep[torch.repeat_interleave(lens, output_size=used)]      # per byte: does its name stay?
+        ptr = torch.zeros(n_new + 1, dtype=torch.int64, device=self.device)
+        ptr[1:] = torch.cumsum(lens[keep], 0)
+        return dict(name_bytes=torch.cat([Ent["name_bytes"][:used][of_kept], Ent["name_bytes"][used:]]),
+                    name_ptr=ptr, n=n_new)
+
+    def graph_rows_host(self, which: str, entities=None):
+        """Rows of the entity CSR (``which`` = "relations") or of the mention CSR ("mentions") on the host ->
+        (rowptr int64 [len(entities) + 1], ids, conf float32 or None): the rows of ``entities`` in the order
+        given (None: every row); ids are entity ids, or LOCAL chunk ids.  What the drop-in client builds a
+        delete's reply from; one gather and one read-back, not a query-path call."""
+        G = self._graph_or_refuse("graph_rows_host")
+        kr, k0, k1 = ("ent_rowptr", "ent_col", None) if which == "relations" else self.GRAPH_CSR
+        rp, ids, pay = G[kr], G[k0], None if k1 is None else G[k1]
+        base = 0 if which == "relations" else self.doc_base
+        if entities is not None:
+            es = self._t(np.asarray(entities, dtype=np.int64).reshape(-1), torch.int64)
+            lo, n = rp[es], rp[es + 1] - rp[es]
+            ends = torch.cumsum(n, 0)
+            total = int(ends[-1].item()) if es.shape[0] else 0
+            at = torch.repeat_interleave(lo - (ends - n), n, output_size=total) + \
+                torch.arange(total, dtype=torch.int64, device=self.device)
+            rp = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), ends])
+            ids, pay = ids[at], None if pay is None else pay[at]
+        return (rp.cpu().numpy(), ids.cpu().numpy().astype(np.int64) - base, None if pay is None else pay.cpu().numpy())
+
+    @_refuse_when_unusable
+    def delete_graph(self, entities=None, relations=None, mentions=None) -> torch.Tensor:
+        """Entities, relations and mentions out of the live index -> the int32 [E_old] remap on the
+        device: old entity id -> new id, -1 = deleted (a caller that holds seed tables renumbers
+        them with it).
+          entities   entity ids, any order, repeats allowed: each leaves with its relations, in both
+                     directions, and its mentions; the survivors are renumbered ascending;
+          relations  (subject, object) id arrays: the edge between each pair goes, in both
+                     directions (the index keeps the undirected set union of the relation rows, so
+                     the edge is what can be removed); a pair that names no edge, or a self pair,
+                     is ignored;
+          mentions   (entity, chunk) with LOCAL chunk ids: every mention of that pair goes;
+                     chunk = -1: every mention of the entity; entity = -1: every mention of the
+                     chunk (the chunk itself stays).
+        One call may combine all three; the result does not depend on their order: a row is gone
+        if any argument names it.  Afterwards ent_rowptr / ent_col / men_rowptr / men_chunk /
+        men_conf and the name store are, to the bit, what build_graph over the surviving rows in
+        their old order, set_graph and set_entity_names would hold.  Everything is validated before
+        the first change (no graph, ids outside the entity / chunk range: ValueError, arrays of
+        unequal length, every entity deleted: build a new index), written out of place and swapped
+        in last (_commit): a refused or failed call leaves the index answering over the old graph.
+        Two host reads of kept counts.  Synchronises the main and the side stream (not a query-path
+        call)."""
+        who = "delete_graph"
+        ents, rel, men = self._validate_delete_graph(entities, relations, mentions)
+        G = self.graph
+        n_ent = int(G["men_rowptr"].shape[0]) - 1
+        if ents is None and rel is None and men is None:
+            return torch.arange(n_ent, dtype=torch.int32, device=self.device)
+        self._sync_streams()
+        keep = torch.ones(n_ent, dtype=torch.bool, device=self.device)
+        if ents is not None:
+            keep[self._t(ents, torch.int64)] = False
+        rank = torch.cumsum(keep, 0, dtype=torch.int32) - 1
+        remap = torch.where(keep, rank, torch.full_like(rank, -1))
+        n_new = int(keep.sum().item())
+        rows = dict(row_remap=remap, rows_out=n_new) if ents is not None else {}
+        new = _NewState(self.n_docs, shortlist=self.shortlist, doc_rel_err=self.doc_rel_err)
+        # ---- relations: the entity CSR, rows and ids renumbered alike, the named edges in both directions
+        ent_rowptr, ent_col = G["ent_rowptr"], G["ent_col"]
+        rp_b = ids_b = None
+        if rel is not None:
+            s, o = self._t(rel[0], torch.int64), self._t(rel[1], torch.int64)
+            rp_b, ids_b = self._pairs_csr(torch.cat([s, o]), torch.cat([o, s]), n_ent)
+        if ents is not None or rel is not None:
+            dest = self._store.destination("ent_col", ent_col, int(ent_col.shape[0]), grow=False)
+            ent_rowptr, out, _, nnz = self._prune_or_refuse(who, ent_rowptr, ent_col, None, id_remap=remap if ents is not None else None,
+                                                            rowptr_b=rp_b, ids_b=ids_b, ids_out=dest, **rows)
+            new.csr["ent_col"] = (out, out[:nnz])
+            ent_col = new.csr["ent_col"][1]
+        # ---- mentions: rows renumbered, chunks named alone masked by id, pairs through B
+        men_rowptr, men_chunk, men_conf = (G[k] for k in self.GRAPH_CSR)
+        rp_b = ids_b = chunk_mask = None
+        if men is not None:
+            e, c = self._t(men[0], torch.int64), self._t(men[1], torch.int64)
+            every_chunk, every_entity = c < 0, e < 0
+            if bool(every_entity.any()):
+                chunk_mask = torch.arange(self.n_docs, dtype=torch.int32, device=self.device)
+                chunk_mask[c[every_entity]] = -1
+            pe, pc = e[~every_chunk & ~every_entity], c[~every_chunk & ~every_entity] + self.doc_base
+            if bool(every_chunk.any()):        # every mention the entity has: its row's own chunk ids
+                es = torch.unique(e[every_chunk])
+                lo, n = men_rowptr[es], men_rowptr[es + 1] - men_rowptr[es]
+                total = int(n.sum().item())
+                at = torch.repeat_interleave(lo - (torch.cumsum(n, 0) - n), n, output_size=total) + \
+                    torch.arange(total, dtype=torch.int64, device=self.device)
+                pe = torch.cat([pe, torch.repeat_interleave(es, n, output_size=total)])
+                pc = torch.cat([pc, men_chunk[at].to(torch.int64)])
+            if pe.shape[0]:
+                rp_b, ids_b = self._pairs_csr(pe, pc, n_ent)
+        if ents is not None or rp_b is not None or chunk_mask is not None:
+            d0, d1 = (self._store.destination(k, G[k], int(G[k].shape[0]), grow=False) for k in ("men_chunk", "men_conf"))
+            men_rowptr, out0, out1, nnz = self._prune_or_refuse(who, men_rowptr, men_chunk, men_conf, id_remap=chunk_mask,
+                                                                id_base=self.doc_base, rowptr_b=rp_b, ids_b=ids_b,
+                                                                ids_out=d0, pay_out=d1, **rows)
+            new.csr["men_chunk"], new.csr["men_conf"] = (out0, out0[:nnz]), (out1, out1[:nnz])
+            men_chunk, men_conf = new.csr["men_chunk"][1], new.csr["men_conf"][1]
+        # (a fresh dict: the chunk-major copy of the mentions cached in the old one is not reused)
+        new.graph = self._graph_with(men_rowptr, men_chunk, men_conf, ent_rowptr, ent_col)
+        if self.entities is not None and ents is not None:
+            new.entities = self._names_without(keep, n_new)
+        self._commit(new)
+        return remap
 
     # ------------------------------------------------------------ delete
     # Delete in place (DESIGN.md "Delete in place"): after delete_rows every device array is what a

@@ -67,12 +67,16 @@ class _ShardEndpoint(GpuIndexClient):
     def __init__(self, index, store: CorpusStore, group=None, front: int = 0,
                  collection_names: Optional[Sequence[str]] = None, org_id: Optional[str] = None,
                  token_embedder: Any = None, lexical_and: bool = False,
-                 max_token_words: int = 32 * 128 // 2, merge_fn: Optional[Callable] = None):
+                 max_token_words: int = 32 * 128 // 2, merge_fn: Optional[Callable] = None,
+                 graph_cascade: bool = False):
         """front: rank (within ``group``) that receives the requests.
         max_token_words: int32 words reserved for a query's float16 token matrix (32 x 128).
         merge_fn(scores [W, 1, k], ids [W, 1, k], k) -> (scores [1, k], ids [1, k]): the per-query
         merge of the gathered shard lists; default thr_merge_topk (tests of the control flow on a
         CPU-only box inject their own)."""
+        if graph_cascade:
+            raise N.NativeError("graph_cascade is not supported through a sharded index client: rebuild the shards "
+                                "(graph deletes from a document-sharded index are out of scope)")
         if getattr(store, "org_ids", None) is not None:
             raise N.NativeError("a sharded index client serves one tenant: this store carries a per-row org_ids "
                                 "column (scoped queries over a document-sharded index are not built)")
@@ -124,6 +128,7 @@ class _ShardEndpoint(GpuIndexClient):
 
     delete_children = _delete_rows = _refuse_delete
     _delete_children_where = _delete_parents_where = _delete_documents_where = _refuse_delete
+    _delete_entities_where = _delete_relations_where = _delete_mentions_where = _refuse_delete
 
     # ---------------------------------------------------------------- messages
     def _broadcast(self, msg: Optional[torch.Tensor]) -> torch.Tensor:

@@ -10,6 +10,7 @@ import numpy as np
 ROW_COLUMNS = {"child_ids": ("id", None), "parent_ids": ("parent_id", None), "document_ids": ("document_id", None),
                "texts": ("text", ""), "pages": ("page", 1), "modalities": ("modality", "text"),
                "collections": ("collection", None), "content_hashes": ("content_hash", None), "org_ids": ("org_id", None)}
+ENTITY_COLUMNS = ("entity_names", "entity_ids", "entity_canonical", "entity_documents")
 
 
 def number_tokens(per_text_tokens, vocab: Dict[str, int]) -> tuple:
@@ -47,6 +48,9 @@ class CorpusStore:
     # the integer index is the id and the name the canonical name
     entity_ids: Optional[List[Any]] = None
     entity_canonical: Optional[List[Optional[str]]] = None
+    # rag_entities.document_id (the document an entity was first extracted from: ON DELETE CASCADE), parallel to
+    # entity_names.  None until a row carries one
+    entity_documents: Optional[List[Optional[Any]]] = None
 
     def __post_init__(self):
         self._row_of = {cid: i for i, cid in enumerate(self.child_ids)}
@@ -105,17 +109,42 @@ class CorpusStore:
         n0 = len(self.entity_names)
         if not rows:
             return range(n0, n0)
-        self._writable(("entity_names", "entity_ids", "entity_canonical"))
+        self._writable(ENTITY_COLUMNS)
         if self.entity_ids is None:
             self.entity_ids = list(range(n0))
         if self.entity_canonical is None:
             self.entity_canonical = [None] * n0
+        if self.entity_documents is None and any(r.get("document_id") is not None for r in rows):
+            self.entity_documents = [None] * n0
         for r in rows:
             self.entity_ids.append(r["id"])
             self.entity_names.append(r.get("name") or "")
             self.entity_canonical.append(r.get("canonical_name"))
+            if self.entity_documents is not None:
+                self.entity_documents.append(r.get("document_id"))
         self._ent_of = self._canon_of = None
         return range(n0, n0 + len(rows))
+
+    def delete_entities(self, indices: Sequence[int]) -> List[Dict[str, Any]]:
+        """Remove the entities with these indices (any order, repeats allowed) -> the removed rows as ``entity_row``
+        gives them, in index order.  entity_names and the id / canonical-name / document columns are compacted (entity i
+        becomes entity i - #deleted below i, as ``GpuIndex.delete_graph`` renumbers the index) and the lookup caches
+        are dropped.  A store without an id column gets one first: the integer ids it answered to stay those entities'."""
+        n = len(self.entity_names)
+        gone = sorted({int(i) for i in indices})
+        if gone and (gone[0] < 0 or gone[-1] >= n):
+            raise ValueError(f"entity index out of range 0 .. {n - 1}")
+        if not gone:
+            return []
+        out = [self.entity_row(i) for i in gone]
+        if self.entity_ids is None:
+            self.entity_ids = list(range(n))
+        dead = set(gone)
+        for name in self._writable(ENTITY_COLUMNS):
+            col = getattr(self, name)
+            setattr(self, name, [col[i] for i in range(n) if i not in dead])
+        self._ent_of = self._canon_of = None
+        return out
 
     # ---- child chunks (rag_child_chunks)
     def has_hash(self, content_hash: Optional[str]) -> bool:
