@@ -160,6 +160,14 @@ _SIGNATURES_GRAPH = {
 # status word -- a row of B not strictly ascending, the result exceeds out_capacity, a row destination >= rows_out
 CSR_PRUNE_SLICE = 1024
 CSR_PRUNE_UNSORTED_B, CSR_PRUNE_OVERFLOW, CSR_PRUNE_BAD_ROW = 1, 2, 4
+# include/thr_hip_text.h: the token-level analysis behind the character table (additive as well)
+_SIGNATURES_TEXT = {
+    "thr_text_tokens_analyzed_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "thr_text_tokens_analyzed": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
+                                        _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+# thr_hip_text.h's #defines (THR_STEM_*): code points of a suffix, steps and rules of a table, bytes of a rule record
+STEM_MAX_SUFFIX, STEM_MAX_STEPS, STEM_MAX_RULES, STEM_RULE_BYTES = 8, 4, 1024, 24
 
 
 def lib_path() -> str:
@@ -180,7 +188,7 @@ def load(build_if_missing: bool = True):
         lib = C.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise NativeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -1259,7 +1267,7 @@ def vocab_grow_workspace_bytes(unknown_capacity: int) -> int:
 
 
 def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, term_ptr, workspace=None,
-                token_capacity: Optional[int] = None):
+                token_capacity: Optional[int] = None, _analysis=None):
     """thr_text_tokens -> dict(doc i32 [cap], term i32 [cap], n_tokens i32 [n], flags i32 [n], n_total i32 [1],
     unknown_off i64 [cap], unknown_len i32 [cap], n_unknown i32 [1], capacity), all on the device: the first
     n_total rows (n_unknown entries) are valid.  text_bytes u8 holds n_bytes bytes of texts and at least 4
@@ -1281,19 +1289,58 @@ def text_tokens(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, te
                           f"the array holds {text_bytes.shape[0]}")
     cap = text_token_capacity(n, n_bytes) if token_capacity is None else int(token_capacity)
     dev = text_bytes.device
-    ws, nbytes = _workspace(workspace, text_tokens_workspace_bytes(n, n_bytes, cap), dev)
+    size = text_tokens_workspace_bytes if _analysis is None else text_tokens_analyzed_workspace_bytes
+    ws, nbytes = _workspace(workspace, size(n, n_bytes, cap), dev)
     out = dict(doc=torch.empty(cap, dtype=torch.int32, device=dev), term=torch.empty(cap, dtype=torch.int32, device=dev),
                n_tokens=torch.empty(n, dtype=torch.int32, device=dev), flags=torch.empty(n, dtype=torch.int32, device=dev),
                n_total=torch.empty(1, dtype=torch.int32, device=dev),
                unknown_off=torch.empty(cap, dtype=torch.int64, device=dev),
                unknown_len=torch.empty(cap, dtype=torch.int32, device=dev),
                n_unknown=torch.empty(1, dtype=torch.int32, device=dev), capacity=cap)
-    _check(load().thr_text_tokens(pb, pp, n, n_bytes, pt, ps, slots.shape[0], pk, pkp, term_ptr.shape[0] - 1, cap,
-                                  out["doc"].data_ptr(), out["term"].data_ptr(), out["n_tokens"].data_ptr(),
-                                  out["flags"].data_ptr(), out["n_total"].data_ptr(), out["unknown_off"].data_ptr(),
-                                  out["unknown_len"].data_ptr(), out["n_unknown"].data_ptr(), ws.data_ptr(),
-                                  nbytes, _stream()), "thr_text_tokens")
+    head = (pb, pp, n, n_bytes, pt, ps, slots.shape[0], pk, pkp, term_ptr.shape[0] - 1)
+    tail = (cap, out["doc"].data_ptr(), out["term"].data_ptr(), out["n_tokens"].data_ptr(), out["flags"].data_ptr(),
+            out["n_total"].data_ptr(), out["unknown_off"].data_ptr(), out["unknown_len"].data_ptr(),
+            out["n_unknown"].data_ptr(), ws.data_ptr(), nbytes, _stream())
+    if _analysis is None:
+        _check(load().thr_text_tokens(*head, *tail), "thr_text_tokens")
+    else:
+        _check(load().thr_text_tokens_analyzed(*head, *_analysis, *tail), "thr_text_tokens_analyzed")
     return out
+
+
+def text_tokens_analyzed_workspace_bytes(n_texts: int, n_bytes: int, token_capacity: int) -> int:
+    return int(load().thr_text_tokens_analyzed_workspace_bytes(n_texts, n_bytes, token_capacity))
+
+
+def text_tokens_analyzed(text_bytes, text_ptr, n_bytes: int, table, slots, term_bytes, term_ptr, stop_slots=None,
+                         stop_bytes=None, stop_ptr=None, step_ptr=(0,), rules=None, workspace=None,
+                         token_capacity: Optional[int] = None):
+    """thr_text_tokens_analyzed (thr_hip_text.h) -> text_tokens' dict, with the stop tokens dropped and the stems
+    looked up.  The stop set as vocab_insert built it (stop_slots int64 [capacity, 2], stop_bytes u8, stop_ptr i64
+    [n_stop + 1]) or three Nones; ``step_ptr``: a HOST sequence of n_steps + 1 ascending ints from 0; ``rules``:
+    a device uint8 tensor of step_ptr[-1] records of STEM_RULE_BYTES bytes (None when there is none)."""
+    if (stop_slots is None) != (stop_bytes is None) or (stop_slots is None) != (stop_ptr is None):
+        raise NativeError("text_tokens_analyzed: the stop set is slots, bytes and pointers, or none of them")
+    pss = _dev(stop_slots, torch.int64, "stop_slots", 2)
+    if stop_slots is not None and stop_slots.shape[1] != 2:
+        raise NativeError("text_tokens_analyzed: stop_slots is int64 [capacity, 2]")
+    psb = _dev(stop_bytes, torch.uint8, "stop_bytes", 1)
+    psp = _dev(stop_ptr, torch.int64, "stop_ptr", 1)
+    steps = [int(v) for v in step_ptr]
+    if not 1 <= len(steps) <= STEM_MAX_STEPS + 1:
+        raise NativeError(f"text_tokens_analyzed: 0 .. {STEM_MAX_STEPS} steps, step_ptr holds {len(steps)} entries")
+    if steps[0] != 0 or any(a > b for a, b in zip(steps, steps[1:])) or steps[-1] > STEM_MAX_RULES:
+        raise NativeError(f"text_tokens_analyzed: step_ptr ascends from 0 to at most {STEM_MAX_RULES}, got {steps}")
+    pr = _dev(rules, torch.uint8, "rules", 1)
+    if (rules.shape[0] if rules is not None else 0) < steps[-1] * STEM_RULE_BYTES:
+        raise NativeError(f"text_tokens_analyzed: {steps[-1]} rules of {STEM_RULE_BYTES} bytes, the array holds "
+                          f"{0 if rules is None else rules.shape[0]} bytes")
+    h_steps = (C.c_int32 * len(steps))(*steps)
+    analysis = (pss, 0 if stop_slots is None else stop_slots.shape[0], psb, psp,
+                0 if stop_ptr is None else stop_ptr.shape[0] - 1, C.cast(h_steps, C.c_void_p), len(steps) - 1,
+                pr if steps[-1] else None)
+    return text_tokens(text_bytes, text_ptr, n_bytes, table, slots, term_bytes, term_ptr, workspace=workspace,
+                       token_capacity=token_capacity, _analysis=analysis)
 
 
 def query_terms(rows: dict, workspace=None):

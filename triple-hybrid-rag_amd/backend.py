@@ -64,6 +64,7 @@ class GpuIndexClient(ClientIngest):
     sets_collections = True  # derives the index's per-doc collection ids from the store's rows
     multi_tenant = False     # set by __init__: no org_id of its own over a store with an org_ids column
     graph_cascade = False    # set by __init__: a document delete also removes the entities first extracted from it
+    tokenizer = staticmethod(tokenize)   # set by __init__: what turns a query's and a chunk's text into tokens
 
     # Derived state, made by __init__ (the class values serve a subclass with an __init__ of its own):
     #   attribute     derived from                                   filled by           dropped by (backend_ingest)
@@ -94,7 +95,8 @@ class GpuIndexClient(ClientIngest):
         the store's column), each RPC and ``graph_chunks`` rank inside {"org": p_org_id} (+ "collection") through the
         index's scopes, a missing or unknown org gets no rows, ``table().eq("org_id", x)`` filters rows, and an insert
         needs ``org_id`` on every row.
-        tokenizer: what the index's vocabulary was built with (default ``tokenize``, from_rows' default).
+        tokenizer: what the index's vocabulary was built with (default ``tokenize``, from_rows' default); queries and
+        inserted chunks go through it.  An ``Analyzer``'s ``.tokenize`` (stop list + stemming) counts as a table's below.
         device_text: query and chunk text become term ids on the device (GpuIndex.set_vocabulary from ``store.vocab``
         -- derived state, rebuilt here, never saved): ``_lexical`` and ``insert_children`` take that route and
         ``query_terms_batch`` serves batches.  Needs ``tokenize`` or a TextTable's ``.tokenize`` as the tokenizer; any
@@ -408,7 +410,7 @@ class GpuIndexClient(ClientIngest):
     def _query_terms(self, query: str) -> Optional[List[int]]:
         """The distinct term ids of the query in order of first appearance (at most
         THR_BM25_MAX_TERMS), or None when nothing can match."""
-        terms, _, flags = host_query_row(tokenize(query), self.store.vocab)
+        terms, _, flags = host_query_row(self.tokenizer(query), self.store.vocab)
         if not terms or getattr(self.index, "lex", True) is None:
             return None
         # AND semantics (plainto_tsquery, rag2_schema.sql:365): a token no chunk holds, or a term

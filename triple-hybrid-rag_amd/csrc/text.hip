@@ -28,6 +28,15 @@
 // query_terms    one wave per query over its token rows, 64 at a time: the distinct known ids in order of
 //                first appearance.
 // Nothing waits for another workgroup, nothing is read back, every output is the same bits every run.
+//
+// thr_text_tokens_analyzed (thr_hip_text.h) is the same three kernels with the token-level analysis switched on
+// by a template parameter: a stop set (the vocabulary's layout, the vocabulary's probe) and suffix rules.  A stop
+// token gets no row, so the count pass must know it: it walks each token and probes the stop set there (only when
+// there is a stop list), and the emit pass decides again, from the same bytes, the same way.  The emit pass keeps
+// the token's last 32 lowered code points in eight 64-bit shift registers while it walks, matches the rules of
+// each step against them (staged in LDS once per workgroup) and, when something was stripped, walks the kept
+// prefix again for its hash.
+#include "../../include/thr_hip_text.h"
 #include "text_common.hpp"
 
 namespace thr {
@@ -42,6 +51,10 @@ constexpr int TX_LDS = 16 + TX_SLICE + 16;            // the slice starts at byt
 constexpr int TX_BIT0 = 32;                           // boundary bits: 32 positions of halo on either side
 constexpr int TX_BITS = TX_BIT0 + TX_SLICE + 32;
 constexpr int TX_SCAN_THREADS = 1024;
+constexpr int TX_TAIL_CPS = THR_STEM_MAX_STEPS * THR_STEM_MAX_SUFFIX;   // what the steps can strip between them
+constexpr int TX_TAIL_WORDS = TX_TAIL_CPS / 4;
+constexpr int TX_RULE_WORDS = 6;                      // a 24-byte rule as uint32 words
+static_assert(TX_TAIL_CPS % 4 == 0 && THR_STEM_MAX_SUFFIX == 8, "a rule's suffix is two 64-bit words of code points");
 static_assert(TX_SLICE % (TX_THREADS * 16) == 0, "slices are staged in 16-byte pieces");
 static_assert(TX_UNIT % WAVE == 0, "a wave takes whole rounds");
 
@@ -183,25 +196,6 @@ __device__ __forceinline__ void tx_classify(const TextArgs& T, const Slice& S, i
     start = !(pe & TX_WORD);
 }
 
-__global__ __launch_bounds__(TX_THREADS) void text_count(TextArgs T, int32_t* __restrict__ unit_count) {
-    __shared__ __attribute__((aligned(16))) uint8_t text[TX_LDS];
-    __shared__ uint32_t bits[TX_BITS / 32];
-    __shared__ int64_t range[2];
-    Slice S;
-    S.text = text;
-    S.bits = bits;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    tx_stage(T, blockIdx.x, S, range);
-    int c = 0;
-#pragma unroll 1
-    for (int r = 0; r < TX_ROUNDS; ++r) {
-        bool start, bad;
-        tx_classify(T, S, wave * TX_UNIT + r * WAVE + lane, start, bad);
-        c += __popcll(__ballot(start));
-    }
-    if (lane == 0) unit_count[(int64_t)blockIdx.x * TX_WAVES + wave] = c;
-}
-
 // out[i] = in[0] + .. + in[i - 1] for i in 0 .. n (n + 1 values); one workgroup.
 __global__ __launch_bounds__(TX_SCAN_THREADS) void text_scan(const int32_t* in, int64_t n, int32_t* out,
                                                              int32_t* total) {
@@ -224,13 +218,27 @@ __global__ __launch_bounds__(TX_SCAN_THREADS) void text_scan(const int32_t* in, 
     }
 }
 
-// The token that starts at byte p of a text that ends at ``end``: its byte length and its term id (-1: none).
-__device__ __forceinline__ int32_t tx_lookup(const TextArgs& T, const Vocab& V, int64_t p, int64_t end, int32_t& tok_len) {
+// The last THR_STEM_MAX_STEPS * THR_STEM_MAX_SUFFIX lowered code points of a token, 16 bits each, the last one in
+// the low bits of w[0].  Only ever indexed by constants (unrolled): it lives in registers.
+struct Tail {
+    uint64_t w[TX_TAIL_WORDS];
+};
+
+// Walk the token that starts at byte p of a text that ends at ``end``, at most max_cp characters of it:
+// -> the byte behind the last character taken; the FNV state over the lowered characters (before tx_fnv_end),
+// their encoded length and their number; with TAIL the last lowered code points.
+template <bool TAIL>
+__device__ __forceinline__ int64_t tx_walk(const TextArgs& T, int64_t p, int64_t end, int64_t max_cp, uint64_t& h_out,
+                                           int64_t& low_len_out, int64_t& n_cp_out, Tail& tail) {
     const uint8_t* B = T.bytes;
     uint64_t h = TX_FNV_BASIS;
     int64_t q = p;
-    int64_t low_len = 0;               // bytes of the lowered token
-    while (q < end) {
+    int64_t low_len = 0, n_cp = 0;     // bytes and characters of the lowered token
+    if (TAIL) {
+#pragma unroll
+        for (int j = 0; j < TX_TAIL_WORDS; ++j) tail.w[j] = 0;
+    }
+    while (q < end && n_cp < max_cp) {
         const int avail = end - q < 4 ? (int)(end - q) : 4;
         int len;
         const uint32_t e = tx_decode(B[q], avail > 1 ? B[q + 1] : 0, avail > 2 ? B[q + 2] : 0, avail, T.table, len);
@@ -238,9 +246,26 @@ __device__ __forceinline__ int32_t tx_lookup(const TextArgs& T, const Vocab& V, 
         const uint32_t cp = e & 0xFFFF;
         h = tx_fnv_cp(h, cp);
         low_len += cp < 0x80 ? 1 : cp < 0x800 ? 2 : 3;
+        ++n_cp;
+        if (TAIL) {
+#pragma unroll
+            for (int j = TX_TAIL_WORDS - 1; j > 0; --j) tail.w[j] = (tail.w[j] << 16) | (tail.w[j - 1] >> 48);
+            tail.w[0] = (tail.w[0] << 16) | cp;
+        }
         q += len;
     }
-    tok_len = (int32_t)(q - p);
+    h_out = h;
+    low_len_out = low_len;
+    n_cp_out = n_cp;
+    return q;
+}
+
+// Probe table V for the lowered bytes [p, q) of a text that ends at ``end`` (h: their FNV state, low_len: their
+// lowered length) -> the id of the key that equals them byte for byte, or -1.  The vocabulary's lookup and the
+// stop set's: one function.
+__device__ __forceinline__ int32_t tx_probe(const TextArgs& T, const Vocab& V, int64_t p, int64_t q, int64_t end,
+                                            uint64_t h, int64_t low_len) {
+    const uint8_t* B = T.bytes;
     h = tx_fnv_end(h);
     uint32_t s = tx_home(h, V.mask);
     for (uint32_t probe = 0; probe <= V.mask; ++probe, s = (s + 1) & V.mask) {
@@ -277,6 +302,106 @@ __device__ __forceinline__ int32_t tx_lookup(const TextArgs& T, const Vocab& V, 
     return -1;
 }
 
+constexpr int64_t TX_NO_LIMIT = INT64_MAX;
+
+// The token that starts at byte p of a text that ends at ``end``: its byte length and its term id (-1: none).
+__device__ __forceinline__ int32_t tx_lookup(const TextArgs& T, const Vocab& V, int64_t p, int64_t end, int32_t& tok_len) {
+    uint64_t h;
+    int64_t low_len, n_cp;
+    Tail none;
+    const int64_t q = tx_walk<false>(T, p, end, TX_NO_LIMIT, h, low_len, n_cp, none);
+    tok_len = (int32_t)(q - p);
+    return tx_probe(T, V, p, q, end, h, low_len);
+}
+
+// ---- the token-level analysis (thr_hip_text.h): a stop set in the vocabulary's layout and a table of suffix rules
+struct Analysis {
+    Vocab stop;                              // slots null: no stop list
+    const uint32_t* rules;                   // TX_RULE_WORDS uint32 per rule: tail[8] as four words, len, min_stem
+    int32_t step[THR_STEM_MAX_STEPS + 1];    // rules step[s] .. step[s + 1] - 1 are step s; checked on the host
+    int32_t n_steps;
+};
+
+// Rules to LDS, once per workgroup, with len clamped to 1 .. THR_STEM_MAX_SUFFIX and min_stem to >= 1: the table is
+// device memory, which the host cannot check.  The caller's next barrier publishes them.
+__device__ __forceinline__ void tx_stage_rules(const Analysis& A, uint32_t* rules) {
+    const int words = A.step[A.n_steps] * TX_RULE_WORDS;
+    for (int i = threadIdx.x; i < words; i += TX_THREADS) {
+        uint32_t v = A.rules[i];
+        const int field = i % TX_RULE_WORDS;
+        if (field == 4) v = (int32_t)v < 1 ? 1u : v > (uint32_t)THR_STEM_MAX_SUFFIX ? (uint32_t)THR_STEM_MAX_SUFFIX : v;
+        if (field == 5) v = (int32_t)v < 1 ? 1u : v;
+        rules[i] = v;
+    }
+}
+
+// Code points s .. s + 7 from the end of the token (s <= TX_TAIL_CPS - THR_STEM_MAX_SUFFIX), 16 bits each.
+__device__ __forceinline__ void tx_tail_window(const Tail& t, int s, uint64_t& lo, uint64_t& hi) {
+    const int word = s >> 2, sh = (s & 3) * 16;
+    uint64_t a = 0, b = 0, c = 0;
+#pragma unroll
+    for (int j = 0; j < TX_TAIL_WORDS; ++j) {
+        if (j == word) a = t.w[j];
+        if (j == word + 1) b = t.w[j];
+        if (j == word + 2) c = t.w[j];
+    }
+    lo = sh ? (a >> sh) | (b << (64 - sh)) : a;
+    hi = sh ? (b >> sh) | (c << (64 - sh)) : b;
+}
+
+// The code points the steps strip from a token of n_cp characters: per step the FIRST rule in table order whose
+// suffix ends the token as it stands and leaves at least its min_stem characters.
+__device__ __forceinline__ int tx_stem(const Analysis& A, const uint32_t* rules, const Tail& tail, int64_t n_cp) {
+    int s = 0;
+    for (int st = 0; st < A.n_steps; ++st) {
+        uint64_t lo, hi;
+        tx_tail_window(tail, s, lo, hi);
+        for (int r = A.step[st]; r < A.step[st + 1]; ++r) {
+            const uint32_t* R = rules + r * TX_RULE_WORDS;
+            const int L = (int)R[4];
+            if (n_cp - s - L < (int64_t)(int32_t)R[5]) continue;
+            const uint64_t rlo = R[0] | ((uint64_t)R[1] << 32), rhi = R[2] | ((uint64_t)R[3] << 32);
+            const uint64_t mlo = L >= 4 ? ~0ull : (1ull << (16 * L)) - 1;
+            const uint64_t mhi = L <= 4 ? 0ull : L >= 8 ? ~0ull : (1ull << (16 * (L - 4))) - 1;
+            if ((((lo ^ rlo) & mlo) | ((hi ^ rhi) & mhi)) == 0) {
+                s += L;
+                break;
+            }
+        }
+    }
+    return s;
+}
+
+// Is the token at byte p a stop word?  The whole lowered token, before any stemming.  (The count pass.)
+__device__ __forceinline__ bool tx_is_stop(const TextArgs& T, const Analysis& A, int64_t p, int64_t end) {
+    uint64_t h;
+    int64_t low_len, n_cp;
+    Tail none;
+    const int64_t q = tx_walk<false>(T, p, end, TX_NO_LIMIT, h, low_len, n_cp, none);
+    return tx_probe(T, A.stop, p, q, end, h, low_len) >= 0;
+}
+
+// The analysed token at byte p -> kept (false: a stop word, no row); its term is the STEM's id and tok_len the
+// bytes of the kept prefix in the text.  A stem shorter than the token is walked again for its hash.
+__device__ __forceinline__ bool tx_lookup_analyzed(const TextArgs& T, const Vocab& V, const Analysis& A,
+                                                   const uint32_t* rules, int64_t p, int64_t end, int32_t& term,
+                                                   int32_t& tok_len) {
+    uint64_t h;
+    int64_t low_len, n_cp;
+    Tail tail;
+    int64_t q = tx_walk<true>(T, p, end, TX_NO_LIMIT, h, low_len, n_cp, tail);
+    if (A.stop.slots && tx_probe(T, A.stop, p, q, end, h, low_len) >= 0) return false;
+    const int strip = tx_stem(A, rules, tail, n_cp);
+    if (strip > 0) {
+        Tail none;
+        int64_t kept;
+        q = tx_walk<false>(T, p, end, n_cp - strip, h, low_len, kept, none);
+    }
+    tok_len = (int32_t)(q - p);
+    term = tx_probe(T, V, p, q, end, h, low_len);
+    return true;
+}
+
 // The text of byte gp among texts d_lo .. d_hi of the slice, or -1 (a byte in front of ptr[0] or behind ptr[n]).
 __device__ __forceinline__ int64_t tx_doc(const TextArgs& T, const Slice& S, int64_t gp) {
     const int64_t lo = S.d_lo < 0 ? 0 : S.d_lo;
@@ -286,11 +411,15 @@ __device__ __forceinline__ int64_t tx_doc(const TextArgs& T, const Slice& S, int
     return d;
 }
 
-__global__ __launch_bounds__(TX_THREADS) void text_emit(TextArgs T, Vocab V, const int32_t* __restrict__ unit_off,
-                                                        int64_t capacity, int32_t* __restrict__ tok_doc,
-                                                        int32_t* __restrict__ tok_term, int64_t* __restrict__ tok_off,
-                                                        int32_t* __restrict__ tok_len, int32_t* __restrict__ n_tokens,
-                                                        int32_t* __restrict__ flags, int32_t* __restrict__ unit_unknown) {
+// The end of text d for a token that starts at byte gp (d < 0: the byte belongs to no text).
+__device__ __forceinline__ int64_t tx_text_end(const TextArgs& T, int64_t d, int64_t gp) {
+    const int64_t end = d >= 0 ? T.ptr[d + 1] : gp + 1;
+    return end < T.n_bytes ? end : T.n_bytes;
+}
+
+// ANALYZED: a token start that is a stop word is not counted (a token of no text is never one).
+template <bool ANALYZED>
+__global__ __launch_bounds__(TX_THREADS) void text_count(TextArgs T, Analysis A, int32_t* __restrict__ unit_count) {
     __shared__ __attribute__((aligned(16))) uint8_t text[TX_LDS];
     __shared__ uint32_t bits[TX_BITS / 32];
     __shared__ int64_t range[2];
@@ -298,6 +427,39 @@ __global__ __launch_bounds__(TX_THREADS) void text_emit(TextArgs T, Vocab V, con
     S.text = text;
     S.bits = bits;
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    tx_stage(T, blockIdx.x, S, range);
+    int c = 0;
+#pragma unroll 1
+    for (int r = 0; r < TX_ROUNDS; ++r) {
+        const int lp = wave * TX_UNIT + r * WAVE + lane;
+        bool start, bad;
+        tx_classify(T, S, lp, start, bad);
+        if (ANALYZED && start && A.stop.slots) {
+            const int64_t gp = S.g0 + lp;
+            const int64_t d = tx_doc(T, S, gp);
+            if (d >= 0 && tx_is_stop(T, A, gp, tx_text_end(T, d, gp))) start = false;
+        }
+        c += __popcll(__ballot(start));
+    }
+    if (lane == 0) unit_count[(int64_t)blockIdx.x * TX_WAVES + wave] = c;
+}
+
+template <bool ANALYZED>
+__global__ __launch_bounds__(TX_THREADS) void text_emit(TextArgs T, Vocab V, Analysis A,
+                                                        const int32_t* __restrict__ unit_off, int64_t capacity,
+                                                        int32_t* __restrict__ tok_doc, int32_t* __restrict__ tok_term,
+                                                        int64_t* __restrict__ tok_off, int32_t* __restrict__ tok_len,
+                                                        int32_t* __restrict__ n_tokens, int32_t* __restrict__ flags,
+                                                        int32_t* __restrict__ unit_unknown) {
+    __shared__ __attribute__((aligned(16))) uint8_t text[TX_LDS];
+    __shared__ uint32_t bits[TX_BITS / 32];
+    __shared__ int64_t range[2];
+    __shared__ uint32_t rules[ANALYZED ? THR_STEM_MAX_RULES * TX_RULE_WORDS : 1];
+    Slice S;
+    S.text = text;
+    S.bits = bits;
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    if (ANALYZED) tx_stage_rules(A, rules);       // (tx_stage's barriers stand between this and the first use)
     tx_stage(T, blockIdx.x, S, range);
     const int64_t unit = (int64_t)blockIdx.x * TX_WAVES + wave;
     int64_t row = unit_off[unit];
@@ -308,29 +470,32 @@ __global__ __launch_bounds__(TX_THREADS) void text_emit(TextArgs T, Vocab V, con
         const int lp = wave * TX_UNIT + r * WAVE + lane;
         bool start, bad;
         tx_classify(T, S, lp, start, bad);
-        const uint64_t starts = __ballot(start);
-        int32_t term = 0;
+        const int64_t gp = S.g0 + lp;
+        int64_t d = -1;
+        int32_t term = -1, len = 0;
+        bool kept = start;                        // a row is written for it
         if (start || bad) {
-            const int64_t gp = S.g0 + lp;
-            const int64_t d = tx_doc(T, S, gp);
+            d = tx_doc(T, S, gp);
             if (d >= 0 && bad) atomicOr(&flags[d], 1);
-            if (start) {
-                const int64_t at = row + __popcll(starts & below);
-                int64_t end = d >= 0 ? T.ptr[d + 1] : gp + 1;
-                end = end < T.n_bytes ? end : T.n_bytes;
-                int32_t len = 0;
-                term = d >= 0 ? tx_lookup(T, V, gp, end, len) : -1;
-                if (d >= 0) atomicAdd(&n_tokens[d], 1);
-                if (at < capacity) {
-                    tok_doc[at] = (int32_t)d;
-                    tok_term[at] = term;
-                    tok_off[at] = gp;
-                    tok_len[at] = len;
-                }
+            if (start && d >= 0) {
+                const int64_t end = tx_text_end(T, d, gp);
+                if (ANALYZED) kept = tx_lookup_analyzed(T, V, A, rules, gp, end, term, len);
+                else term = tx_lookup(T, V, gp, end, len);
+                if (kept) atomicAdd(&n_tokens[d], 1);
             }
         }
-        unknown += __popcll(__ballot(start && term < 0));
-        row += __popcll(starts);
+        const uint64_t keeps = __ballot(kept);
+        if (kept) {
+            const int64_t at = row + __popcll(keeps & below);
+            if (at < capacity) {
+                tok_doc[at] = (int32_t)d;
+                tok_term[at] = term;
+                tok_off[at] = gp;
+                tok_len[at] = len;
+            }
+        }
+        unknown += __popcll(__ballot(kept && term < 0));
+        row += __popcll(keeps);
     }
     if (lane == 0) unit_unknown[unit] = unknown;
 }
@@ -466,13 +631,14 @@ extern "C" size_t thr_text_tokens_workspace_bytes(int64_t n_texts, int64_t n_byt
     return A.total;
 }
 
-extern "C" int thr_text_tokens(const uint8_t* text_bytes, const int64_t* text_ptr, int64_t n_texts, int64_t n_bytes,
-                               const uint32_t* table, const void* slots, int64_t capacity, const uint8_t* term_bytes,
-                               const int64_t* term_ptr, int64_t n_vocab, int64_t token_capacity, int32_t* tok_doc,
-                               int32_t* tok_term, int32_t* n_tokens, int32_t* flags, int32_t* n_total,
-                               int64_t* unknown_off, int32_t* unknown_len, int32_t* n_unknown, void* workspace,
-                               size_t workspace_bytes, thr_stream_t stream) {
-    clear_status();
+// thr_text_tokens' refusals and launches; ANALYZED: with the analysis ``A`` (checked by the caller).
+template <bool ANALYZED>
+static int text_tokens_run(const uint8_t* text_bytes, const int64_t* text_ptr, int64_t n_texts, int64_t n_bytes,
+                           const uint32_t* table, const void* slots, int64_t capacity, const uint8_t* term_bytes,
+                           const int64_t* term_ptr, int64_t n_vocab, const Analysis& An, int64_t token_capacity,
+                           int32_t* tok_doc, int32_t* tok_term, int32_t* n_tokens, int32_t* flags, int32_t* n_total,
+                           int64_t* unknown_off, int32_t* unknown_len, int32_t* n_unknown, void* workspace,
+                           size_t workspace_bytes, thr_stream_t stream) {
     THR_RETURN_IF(!text_shape_ok(n_texts, n_bytes), THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(token_capacity < 1 || token_capacity > THR_TEXT_MAX_BYTES, THR_ERR_UNSUPPORTED);
     THR_RETURN_IF(!text_bytes || !text_ptr || !table || !slots || !term_bytes || !term_ptr || !tok_doc || !tok_term ||
@@ -495,15 +661,16 @@ extern "C" int thr_text_tokens(const uint8_t* text_bytes, const int64_t* text_pt
     if (e != hipSuccess) return (int)e;
     const TextArgs T = {text_bytes, text_ptr, n_texts, n_bytes, table};
     const Vocab V = {(const VocabSlot*)slots, (uint32_t)(capacity - 1), term_bytes, term_ptr, n_vocab};
-    hipLaunchKernelGGL(text_count, dim3((unsigned)slices), dim3(TX_THREADS), 0, st, T, P.unit_off);
+    hipLaunchKernelGGL(text_count<ANALYZED>, dim3((unsigned)slices), dim3(TX_THREADS), 0, st, T, An, P.unit_off);
     int rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(text_scan, dim3(1), dim3(TX_SCAN_THREADS), 0, st, (const int32_t*)P.unit_off, units, P.unit_off,
                        n_total);
     rc = launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(text_emit, dim3((unsigned)slices), dim3(TX_THREADS), 0, st, T, V, (const int32_t*)P.unit_off,
-                       token_capacity, tok_doc, tok_term, P.tok_off, P.tok_len, n_tokens, flags, P.unit_unknown);
+    hipLaunchKernelGGL(text_emit<ANALYZED>, dim3((unsigned)slices), dim3(TX_THREADS), 0, st, T, V, An,
+                       (const int32_t*)P.unit_off, token_capacity, tok_doc, tok_term, P.tok_off, P.tok_len, n_tokens, flags,
+                       P.unit_unknown);
     rc = launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(text_scan, dim3(1), dim3(TX_SCAN_THREADS), 0, st, (const int32_t*)P.unit_unknown, units,
@@ -514,6 +681,61 @@ extern "C" int thr_text_tokens(const uint8_t* text_bytes, const int64_t* text_pt
                        (const int32_t*)P.unit_unknown, units, token_capacity, (const int32_t*)tok_term,
                        (const int64_t*)P.tok_off, (const int32_t*)P.tok_len, unknown_off, unknown_len);
     return launch_status();
+}
+
+extern "C" int thr_text_tokens(const uint8_t* text_bytes, const int64_t* text_ptr, int64_t n_texts, int64_t n_bytes,
+                               const uint32_t* table, const void* slots, int64_t capacity, const uint8_t* term_bytes,
+                               const int64_t* term_ptr, int64_t n_vocab, int64_t token_capacity, int32_t* tok_doc,
+                               int32_t* tok_term, int32_t* n_tokens, int32_t* flags, int32_t* n_total,
+                               int64_t* unknown_off, int32_t* unknown_len, int32_t* n_unknown, void* workspace,
+                               size_t workspace_bytes, thr_stream_t stream) {
+    clear_status();
+    return text_tokens_run<false>(text_bytes, text_ptr, n_texts, n_bytes, table, slots, capacity, term_bytes, term_ptr,
+                                  n_vocab, Analysis{}, token_capacity, tok_doc, tok_term, n_tokens, flags, n_total,
+                                  unknown_off, unknown_len, n_unknown, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t thr_text_tokens_analyzed_workspace_bytes(int64_t n_texts, int64_t n_bytes, int64_t token_capacity) {
+    return thr_text_tokens_workspace_bytes(n_texts, n_bytes, token_capacity);
+}
+
+extern "C" int thr_text_tokens_analyzed(const uint8_t* text_bytes, const int64_t* text_ptr, int64_t n_texts,
+                                        int64_t n_bytes, const uint32_t* table, const void* slots, int64_t capacity,
+                                        const uint8_t* term_bytes, const int64_t* term_ptr, int64_t n_vocab,
+                                        const void* stop_slots, int64_t stop_capacity, const uint8_t* stop_bytes,
+                                        const int64_t* stop_ptr, int64_t n_stop, const int32_t* h_step_ptr, int n_steps,
+                                        const void* rules, int64_t token_capacity, int32_t* tok_doc, int32_t* tok_term,
+                                        int32_t* n_tokens, int32_t* flags, int32_t* n_total, int64_t* unknown_off,
+                                        int32_t* unknown_len, int32_t* n_unknown, void* workspace, size_t workspace_bytes,
+                                        thr_stream_t stream) {
+    clear_status();
+    Analysis A = {};
+    // the rule table: the step pointers are HOST memory (five numbers at the most) and checked here
+    THR_RETURN_IF(n_steps < 0 || n_steps > THR_STEM_MAX_STEPS, THR_ERR_INVALID);
+    THR_RETURN_IF(n_steps > 0 && !h_step_ptr, THR_ERR_INVALID);
+    A.n_steps = n_steps;
+    for (int s = 0; s <= n_steps && n_steps > 0; ++s) {
+        const int32_t v = h_step_ptr[s];
+        THR_RETURN_IF(s == 0 ? v != 0 : v < A.step[s - 1], THR_ERR_INVALID);
+        THR_RETURN_IF(v > THR_STEM_MAX_RULES, THR_ERR_INVALID);
+        A.step[s] = v;
+    }
+    const int n_rules = A.step[n_steps];
+    THR_RETURN_IF(n_rules > 0 && (!rules || ((uintptr_t)rules & 7) != 0), THR_ERR_INVALID);
+    A.rules = (const uint32_t*)rules;
+    // the stop set: capacity 0 with null pointers is no stop list, anything else a whole vocabulary
+    if (stop_capacity == 0) {
+        THR_RETURN_IF(stop_slots || stop_bytes || stop_ptr || n_stop != 0, THR_ERR_INVALID);
+    } else {
+        THR_RETURN_IF(!stop_slots || !stop_bytes || !stop_ptr, THR_ERR_INVALID);
+        THR_RETURN_IF(thr_vocab_table_bytes(stop_capacity) == 0 || n_stop < 0 || n_stop > stop_capacity / 2,
+                      THR_ERR_INVALID);
+        THR_RETURN_IF(((uintptr_t)stop_slots & 15) != 0 || ((uintptr_t)stop_ptr & 7) != 0, THR_ERR_INVALID);
+        A.stop = {(const VocabSlot*)stop_slots, (uint32_t)(stop_capacity - 1), stop_bytes, stop_ptr, n_stop};
+    }
+    return text_tokens_run<true>(text_bytes, text_ptr, n_texts, n_bytes, table, slots, capacity, term_bytes, term_ptr,
+                                 n_vocab, A, token_capacity, tok_doc, tok_term, n_tokens, flags, n_total, unknown_off,
+                                 unknown_len, n_unknown, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t thr_query_terms_workspace_bytes(int n_queries) {

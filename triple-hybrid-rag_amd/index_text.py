@@ -18,6 +18,10 @@ holds an exceptional code point, a code point above U+FFFF or a surrogate is EXC
 it, the wrappers here find it on the host beforehand (one regular-expression search per text) and answer it
 with the table's host tokenizer, so the answer is always the host's.
 
+The token-level half of the analysis is DATA as well: an ``Analyzer`` puts a stop set and a table of suffix rules
+(truncation only, so a stem is the lowered form of a prefix of its token's bytes) on top of a ``TextTable`` and
+stands wherever one stands; with it set, the token rows come from thr_text_tokens_analyzed (thr_hip_text.h).
+
 What stays on the host: the UTF-8 encoding (("utf-8", "surrogatepass"), as index_entities), the exceptional
 texts, and the strings of unknown tokens (an ingest numbers them: GpuIndexClient.insert_children).
 
@@ -47,7 +51,8 @@ CONTEXTS = ("a{}a", " {} ", "a{}", "{}a")       # between letters, between space
 
 def tokenize(text: str) -> List[str]:
     """Lower-cased word tokens (the reference leaves tokenisation to PostgreSQL's 'portuguese' text-search configuration,
-    which is not reproduced: no stemming).  ``backend.tokenize`` is this object; ``TextTable.default()`` is built from it."""
+    which is not reproduced: this is the character half alone; ``Analyzer`` adds a stop list and suffix stemming of the
+    project's own).  ``backend.tokenize`` is this object; ``TextTable.default()`` is built from it."""
     return _TOKEN.findall(text.lower())
 
 
@@ -136,15 +141,173 @@ class TextTable:
         return TextTable(entries, lambda text: _TOKEN.findall("".join(map(fn, text))))
 
 
-def is_table_tokenizer(tokenizer) -> Optional[TextTable]:
-    """The TextTable whose ``.tokenize`` this is, or None."""
+class Analyzer:
+    """The token-level analysis on top of a ``TextTable``: a stop list and suffix stemming, as DATA.  This class
+    IS the definition (thr_hip_text.h restates it; the device is held to it bit for bit):
+
+        stem(tok):      for each step: among the step's rules (suffix, min_stem) with tok.endswith(suffix) and
+                        len(tok) - len(suffix) >= min_stem the one with the longest suffix is taken (none: the step
+                        does nothing) and tok = tok[:-len(suffix)]
+        tokenize(text): [stem(t) for t in table.tokenize(text) if t not in stop]
+
+    Lengths are code points of the lowered token (after the table's character map); the stop check is made on the
+    whole lowered token, before stemming; a rule strips and never replaces, so a stem is the lowered form of a
+    prefix of the token's bytes in the text, and everything behind the tokenizer works on a (byte offset, byte
+    length) place as before.  It stands wherever a TextTable stands: ``set_vocabulary(terms, table=analyzer)``,
+    ``GpuIndexClient(tokenizer=analyzer.tokenize, device_text=True)``, ``from_rows(tokenizer=analyzer.tokenize)``.
+    An exceptional text is answered on the host, with the stop list and the stemmer applied on top of the table's
+    host tokenizer.  Nothing of it is saved with an index: it is handed to the client that opens the store."""
+
+    def __init__(self, table: Optional[TextTable] = None, stop: Sequence[str] = (), steps: Sequence[Sequence[Tuple[str, int]]] = ()):
+        self.table = table if table is not None else TextTable.default()
+        self.stop: Tuple[str, ...] = tuple(dict.fromkeys(stop))
+        self.steps: Tuple[Tuple[Tuple[str, int], ...], ...] = tuple(tuple((s, int(m)) for s, m in step) for step in steps)
+        for w in self.stop:
+            self._fixed_point(w, "stop word")
+        if len(self.steps) > N.STEM_MAX_STEPS:
+            raise ValueError(f"Analyzer: {len(self.steps)} steps, at most THR_STEM_MAX_STEPS ({N.STEM_MAX_STEPS})")
+        if sum(map(len, self.steps)) > N.STEM_MAX_RULES:
+            raise ValueError(f"Analyzer: {sum(map(len, self.steps))} rules, at most THR_STEM_MAX_RULES ({N.STEM_MAX_RULES})")
+        for i, step in enumerate(self.steps):
+            seen = set()
+            for suffix, min_stem in step:
+                if suffix == "":
+                    raise ValueError(f"Analyzer: step {i} holds an empty suffix")
+                if len(suffix) > N.STEM_MAX_SUFFIX:
+                    raise ValueError(f"Analyzer: suffix {suffix!r} of step {i} is longer than THR_STEM_MAX_SUFFIX "
+                                     f"({N.STEM_MAX_SUFFIX}) code points")
+                self._fixed_point(suffix, f"suffix of step {i}")
+                if min_stem < 1:
+                    raise ValueError(f"Analyzer: min_stem {min_stem} of suffix {suffix!r} in step {i} is below 1 "
+                                     "(a stem is never empty)")
+                if suffix in seen:
+                    raise ValueError(f"Analyzer: suffix {suffix!r} occurs twice in step {i}")
+                seen.add(suffix)
+        self._stop = frozenset(self.stop)
+        # longest suffix first (two suffixes of one length cannot both end a token): first match = longest match
+        self._compiled = tuple(tuple(sorted(step, key=lambda r: -len(r[0]))) for step in self.steps)
+
+    def _fixed_point(self, w: str, what: str) -> None:
+        if self.table.is_exceptional(w):
+            raise ValueError(f"Analyzer: {what} {w!r} holds an exceptional code point")
+        if self.table.tokenize(w) != [w]:
+            raise ValueError(f"Analyzer: {what} {w!r} is not a fixed point of the table's tokenizer "
+                             f"(it gives {self.table.tokenize(w)!r})")
+
+    # ------------------------------------------------------------ what a TextTable has
+    @property
+    def entries(self) -> np.ndarray:
+        return self.table.entries
+
+    def is_exceptional(self, text: str) -> bool:
+        return self.table.is_exceptional(text)
+
+    def exceptional_among(self, texts: Sequence[str]) -> List[int]:
+        return self.table.exceptional_among(texts)
+
+    def restate(self, text: str) -> List[str]:
+        """The CHARACTER model alone (TextTable.restate): the lowered slice at an unknown stem's place is the stem."""
+        return self.table.restate(text)
+
+    @property
+    def trivial(self) -> bool:
+        """No stop words and no rules: the analyzer is its table."""
+        return not self.stop and not any(self.steps)
+
+    # ------------------------------------------------------------ the definition
+    def stem(self, tok: str) -> str:
+        for step in self._compiled:
+            for suffix, min_stem in step:
+                if len(tok) - len(suffix) >= min_stem and tok.endswith(suffix):
+                    tok = tok[:-len(suffix)]
+                    break
+        return tok
+
+    def tokenize(self, text: str) -> List[str]:
+        """The host tokenizer (from_rows, GpuIndexClient(tokenizer=)): also the answer for an exceptional text."""
+        stop = self._stop
+        return [self.stem(t) for t in self.table.tokenize(text) if t not in stop]
+
+    # ------------------------------------------------------------ the device tables (thr_hip_text.h)
+    def rule_table(self) -> Tuple[List[int], np.ndarray]:
+        """-> (step_ptr, rules uint8 [n_rules * THR_STEM_RULE_BYTES]): per step longest suffix first, a record
+        { uint16 tail[8] (the suffix from its END), int32 len, int32 min_stem }."""
+        step_ptr, recs = [0], []
+        for step in self._compiled:
+            for suffix, min_stem in step:
+                rec = np.zeros(N.STEM_RULE_BYTES, dtype=np.uint8)
+                rec[:16].view(np.uint16)[:len(suffix)] = [ord(c) for c in reversed(suffix)]
+                rec[16:].view(np.int32)[:] = (len(suffix), min(min_stem, 0x7FFFFFFF))
+                recs.append(rec)
+            step_ptr.append(len(recs))
+        return step_ptr, (np.concatenate(recs) if recs else np.zeros(0, dtype=np.uint8))
+
+    # ------------------------------------------------------------ the shipped example
+    @staticmethod
+    def portuguese(fold: bool = False) -> "Analyzer":
+        """A light Portuguese analysis, THE PROJECT'S OWN: a function-word stop list written for this project
+        (articles, prepositions and their contractions, pronouns, conjunctions, the common forms of ser / estar /
+        ter / haver) and three truncation steps -- plural; gender, adverb, diminutive and -ão; the common noun
+        and verb endings as they stand once the gender vowel is gone.  It is NEITHER the Snowball stemmer NOR the
+        PostgreSQL stop file, it claims no equality with the 'portuguese' text-search configuration, and it is
+        checked only against the pairs listed in tests/test_text_analyzer_host.py.  ``fold``: over the
+        accent-folding table (``fold_accents``), with the list and the suffixes folded the same way."""
+        table = _fold_table() if fold else TextTable.default()
+        fix = (lambda w: "".join(map(fold_accents, w))) if fold else (lambda w: w)
+        steps = [[(fix(s), m) for s, m in step] for step in _PT_STEPS]
+        steps = [list(dict(step).items()) for step in steps]          # (folding can make two suffixes one)
+        return Analyzer(table, [fix(w) for w in _PT_STOP.split()], steps)
+
+
+@functools.lru_cache(maxsize=1)
+def _fold_table() -> TextTable:
+    return TextTable.from_char_map(fold_accents)
+
+
+_PT_STOP = """
+o a os as um uma uns umas
+de em por para com sem sob sobre entre até após desde contra perante
+do da dos das no na nos nas pelo pela pelos pelas ao aos à às num numa nuns numas dum duma
+deste desta destes destas desse dessa desses dessas daquele daquela daqueles daquelas disto disso daquilo
+neste nesta nestes nestas nesse nessa nesses nessas naquele naquela naqueles naquelas nisto nisso naquilo àquele àquela
+eu tu ele ela nós vós eles elas você vocês me te se lhe lhes vos
+meu minha meus minhas teu tua teus tuas seu sua seus suas nosso nossa nossos nossas
+este esta estes estas esse essa esses essas aquele aquela aqueles aquelas isto isso aquilo
+que quem qual quais cujo cuja onde quando como
+e ou mas nem porém contudo todavia porque pois embora enquanto logo portanto também já não mais muito
+ser sou és é somos são era eram foi foram seja sejam fosse fossem será serão sendo sido
+estar estou está estamos estão estava estavam esteve estiveram esteja estejam estando estado
+ter tenho tem têm temos tinha tinham teve tiveram tenha tenham tendo tido terá terão
+haver há hei havia haviam houve houveram haja hajam havendo havido
+"""
+_PT_STEPS = (
+    # plural
+    (("ões", 2), ("ães", 2), ("ais", 3), ("ns", 3), ("es", 3), ("s", 3)),
+    # gender, adverb, diminutive, -ão
+    (("mente", 4), ("zinho", 3), ("zinha", 3), ("inho", 3), ("inha", 3), ("ão", 2), ("a", 3), ("o", 3)),
+    # noun and verb endings, as they stand behind the two steps above (falado -> falad -> fal)
+    (("avam", 3), ("aram", 3), ("eram", 3), ("iram", 3), ("and", 3), ("end", 3), ("ind", 3), ("ar", 3), ("er", 3),
+     ("ir", 3), ("ad", 3), ("id", 3), ("av", 3), ("ou", 3), ("eu", 3), ("iu", 3), ("am", 3), ("em", 3), ("ei", 3),
+     ("al", 3), ("a", 3), ("e", 3), ("i", 3), ("o", 3)),
+)
+
+
+def is_table_tokenizer(tokenizer):
+    """The TextTable (or Analyzer) whose ``.tokenize`` this is, or None.  An Analyzer with no stop words and no
+    rules is its table."""
     owner = getattr(tokenizer, "__self__", None)
-    return owner if isinstance(owner, TextTable) and getattr(tokenizer, "__func__", None) is TextTable.tokenize else None
+    func = getattr(tokenizer, "__func__", None)
+    if isinstance(owner, TextTable) and func is TextTable.tokenize:
+        return owner
+    if isinstance(owner, Analyzer) and func is Analyzer.tokenize:
+        return owner.table if owner.trivial else owner
+    return None
 
 
 def tokenizer_table(tokenizer, needs: str) -> TextTable:
-    """The analysis table a tokenizer stands for: ``backend.tokenize`` is ``TextTable.default()``, a table's
-    ``.tokenize`` that table.  Any other is refused by name; ``needs`` begins the message (the caller's option)."""
+    """The analysis a tokenizer stands for: ``backend.tokenize`` is ``TextTable.default()``, a table's ``.tokenize``
+    that table, an ``Analyzer``'s ``.tokenize`` that analyzer.  Any other is refused by name; ``needs`` begins the
+    message (the caller's option)."""
     table = TextTable.default() if tokenizer is tokenize else is_table_tokenizer(tokenizer)
     if table is None:
         name = getattr(tokenizer, "__qualname__", None) or repr(tokenizer)
@@ -242,8 +405,9 @@ class TextSearch:
     # ------------------------------------------------------------ the vocabulary
     def set_vocabulary(self, terms: Sequence[str], table: Optional[TextTable] = None) -> "TextSearch":
         """The device vocabulary ``query_terms`` / ``text_rows`` look tokens up in (index set-up): terms[i] is
-        the string of term id i, as the tokenizer produces it (lowered).  ``table``: the analysis, default
-        ``TextTable.default()``.  Derived state: nothing of it is saved with the index.  Duplicates are
+        the string of term id i, as the tokenizer produces it (lowered; with an ``Analyzer``, a stem).  ``table``: the
+        analysis, default ``TextTable.default()``; an ``Analyzer``'s stop table and rules are uploaded beside the
+        character table and the token rows then come from thr_text_tokens_analyzed.  Derived state: nothing of it is saved with the index.  Duplicates are
         refused; after set_lexical the count must be the lexical index's vocabulary size."""
         terms = list(terms)
         ids = {t: i for i, t in enumerate(terms)}
@@ -254,11 +418,27 @@ class TextSearch:
             raise ValueError(f"set_vocabulary: {len(terms)} terms for the {L['rowptr'].shape[0] - 1} terms of the "
                              "lexical index (set_lexical)")
         table = table or TextTable.default()
+        if isinstance(table, Analyzer) and table.trivial:
+            table = table.table
         self.text = dict(table=table, table_dev=self._t(table.entries.view(np.int32), torch.int32), ids=ids,
                          term_bytes=torch.zeros(16, dtype=torch.uint8, device=self.device),
-                         term_ptr=torch.zeros(1, dtype=torch.int64, device=self.device), n_bytes=0, slots=None)
+                         term_ptr=torch.zeros(1, dtype=torch.int64, device=self.device), n_bytes=0, slots=None,
+                         analysis=self._upload_analysis(table) if isinstance(table, Analyzer) else None)
         self._extend_vocabulary(terms)
         return self
+
+    def _upload_analysis(self, analyzer: Analyzer) -> dict:
+        """The analyzer's stop set (the vocabulary's layout, built with thr_vocab_insert) and its rule table on the
+        device: thr_text_tokens_analyzed's extra operands."""
+        step_ptr, rules = analyzer.rule_table()
+        A = dict(stop_slots=None, stop_bytes=None, stop_ptr=None, step_ptr=step_ptr,
+                 rules=self._t(rules, torch.uint8) if len(rules) else None)
+        if analyzer.stop:
+            blob, ptr = pack_texts(analyzer.stop)
+            A["stop_bytes"], A["stop_ptr"] = self._t(blob, torch.uint8), self._t(ptr, torch.int64)
+            A["stop_slots"] = torch.zeros((vocab_capacity(len(analyzer.stop)), 2), dtype=torch.int64, device=self.device)
+            N.vocab_insert(A["stop_slots"], A["stop_bytes"], A["stop_ptr"], 0, len(analyzer.stop))
+        return A
 
     def grow_vocabulary(self, new_terms: Sequence[str]) -> "TextSearch":
         """Append terms: they get the next ids (thr_vocab_insert; above 1/2 load the table is reallocated and
@@ -402,8 +582,13 @@ class TextSearch:
         cap = N.text_token_capacity(len(texts), n_bytes)
         need = N.text_tokens_workspace_bytes(len(texts), n_bytes, cap)
         bytes_dev, ptr_dev = self._t(blob, torch.uint8), self._t(ptr, torch.int64)
-        rows = N.text_tokens(bytes_dev, ptr_dev, n_bytes, X["table_dev"], X["slots"],
-                             X["term_bytes"], X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)))
+        A = X.get("analysis")
+        if A is None:
+            rows = N.text_tokens(bytes_dev, ptr_dev, n_bytes, X["table_dev"], X["slots"],
+                                 X["term_bytes"], X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)))
+        else:       # an Analyzer: stop tokens dropped, stems looked up (the workspace is thr_text_tokens')
+            rows = N.text_tokens_analyzed(bytes_dev, ptr_dev, n_bytes, X["table_dev"], X["slots"], X["term_bytes"],
+                                          X["term_ptr"], workspace=self._scratch("_ws_text", max(need, 8)), **A)
         rows["blob"], rows["ptr"] = blob, ptr
         rows["bytes_dev"], rows["ptr_dev"] = bytes_dev, ptr_dev      # (thr_vocab_grow reads the batch again)
         return rows
