@@ -168,6 +168,15 @@ _SIGNATURES_TEXT = {
 }
 # thr_hip_text.h's #defines (THR_STEM_*): code points of a suffix, steps and rules of a table, bytes of a rule record
 STEM_MAX_SUFFIX, STEM_MAX_STEPS, STEM_MAX_RULES, STEM_RULE_BYTES = 8, 4, 1024, 24
+# include/thr_hip_rerank.h: the FP8 token store of the late-interaction rerank (additive as well)
+_SIGNATURES_RERANK = {
+    "thr_maxsim_quantize_fp8": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "thr_maxsim_fp8": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "thr_maxsim_fp8_ids": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp]),
+}
+# token dims thr_maxsim_fp8 has a kernel for (csrc/maxsim_fp8.hip THR_M8_KPAIRS, times 32): a lane's 16 bytes
+# of the packed image are two k-steps, so 16 -- which thr_maxsim takes -- is not among them
+MAXSIM_FP8_TOK_DIMS = (32, 64, 96, 128, 192, 256)
 
 
 def lib_path() -> str:
@@ -188,7 +197,8 @@ def load(build_if_missing: bool = True):
         lib = C.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise NativeError(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items())
+                              + list(_SIGNATURES_RERANK.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -1557,6 +1567,63 @@ def _maxsim_call(entry: str, qtok, dtok, cand, cand_dtype, cand_name: str, id_ba
     out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
     _check(getattr(load(), entry)(pq, nq, qt, pdt, nd, dt, td, pc, *id_base, cand.shape[1], out.data_ptr(),
                                   1 if packed else 0, _stream()), entry)
+    return out
+
+
+# ------------------------------------------------- a8, FP8 token store (thr_hip_rerank.h)
+def maxsim_fp8_check_tokens(what: str, tok_dim: int, *n_tokens: int) -> None:
+    """The shapes thr_maxsim_quantize_fp8 / thr_maxsim_fp8 / thr_maxsim_fp8_ids take, refused here with
+    the list in the message (the library answers the same shapes with THR_ERR_UNSUPPORTED)."""
+    if any(n <= 0 or n % 32 for n in n_tokens):
+        raise NativeError(f"{what}: q_tokens / d_tokens must be positive multiples of 32, got {n_tokens}")
+    if tok_dim not in MAXSIM_FP8_TOK_DIMS:
+        raise NativeError(f"{what}: tok_dim {tok_dim} is not supported: the FP8 MaxSim kernels take tok_dim in "
+                          f"{list(MAXSIM_FP8_TOK_DIMS)}")
+
+
+def maxsim_quantize_fp8(dtok: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Row-major float16 token store [n, d_tokens, tok_dim] -> (codes uint8 [n, d_tokens, tok_dim]: the
+    packed E4M3 image of thr_hip_rerank.h, d_tokens * tok_dim bytes per document -- the shape names the
+    store, not the place of a byte; scales float32 [n, d_tokens])."""
+    pdt = _dev(dtok, torch.float16, "dtok", 3)
+    nd, dt, td = dtok.shape
+    maxsim_fp8_check_tokens("maxsim_quantize_fp8", td, dt)
+    codes = torch.empty(dtok.shape, dtype=torch.uint8, device=dtok.device)
+    scales = torch.empty((nd, dt), dtype=torch.float32, device=dtok.device)
+    if nd:
+        _check(load().thr_maxsim_quantize_fp8(pdt, nd, dt, td, codes.data_ptr(), scales.data_ptr(), _stream()),
+               "thr_maxsim_quantize_fp8")
+    return codes, scales
+
+
+def maxsim_fp8(qtok: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """cand holds LOCAL doc indices; negative or out-of-range entries score -inf."""
+    return _maxsim_fp8_call("thr_maxsim_fp8", qtok, codes, scales, cand, torch.int32, "cand", ())
+
+
+def maxsim_fp8_ids(qtok: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, cand_ids: torch.Tensor,
+                   id_base: int) -> torch.Tensor:
+    """cand_ids holds GLOBAL doc ids (int64) of a shard starting at ``id_base``; negative ids and
+    ids outside the shard score -inf."""
+    return _maxsim_fp8_call("thr_maxsim_fp8_ids", qtok, codes, scales, cand_ids, torch.int64, "cand_ids",
+                            (int(id_base),))
+
+
+def _maxsim_fp8_call(entry: str, qtok, codes, scales, cand, cand_dtype, cand_name: str, id_base: tuple):
+    """``entry`` (thr_maxsim_fp8 / thr_maxsim_fp8_ids) over candidates of ``cand_dtype``; ``id_base``: the
+    argument thr_maxsim_fp8_ids takes behind the candidates, () for thr_maxsim_fp8."""
+    pq = _dev(qtok, torch.float16, "qtok", 3)
+    pcd = _dev(codes, torch.uint8, "codes", 3)
+    psc = _dev(scales, torch.float32, "scales", 2)
+    pc = _dev(cand, cand_dtype, cand_name, 2)
+    nq, qt, td = qtok.shape
+    nd, dt, td2 = codes.shape
+    if td != td2 or cand.shape[0] != nq or tuple(scales.shape) != (nd, dt):
+        raise NativeError("maxsim_fp8: shape mismatch")
+    maxsim_fp8_check_tokens(entry[4:], td, qt, dt)
+    out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
+    _check(getattr(load(), entry)(pq, nq, qt, pcd, psc, nd, dt, td, pc, *id_base, cand.shape[1], out.data_ptr(),
+                                  _stream()), entry)
     return out
 
 

@@ -17,7 +17,8 @@ Layout in HBM (per shard of n documents, D dims):
     graph     entity CSR (replicated) + entity->chunk mention CSR (this shard's chunks)
     entities  uint8 lower-cased entity names, 0xFF-separated + int64 [E+1] offsets (set_entity_names;
               index_entities.EntitySearch: find_entities, a batch's keywords -> its graph seeds)
-    tokens    float16 [n, T_d, 128] late-interaction token matrices
+    tokens    float16 [n, T_d, 128] late-interaction token matrices; with set_tokens(store="fp8") uint8
+              [n, T_d, 128] E4M3 codes (packed image) + token_scales float32 [n, T_d]
     attributes int32 [n] per name (set_attributes; "collection" = doc_coll): what a scope tests
                (index_scope.ScopedSearch: scope_plan, the row-list and the label routes)
 
@@ -70,6 +71,8 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
     _lex_global = False         # idf / avgdl are a sharded corpus' (set_lexical_rows with a group)
     _unusable: Optional[str] = None    # set when a delete failed while rows were moving in place
     df_local = df_global = None        # per-term document frequencies (set_lexical_rows, append_rows, delete_rows)
+    token_store = "f16"         # set_tokens(store=): "fp8" keeps ``tokens`` as the packed E4M3 image ...
+    token_scales = None         # ... and one float32 scale per document token here
 
     def __init__(self, device: Optional[torch.device] = None, doc_base: int = 0):
         if not torch.cuda.is_available():
@@ -251,7 +254,8 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
     def export_derived(self) -> dict:
         """What index set-up computed on the device and a saved index can carry along, as host
         arrays: the float16 image of the rows (+ its layout tag and measured error), the BM25
-        bounds / per-posting impacts and the dense-term rows (+ the parameters they hold for)."""
+        bounds / per-posting impacts and the dense-term rows (+ the parameters they hold for), the
+        FP8 token store (packed E4M3 image + scales: HostIndex.to_gpu(token_store="fp8") takes it as it is)."""
         out: dict = {}
         if self.docs16 is not None and self.shortlist == "f16":
             out.update(docs16=self.docs16.cpu().numpy(), doc_rel_err=float(self.doc_rel_err),
@@ -264,6 +268,8 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
             if L["dense"] is not None:
                 out.update(dense_slot=L["dense"][0].cpu().numpy(), dense_imp=L["dense"][1].cpu().numpy(),
                            dense_tf=L["dense"][2].cpu().numpy(), dense_stride=int(L["dense"][3]))
+        if self.token_store == "fp8" and self.tokens is not None:
+            out.update(tokens_fp8=self.tokens.cpu().numpy(), token_scales=self.token_scales.cpu().numpy())
         return out
 
     def set_collections(self, doc_coll) -> "GpuIndex":
@@ -294,17 +300,52 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
                                                          G["men_conf"], self.doc_base, self.n_docs)
         return G["transposed"]
 
-    def set_tokens(self, dtok, pack: bool = True) -> "GpuIndex":
+    TOKEN_STORES = ("f16", "fp8")
+
+    def set_tokens(self, dtok, pack: bool = True, store: str = "f16") -> "GpuIndex":
         """Late-interaction token store f16 [n, d_tokens, tok_dim].  pack=True keeps it in the
         fragment-major layout of thr_maxsim_pack (the row-major copy is dropped).  d_tokens is a
-        multiple of 32 and tok_dim one of _native.MAXSIM_TOK_DIMS."""
+        multiple of 32 and tok_dim one of _native.MAXSIM_TOK_DIMS.
+
+        store="fp8" (opt-in) keeps the tokens as OCP E4M3 codes with one float32 scale per token
+        (thr_hip_rerank.h: half the bytes per chunk; scores differ from the float16 store's by the
+        quantisation error): ``tokens`` is then the packed uint8 image, ``token_scales`` float32
+        [n, d_tokens], the float16 copy is dropped (the image is always packed: ``pack`` is not asked),
+        and tok_dim is one of _native.MAXSIM_FP8_TOK_DIMS."""
+        shape = self._check_token_store("set_tokens", store, dtok)
         tok = self._t(dtok, torch.float16)
-        if tok.dim() != 3:
-            raise N.NativeError("set_tokens: tokens must be [n, d_tokens, tok_dim]")
+        if store == "fp8":
+            self._install_tokens(*N.maxsim_quantize_fp8(tok), store="fp8")
+            return self
         # a store the scorer has no kernel for is refused here, packed or not, not at the first query
-        N.maxsim_check_tokens("set_tokens", int(tok.shape[2]), int(tok.shape[1]))
-        self.tokens_packed = bool(pack)
-        self.tokens = N.maxsim_pack(tok) if pack else tok
+        N.maxsim_check_tokens("set_tokens", shape[2], shape[1])
+        self._install_tokens(N.maxsim_pack(tok) if pack else tok, None, store="f16", packed=bool(pack))
+        return self
+
+    @classmethod
+    def _check_token_store(cls, what: str, store: str, dtok) -> tuple:
+        """What can be refused about a token store before any device work -> its shape."""
+        if store not in cls.TOKEN_STORES:
+            raise N.NativeError(f"{what}: store must be one of {list(cls.TOKEN_STORES)}, got {store!r}")
+        shape = tuple(int(s) for s in (dtok.shape if hasattr(dtok, "shape") else np.shape(dtok)))
+        if len(shape) != 3:
+            raise N.NativeError(f"{what}: tokens must be [n, d_tokens, tok_dim]")
+        if store == "fp8":
+            N.maxsim_fp8_check_tokens(f"{what}(store='fp8')", shape[2], shape[1])
+        return shape
+
+    def _install_tokens(self, tokens, scales, store: str, packed: bool = True) -> None:
+        self.tokens, self.token_scales = tokens, scales
+        self.token_store, self.tokens_packed = store, packed
+
+    def set_tokens_fp8(self, codes, scales) -> "GpuIndex":
+        """An FP8 token store that exists already (a saved index' image: index_build.load): codes uint8
+        [n, d_tokens, tok_dim] in the packed layout of thr_hip_rerank.h, scales float32 [n, d_tokens].
+        Nothing is requantised."""
+        shape = self._check_token_store("set_tokens_fp8", "fp8", codes)
+        if tuple(int(s) for s in scales.shape) != shape[:2]:
+            raise N.NativeError(f"set_tokens_fp8: scales must be [{shape[0]}, {shape[1]}], got {tuple(scales.shape)}")
+        self._install_tokens(self._t(codes, torch.uint8), self._t(scales, torch.float32), store="fp8")
         return self
 
     # ------------------------------------------------------------ channels
@@ -572,7 +613,11 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
     @_refuse_when_unusable
     def maxsim(self, qtok: torch.Tensor, cand_global_ids: torch.Tensor) -> torch.Tensor:
         """MaxSim of each query against its candidate docs (global ids; ids outside this
-        shard or negative score -inf)."""
+        shard or negative score -inf).  Over an FP8 store (set_tokens(store="fp8")) the scores are
+        MaxSim over the dequantised tokens."""
+        if self.token_store == "fp8":
+            return N.maxsim_fp8_ids(self._t(qtok, torch.float16), self.tokens, self.token_scales,
+                                    self._t(cand_global_ids, torch.int64), self.doc_base)
         return N.maxsim_ids(self._t(qtok, torch.float16), self.tokens, self._t(cand_global_ids, torch.int64),
                             self.doc_base, packed=self.tokens_packed)
 

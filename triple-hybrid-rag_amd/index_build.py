@@ -55,10 +55,29 @@ class HostIndex:
     derived: Optional[Dict[str, Any]] = None   # GpuIndex.export_derived(): saved with the index, reused by to_gpu()
     attributes: Optional[Dict[str, np.ndarray]] = None   # per-row int32 columns a scope tests (GpuIndex.set_attributes)
 
-    def to_gpu(self, doc_base: int = 0, shortlist: str = "auto"):
+    def fp8_image(self):
+        """(codes, scales) of a saved FP8 token store that belongs to these rows, or None."""
+        d = self.derived or {}
+        codes, scales = d.get("tokens_fp8"), d.get("token_scales")
+        if codes is None or scales is None or len(codes) != len(self.docs) or tuple(scales.shape) != tuple(codes.shape[:2]):
+            return None
+        return codes, scales
+
+    def to_gpu(self, doc_base: int = 0, shortlist: str = "auto", token_store: str = "f16"):
         """``shortlist``: GpuIndex.set_dense's -- "f16-anydim" puts a 1536-d or the 4000-d legacy store
-        on the f16 matrix cores, where "auto" scores every row in float64."""
+        on the f16 matrix cores, where "auto" scores every row in float64.
+        ``token_store``: GpuIndex.set_tokens' ``store``.  "fp8" takes the E4M3 image a save wrote
+        (``save(hi, path, gpu_index=)`` of an index with an FP8 store) as it is -- ``tokens`` may then be
+        None: a deployment need never hold the float16 tokens -- and quantises ``tokens`` on the device
+        when there is no image."""
         from .index import GpuIndex
+        if token_store not in GpuIndex.TOKEN_STORES:
+            raise ValueError(f"to_gpu: token_store must be one of {list(GpuIndex.TOKEN_STORES)}, got {token_store!r}")
+        image = self.fp8_image() if token_store == "fp8" else None
+        if token_store == "fp8":     # refused before a device is asked for
+            if image is None and self.tokens is None:
+                raise ValueError("to_gpu(token_store='fp8'): this index has neither token matrices nor a saved FP8 image")
+            GpuIndex._check_token_store("to_gpu", "fp8", image[0] if image is not None else self.tokens)
         idx = GpuIndex(doc_base=doc_base).set_dense(self.docs, shortlist=shortlist, derived=self.derived)
         if self.rowptr is not None:
             idx.set_lexical(self.rowptr, self.post_doc, self.post_tf, self.doclen, self.idf,
@@ -66,8 +85,10 @@ class HostIndex:
         if self.ent_rowptr is not None:
             idx.set_graph(self.ent_rowptr, self.ent_col, self.men_rowptr, self.men_chunk,
                           self.men_conf)
-        if self.tokens is not None:
-            idx.set_tokens(self.tokens)
+        if image is not None:
+            idx.set_tokens_fp8(*image)
+        elif self.tokens is not None:
+            idx.set_tokens(self.tokens, store=token_store)
         if self.attributes:
             idx.set_attributes(self.attributes)
         return idx
@@ -302,7 +323,8 @@ def from_rows(child_rows: Sequence[Dict[str, Any]], parent_rows: Sequence[Dict[s
 
 _ARRAYS = ("docs", "rowptr", "post_doc", "post_tf", "doclen", "idf", "ent_rowptr", "ent_col",
            "men_rowptr", "men_chunk", "men_conf", "tokens")
-_DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf")
+_DERIVED_ARRAYS = ("docs16", "term_ub", "block_ub", "post_imp", "dense_slot", "dense_imp", "dense_tf",
+                   "tokens_fp8", "token_scales")    # (the last two: GpuIndex.set_tokens(store="fp8")'s image)
 _DERIVED_SCALARS = ("doc_rel_err", "f16_layout", "lexical_tag", "dense_stride")
 _STRING_COLUMNS = ("child_ids", "parent_ids", "document_ids", "texts", "modalities", "collections",
                    "entity_names", "content_hashes", "org_ids", "entity_ids", "entity_canonical", "entity_documents")

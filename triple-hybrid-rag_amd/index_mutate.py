@@ -43,7 +43,7 @@ class _Storage:
     into a larger buffer, of which the index then holds the leading part; ``held`` records that
     buffer together with the view it was recorded for.  A builder that replaces the array (set_dense
     again, ...) leaves a record about a tensor the index no longer holds: it counts for nothing."""
-    ROWS = ("docs", "docs16", "dnorm", "inv_norm", "doc_coll", "tokens")    # GpuIndex attributes
+    ROWS = ("docs", "docs16", "dnorm", "inv_norm", "doc_coll", "tokens", "token_scales")    # GpuIndex attributes
     GROWTH = 1.5    # a buffer that is too small is replaced by one of GROWTH x its size (at least the need)
 
     def __init__(self):
@@ -323,7 +323,8 @@ class MutableIndex:
         if tk.ndim != 3 or tk.shape[0] != m or tuple(tk.shape[1:]) != tuple(self.tokens.shape[1:]):
             raise N.NativeError(f"append_rows: tokens must be [{m}, {self.tokens.shape[1]}, {self.tokens.shape[2]}]")
         # (set_tokens applies the same check: this one holds for a store that came another way)
-        N.maxsim_check_tokens("append_rows: tokens", int(tk.shape[2]), int(tk.shape[1]))
+        check = N.maxsim_fp8_check_tokens if self.token_store == "fp8" else N.maxsim_check_tokens
+        check("append_rows: tokens", int(tk.shape[2]), int(tk.shape[1]))
         return tk
 
     def _check_dense_part(self, docs, n_rows):
@@ -474,8 +475,12 @@ class MutableIndex:
             self._extend(new, "attr:" + name, self._attrs[name], self._t(col, torch.int32), n_old)
         if P["tokens"] is not None:
             tok = self._t(P["tokens"], torch.float16)
-            self._extend(new, "tokens", self.tokens, N.maxsim_pack(tok) if self.tokens_packed else tok,
-                         n_old)     # (the packed layout is doc-local)
+            if self.token_store == "fp8":   # (quantised per token: the batch's image is a fresh build's rows)
+                tok, scales = N.maxsim_quantize_fp8(tok)
+                self._extend(new, "token_scales", self.token_scales, scales, n_old)
+            elif self.tokens_packed:
+                tok = N.maxsim_pack(tok)
+            self._extend(new, "tokens", self.tokens, tok, n_old)     # (the packed layouts are doc-local)
         if P["lex"] is not None:
             self._append_lexical(P["lex"], n_old, new)
         if P["mentions"] is not None:
