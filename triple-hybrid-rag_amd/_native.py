@@ -177,6 +177,15 @@ _SIGNATURES_RERANK = {
 # token dims thr_maxsim_fp8 has a kernel for (csrc/maxsim_fp8.hip THR_M8_KPAIRS, times 32): a lane's 16 bytes
 # of the packed image are two k-steps, so 16 -- which thr_maxsim takes -- is not among them
 MAXSIM_FP8_TOK_DIMS = (32, 64, 96, 128, 192, 256)
+# include/thr_hip_parent.h: child -> parent expansion (the groups of a fused row, MaxSim over a parent's children;
+# additive as well).  The scorers take MAXSIM_TOK_DIMS (float16, packed image) / MAXSIM_FP8_TOK_DIMS.
+_SIGNATURES_PARENT = {
+    "thr_parent_groups": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "thr_maxsim_parent_ids": (_i32, [_vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64,
+                                     _vp, _vp]),
+    "thr_maxsim_parent_fp8_ids": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32,
+                                         _i64, _vp, _vp]),
+}
 
 
 def lib_path() -> str:
@@ -198,7 +207,7 @@ def load(build_if_missing: bool = True):
     except OSError as e:  # pragma: no cover
         raise NativeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items())
-                              + list(_SIGNATURES_RERANK.items())):
+                              + list(_SIGNATURES_RERANK.items()) + list(_SIGNATURES_PARENT.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -1624,6 +1633,67 @@ def _maxsim_fp8_call(entry: str, qtok, codes, scales, cand, cand_dtype, cand_nam
     out = torch.empty(cand.shape, dtype=torch.float32, device=qtok.device)
     _check(getattr(load(), entry)(pq, nq, qt, pcd, psc, nd, dt, td, pc, *id_base, cand.shape[1], out.data_ptr(),
                                   _stream()), entry)
+    return out
+
+
+# ------------------------------------------------- child -> parent expansion (thr_hip_parent.h)
+def parent_groups(ids: torch.Tensor, counts: Optional[torch.Tensor], parent_of: torch.Tensor, id_base: int = 0):
+    """The groups of each fused row ids[q][0 .. counts[q]) under the column ``parent_of`` (int32 [n_docs], -1 = no
+    parent) -> (leader i32 [nq, n], slot i32 [nq, n], uniq_ids i64 [nq, n], n_uniq i32 [nq]): thr_hip_parent.h."""
+    pi = _dev(ids, torch.int64, "ids", 2)
+    pc = _dev(counts, torch.int32, "counts", 1) if counts is not None else None
+    pp = _dev(parent_of, torch.int32, "parent_of", 1)
+    nq, n = ids.shape
+    if counts is not None and counts.shape[0] != nq:
+        raise NativeError("parent_groups: one count per query")
+    rrf_check_top_k("parent_groups", n)
+    leader = torch.empty((nq, n), dtype=torch.int32, device=ids.device)
+    slot = torch.empty((nq, n), dtype=torch.int32, device=ids.device)
+    uniq = torch.empty((nq, n), dtype=torch.int64, device=ids.device)
+    n_uniq = torch.empty(nq, dtype=torch.int32, device=ids.device)
+    if nq:
+        _check(load().thr_parent_groups(pi, pc, nq, n, pp, parent_of.shape[0], int(id_base), leader.data_ptr(),
+                                        slot.data_ptr(), uniq.data_ptr(), n_uniq.data_ptr(), _stream()),
+               "thr_parent_groups")
+    return leader, slot, uniq, n_uniq
+
+
+def maxsim_parent_ids(qtok: torch.Tensor, dtok: torch.Tensor, cand_ids: torch.Tensor, id_base: int,
+                      parent_of: torch.Tensor, par_rowptr: torch.Tensor, par_child: torch.Tensor) -> torch.Tensor:
+    """MaxSim of each query against the PARENT of each candidate -- the token blocks of every row of the candidate's
+    family -- over the float16 store in its PACKED image (maxsim_pack); candidates as maxsim_ids."""
+    return _maxsim_parent_call("thr_maxsim_parent_ids", maxsim_check_tokens, qtok, (dtok, torch.float16, "dtok", 3), None,
+                               cand_ids, id_base, parent_of, par_rowptr, par_child)
+
+
+def maxsim_parent_fp8_ids(qtok: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, cand_ids: torch.Tensor,
+                          id_base: int, parent_of: torch.Tensor, par_rowptr: torch.Tensor,
+                          par_child: torch.Tensor) -> torch.Tensor:
+    """maxsim_parent_ids over the FP8 store (maxsim_quantize_fp8's image and scales)."""
+    return _maxsim_parent_call("thr_maxsim_parent_fp8_ids", maxsim_fp8_check_tokens, qtok, (codes, torch.uint8, "codes", 3),
+                               scales, cand_ids, id_base, parent_of, par_rowptr, par_child)
+
+
+def _maxsim_parent_call(entry: str, check_tokens, qtok, store, scales, cand_ids, id_base, parent_of, par_rowptr, par_child):
+    pq = _dev(qtok, torch.float16, "qtok", 3)
+    pst = _dev(*store)
+    pc = _dev(cand_ids, torch.int64, "cand_ids", 2)
+    pp = _dev(parent_of, torch.int32, "parent_of", 1)
+    pr = _dev(par_rowptr, torch.int64, "par_rowptr", 1)
+    pch = _dev(par_child, torch.int32, "par_child", 1)
+    nq, qt, td = qtok.shape
+    nd, dt, td2 = store[0].shape
+    if td != td2 or cand_ids.shape[0] != nq or parent_of.shape[0] != nd or par_rowptr.shape[0] < 2:
+        raise NativeError(f"{entry[4:]}: shape mismatch")
+    sc = ()
+    if scales is not None:
+        if tuple(scales.shape) != (nd, dt):
+            raise NativeError(f"{entry[4:]}: shape mismatch")
+        sc = (_dev(scales, torch.float32, "scales", 2),)
+    check_tokens(entry[4:], td, qt, dt)
+    out = torch.empty(cand_ids.shape, dtype=torch.float32, device=qtok.device)
+    _check(getattr(load(), entry)(pq, nq, qt, pst, *sc, nd, dt, td, pc, int(id_base), cand_ids.shape[1], pp, pr, pch,
+                                  par_rowptr.shape[0] - 1, par_child.shape[0], out.data_ptr(), _stream()), entry)
     return out
 
 

@@ -65,6 +65,7 @@ class GpuIndexClient(ClientIngest):
     multi_tenant = False     # set by __init__: no org_id of its own over a store with an org_ids column
     graph_cascade = False    # set by __init__: a document delete also removes the entities first extracted from it
     tokenizer = staticmethod(tokenize)   # set by __init__: what turns a query's and a chunk's text into tokens
+    parent_rerank = False    # set by __init__: maxsim_scores scores a chunk's parent passage (index "parent" column)
 
     # Derived state, made by __init__ (the class values serve a subclass with an __init__ of its own):
     #   attribute     derived from                                   filled by           dropped by (backend_ingest)
@@ -81,7 +82,8 @@ class GpuIndexClient(ClientIngest):
                  token_embedder: Any = None, lexical_and: bool = False,
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
                  collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
-                 tokenizer: Any = None, number_on_device: bool = False, graph_cascade: bool = False):
+                 tokenizer: Any = None, number_on_device: bool = False, graph_cascade: bool = False,
+                 parent_rerank: bool = False):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's ``plainto_tsquery`` does
         (rag2_schema.sql:365); default is BM25's OR form, the north star's and the oracle's.
         image_index / image_rows: the legacy image channel (``kb_chunks_image_search``,
@@ -108,7 +110,13 @@ class GpuIndexClient(ClientIngest):
         graph_cascade: ``table("rag_documents").delete()`` also removes the entities whose ``document_id`` is a deleted
         document, with their relations and mentions, as the schema's ON DELETE CASCADE does (rag2_schema.sql:187,
         217-220, 254, 258-259).  Needs the store's ``entity_documents`` column; default False: entities outlive their
-        document, the behaviour before the flag."""
+        document, the behaviour before the flag.
+        parent_rerank: ``maxsim_scores`` -- what ``Reranker._rerank_batch_native`` and ``RAG2Retriever._rerank`` rank on
+        -- scores a chunk's PARENT passage (the token blocks of every chunk of the same parent), as the reference
+        reranks ``c.parent_text or c.text`` (retrieval.py:419).  ``store.parent_ids`` are numbered by first appearance
+        (None -> -1) into the index's "parent" column (GpuIndex.set_parents; one the index already has is checked
+        against the store's column), ``insert_children`` passes the column with each append.  Needs a token store in
+        the packed float16 or the FP8 layout.  Default False: the chunk's own tokens, the behaviour before the flag."""
         if graph_cascade and getattr(store, "entity_documents", None) is None:
             raise ValueError("graph_cascade=True needs the store's entity_documents column (rag_entities.document_id): "
                              "no entity row of this store carries a document_id")
@@ -162,10 +170,37 @@ class GpuIndexClient(ClientIngest):
                 if ix is not None and "org" not in ix.attribute_names():
                     orgs = store.org_ids if rows is None else [store.org_ids[r] for r in rows]
                     ix.set_attributes({"org": np.array([self._org_code.get(o, -1) for o in orgs], dtype=np.int32)})
+        self.parent_rerank = bool(parent_rerank)
+        self._parent_code: Dict[Any, int] = {}
+        if self.parent_rerank:
+            self._number_parents()
         if device_text:
             self._text_table()          # (refuses a custom tokenizer before anything is uploaded)
             self.device_text = True
             self._sync_vocabulary()
+
+    # -------------------------------------------------------------- parents
+    def _number_parents(self) -> None:
+        """``_parent_code``: parent id -> parent number, kept the way ``_org_code`` is.  A column that came with the
+        index (a saved one: numbers given at inserts never move) is read off the rows, once; else the store's
+        parent_ids are numbered by first appearance and the column is set."""
+        index, pids = self.index, list(self.store.parent_ids)
+        if "parent" in index.attribute_names():
+            for p, c in zip(pids, index.attribute("parent").cpu().tolist()):
+                if c != (-1 if p is None else self._parent_code.setdefault(p, c)):
+                    raise ValueError("the index's \"parent\" attribute does not follow the store's parent_ids column")
+            if len(set(self._parent_code.values())) != len(self._parent_code) or \
+                    min(self._parent_code.values(), default=0) < 0:
+                raise ValueError("the index's \"parent\" attribute gives two parents of the store the same number, or one none")
+        else:
+            for p in pids:
+                if p is not None:
+                    self._parent_code.setdefault(p, len(self._parent_code))
+            index.set_parents(self._parent_column(pids, self._parent_code))
+
+    @staticmethod
+    def _parent_column(parent_ids, code: Dict[Any, int]) -> np.ndarray:
+        return np.array([-1 if p is None else code[p] for p in parent_ids], dtype=np.int32)
 
     # -------------------------------------------------------------- text on the device
     def _text_table(self) -> TextTable:
@@ -523,14 +558,16 @@ class GpuIndexClient(ClientIngest):
     # -------------------------------------------------------------- rerank
     def maxsim_scores(self, query: str, child_ids: List[str]) -> List[float]:
         """MaxSim of the query's token matrix against the given chunks, divided by the number of
-        query tokens so unit-norm tokens give a [-1, 1] relevance like a cross-encoder's."""
+        query tokens so unit-norm tokens give a [-1, 1] relevance like a cross-encoder's.  Under
+        ``parent_rerank`` the chunk's parent passage is scored: the chunks of one parent get one score."""
         if self.token_embedder is None or self.index.tokens is None:
             raise RuntimeError("no token embedder / token store: late-interaction rerank unavailable")
         qtok = np.asarray(self.token_embedder.embed_query_tokens(query), dtype=np.float16)[None]
         ids = [self.store.row_index(c) for c in child_ids]
         cand = torch.tensor([[self.store.doc_base + i if i is not None else -1 for i in ids]],
                             dtype=torch.int64, device=self.index.device)
-        sc = self.index.maxsim(torch.from_numpy(qtok).to(self.index.device), cand)[0]
+        sc = self.index.maxsim(torch.from_numpy(qtok).to(self.index.device), cand,
+                               **({"expand": "parent"} if self.parent_rerank else {}))[0]
         return [float(v) / qtok.shape[1] if np.isfinite(v) else 0.5 for v in sc.tolist()]
 
     def text_to_child_id(self, text: str) -> Optional[str]:

@@ -115,6 +115,12 @@ class ClientIngest:
             for r in rows:   # an org no earlier row carries gets the next id (ids never move)
                 org_code.setdefault(r["org_id"], max(org_code.values(), default=-1) + 1)
             parts["attributes"] = {"org": np.array([org_code[r["org_id"]] for r in rows], dtype=np.int32)}
+        if self.parent_rerank:
+            parent_code = dict(self._parent_code)
+            for r in rows:   # a parent no earlier row names gets the next number (numbers never move)
+                if r.get("parent_id") is not None:
+                    parent_code.setdefault(r["parent_id"], max(parent_code.values(), default=-1) + 1)
+            parts.setdefault("attributes", {})["parent"] = self._parent_column([r.get("parent_id") for r in rows], parent_code)
         if idx.tokens is not None:
             if any(r.get("tokens") is None for r in rows):
                 raise ValueError("the index has a late-interaction token store: every inserted row needs its "
@@ -138,6 +144,8 @@ class ClientIngest:
             st.vocab.update((tok, numbered.n_before + i) for i, tok in enumerate(numbered.pending.terms))
         if self.multi_tenant:
             self._org_code = org_code
+        if self.parent_rerank:
+            self._parent_code = parent_code
         self._rows_changed()
         return [{"id": r["id"]} for r in rows]
 

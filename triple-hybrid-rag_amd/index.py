@@ -20,7 +20,8 @@ Layout in HBM (per shard of n documents, D dims):
     tokens    float16 [n, T_d, 128] late-interaction token matrices; with set_tokens(store="fp8") uint8
               [n, T_d, 128] E4M3 codes (packed image) + token_scales float32 [n, T_d]
     attributes int32 [n] per name (set_attributes; "collection" = doc_coll): what a scope tests
-               (index_scope.ScopedSearch: scope_plan, the row-list and the label routes)
+               (index_scope.ScopedSearch: scope_plan, the row-list and the label routes); "parent" = the parent
+               number of a chunk (set_parents; index_parent.ParentSearch: maxsim(expand="parent"), its derived CSR)
 
 Changing a live index (reserve_rows, append_rows, delete_rows) and the record of which buffer holds
 which of these arrays is the base class, ``index_mutate.MutableIndex``.
@@ -41,6 +42,7 @@ from .index_mutate import MutableIndex, _refuse_when_unusable, _Storage
 from .index_entities import EntitySearch
 from .index_text import TextSearch
 from .index_scope import ScopedSearch, ScopePlan
+from .index_parent import PARENT_MODES, ParentSearch
 
 log = logging.getLogger(__name__)
 
@@ -62,9 +64,12 @@ class BatchResult:
     # queries that needed the exhaustive float64 path: an int, or (batch path, so that a batch
     # needs no host synchronisation) a device int32[1] -- int(result.rescued) reads it back
     rescued: object = 0
+    # retrieve_batch(parents=): int32 [nq, top_k], the parent number of each returned id; -1 for padding and for a
+    # row without a parent.  None when the parent modes were not asked for.
+    parents: Optional[torch.Tensor] = None
 
 
-class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
+class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableIndex):
     # what an index has before anything sets it (also: one made without __init__, as the host tests do)
     _side = None                # the second HIP stream of side_channels, made on first use
     _shortlist_of = None        # what the candidate lists in the dense workspace belong to (dense_shortlist)
@@ -611,10 +616,16 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
         return S, I, cnt
 
     @_refuse_when_unusable
-    def maxsim(self, qtok: torch.Tensor, cand_global_ids: torch.Tensor) -> torch.Tensor:
+    def maxsim(self, qtok: torch.Tensor, cand_global_ids: torch.Tensor, expand: Optional[str] = None) -> torch.Tensor:
         """MaxSim of each query against its candidate docs (global ids; ids outside this
         shard or negative score -inf).  Over an FP8 store (set_tokens(store="fp8")) the scores are
-        MaxSim over the dequantised tokens."""
+        MaxSim over the dequantised tokens.
+        expand="parent" (set_parents; the packed float16 or the FP8 store): the score of a candidate is MaxSim
+        against its PARENT -- the token blocks of every row with the candidate's parent number, the row alone when it
+        has none -- as the reference reranks ``c.parent_text or c.text`` (retrieval.py:419).  The candidates of one
+        parent are scored once and share the bits (index_parent.ParentSearch)."""
+        if self._check_expand("maxsim", expand):
+            return self._maxsim_parent(qtok, cand_global_ids)
         if self.token_store == "fp8":
             return N.maxsim_fp8_ids(self._t(qtok, torch.float16), self.tokens, self.token_scales,
                                     self._t(cand_global_ids, torch.int64), self.doc_base)
@@ -676,7 +687,7 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
                        qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100,
                        rescue: bool = True, scopes=None, scope_rows_max: Optional[int] = None,
-                       scope_graph: bool = False) -> BatchResult:
+                       scope_graph: bool = False, parents: Optional[str] = None) -> BatchResult:
         """plan.semantic/lexical/graph_top_k = 100/50/50 and weights 0.7/0.8/1.0 are the
         reference's QueryPlan defaults (src/voice_agent/rag2/query_planner.py:23-50).
         scopes: as dense_search, resolved once for the batch; the dense and the lexical channel
@@ -687,7 +698,22 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
         and relation query carries .eq("org_id", org_id), graph_search.py:154-230 -- and by nothing
         else (no p_collection there, retrieval.py:316-356).  False (the default) keeps the graph
         channel unfiltered under ``scopes=``: right only where an org's entities mention that org's
-        chunks alone."""
+        chunks alone.
+        parents: child -> parent expansion between the fusion and the rerank (the reference's funnel step 4; needs
+        set_parents).  None: no expansion.  "rerank": every fused candidate stays, its rerank score is MaxSim against
+        its PARENT (maxsim(expand="parent")); siblings tie and keep their fused order.  Needs ``qtok`` and a token
+        store.  "collapse": max(rerank_top_k, top_k) candidates are fused, of each parent only the best-fused child
+        stays (with its RRF score), then the parent-score rerank when ``qtok`` is given, then top_k: no two returned
+        ids share a parent.  Either way ``BatchResult.parents`` holds the parent number of each returned id."""
+        if parents not in PARENT_MODES:
+            raise ValueError(f"retrieve_batch: parents must be one of {list(PARENT_MODES)}, got {parents!r}")
+        if parents is not None:
+            self._parent_column(f"retrieve_batch(parents={parents!r})")
+            if parents == "rerank" and (qtok is None or self.tokens is None):
+                raise ValueError("retrieve_batch(parents='rerank') reranks on the parent score: it needs qtok and a "
+                                 "token store (set_tokens)")
+            if qtok is not None and self.tokens is not None:
+                self._check_expand("retrieve_batch", "parent")
         if scopes is not None:
             scopes = self.scope_plan(scopes, queries.shape[0])
         w = {"lexical": 0.7, "semantic": 0.8, "graph": 1.0}
@@ -707,11 +733,22 @@ class GpuIndex(ScopedSearch, EntitySearch, TextSearch, MutableIndex):
             ch["graph"] = gra
             Ig = gra[1]
         rerank = qtok is not None and self.tokens is not None
-        n_fused = max(rerank_top_k, top_k) if rerank else top_k
+        n_fused = max(rerank_top_k, top_k) if rerank or parents == "collapse" else top_k
         ids, sc, _, cnt = N.rrf_fuse(Il, Is, Ig, n_fused, w["lexical"], w["semantic"], w["graph"])
+        if parents == "collapse":
+            # the leaders only: the best-fused child stands for its parent, with its RRF score
+            leader, _, ids, cnt = self.parent_groups(ids, cnt)
+            at = torch.sort((leader == torch.arange(n_fused, device=leader.device, dtype=leader.dtype)).to(torch.int8),
+                            dim=1, descending=True, stable=True).indices      # the leaders' positions, in order
+            live = torch.arange(n_fused, device=cnt.device)[None, :] < cnt[:, None]
+            sc = torch.where(live, torch.gather(sc, 1, at), torch.full_like(sc, float("-inf")))
+            if not rerank:
+                ids, sc = ids[:, :top_k].contiguous(), sc[:, :top_k].contiguous()
+                cnt = torch.clamp(cnt, max=top_k)
         if rerank:
             # MaxSim of the fused top rerank_top_k, then the reference's stable descending sort
             # on ``rerank_score or 0`` (retrieval.py:449-455), on the device
-            ids, sc, cnt = N.rerank_order(self.maxsim(qtok, ids), ids, cnt, top_k)
-        return BatchResult(ids, sc, cnt, ch, nres)
+            expand = None if parents is None else "parent"
+            ids, sc, cnt = N.rerank_order(self.maxsim(qtok, ids, expand=expand), ids, cnt, top_k)
+        return BatchResult(ids, sc, cnt, ch, nres, None if parents is None else self.parents_of(ids))
 
