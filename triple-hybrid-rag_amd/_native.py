@@ -186,6 +186,11 @@ _SIGNATURES_PARENT = {
     "thr_maxsim_parent_fp8_ids": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32,
                                          _i64, _vp, _vp]),
 }
+# include/thr_hip_diversify.h: diversified top-k (MMR over the candidates' dense rows; additive as well)
+_SIGNATURES_DIVERSIFY = {
+    "thr_mmr_select": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i64, _dbl, _i32, _vp, _vp, _vp, _vp, _vp,
+                              _vp]),
+}
 
 
 def lib_path() -> str:
@@ -207,7 +212,8 @@ def load(build_if_missing: bool = True):
     except OSError as e:  # pragma: no cover
         raise NativeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items())
-                              + list(_SIGNATURES_RERANK.items()) + list(_SIGNATURES_PARENT.items())):
+                              + list(_SIGNATURES_RERANK.items()) + list(_SIGNATURES_PARENT.items())
+                              + list(_SIGNATURES_DIVERSIFY.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -1695,6 +1701,63 @@ def _maxsim_parent_call(entry: str, check_tokens, qtok, store, scales, cand_ids,
     _check(getattr(load(), entry)(pq, nq, qt, pst, *sc, nd, dt, td, pc, int(id_base), cand_ids.shape[1], pp, pr, pch,
                                   par_rowptr.shape[0] - 1, par_child.shape[0], out.data_ptr(), _stream()), entry)
     return out
+
+
+# ------------------------------------------------- diversified top-k (thr_hip_diversify.h)
+def mmr_check_dim(what: str, dim: int) -> None:
+    """The row length thr_mmr_select takes, refused here with the limits in the message."""
+    if not (4 <= int(dim) <= THR_DENSE_ANYDIM_MAX and int(dim) % 4 == 0):
+        raise NativeError(f"{what}: dim must be a multiple of 4 in 4 .. {THR_DENSE_ANYDIM_MAX}, got {dim}")
+
+
+def mmr_check_lam(what: str, lam) -> float:
+    """MMR's lambda as thr_mmr_select takes it: a float in [0, 1] (-0.0 and 1.0 are inside, NaN is not)."""
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:       # (NaN fails both)
+        raise NativeError(f"{what}: lam must be in [0, 1], got {lam}")
+    return lam
+
+
+def mmr_select(ids: torch.Tensor, scores: torch.Tensor, counts: Optional[torch.Tensor], docs: torch.Tensor,
+               dnorm: torch.Tensor, id_base: int, top_k: int, lam: float, want_mmr: bool = True):
+    """Maximal Marginal Relevance over each list ids[q][0 .. counts[q]) / scores (float64, best first), the
+    similarities from the float32 rows ``docs`` and their float64 norms ``dnorm`` (thr_hip_diversify.h) ->
+    (ids i64 [nq, top_k], scores f64 [nq, top_k] -- the original ones, in selection order --, counts i32 [nq],
+    pos i32 [nq, top_k], mmr f64 [nq, top_k] or None)."""
+    pi = _dev(ids, torch.int64, "ids", 2)
+    ps = _dev(scores, torch.float64, "scores", 2)
+    pc = _dev(counts, torch.int32, "counts", 1) if counts is not None else None
+    pd = _dev(docs, torch.float32, "docs", 2)
+    pn = _dev(dnorm, torch.float64, "dnorm", 1)
+    nq, n = ids.shape
+    nd, dim = docs.shape
+    if tuple(scores.shape) != (nq, n) or (counts is not None and counts.shape[0] != nq):
+        raise NativeError("mmr_select: one score per id and one count per query")
+    if dnorm.shape[0] != nd:
+        raise NativeError("mmr_select: dnorm length != n_docs")
+    if nd < 1:
+        raise NativeError("mmr_select: no rows")
+    if pd % 16:
+        raise NativeError("mmr_select: docs must be 16-byte aligned")
+    if any(t.device != ids.device for t in (scores, docs, dnorm) + (() if counts is None else (counts,))):
+        raise NativeError("mmr_select: every operand lives on one device")
+    mmr_check_dim("mmr_select", dim)
+    rrf_check_top_k("mmr_select (the width of the list)", n)
+    if not 1 <= int(top_k) <= n:
+        raise NativeError(f"mmr_select: top_k must be in 1 .. {n} (the width of the list), got {top_k}")
+    lam = mmr_check_lam("mmr_select", lam)
+    dev = ids.device
+    out_ids = torch.empty((nq, top_k), dtype=torch.int64, device=dev)
+    out_sc = torch.empty((nq, top_k), dtype=torch.float64, device=dev)
+    out_pos = torch.empty((nq, top_k), dtype=torch.int32, device=dev)
+    out_mmr = torch.empty((nq, top_k), dtype=torch.float64, device=dev) if want_mmr else None
+    cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+    if nq:
+        _check(load().thr_mmr_select(pi, ps, pc, nq, n, pd, pn, nd, dim, int(id_base), lam, int(top_k),
+                                     out_ids.data_ptr(), out_sc.data_ptr(), out_pos.data_ptr(),
+                                     out_mmr.data_ptr() if want_mmr else None, cnt.data_ptr(), _stream()),
+               "thr_mmr_select")
+    return out_ids, out_sc, cnt, out_pos, out_mmr
 
 
 def rerank_order(scores: torch.Tensor, ids: torch.Tensor, counts: Optional[torch.Tensor], top_k: int):

@@ -51,6 +51,7 @@ from . import _native as N
 from .backend_ingest import ClientIngest
 from .backend_tables import TABLES, LazyRows, _Reply, _TableQuery
 from .index import GpuIndex
+from .index_diversify import check_lam
 from .index_entities import match_names, name_trigrams
 from .index_scope import In
 from .index_text import _TOKEN, TextTable, host_query_row, tokenize, tokenizer_table  # noqa: F401
@@ -66,6 +67,7 @@ class GpuIndexClient(ClientIngest):
     graph_cascade = False    # set by __init__: a document delete also removes the entities first extracted from it
     tokenizer = staticmethod(tokenize)   # set by __init__: what turns a query's and a chunk's text into tokens
     parent_rerank = False    # set by __init__: maxsim_scores scores a chunk's parent passage (index "parent" column)
+    diversify = None         # set by __init__: MMR's lambda of the final cut (mmr_order), None = the plain truncation
 
     # Derived state, made by __init__ (the class values serve a subclass with an __init__ of its own):
     #   attribute     derived from                                   filled by           dropped by (backend_ingest)
@@ -83,7 +85,7 @@ class GpuIndexClient(ClientIngest):
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
                  collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
                  tokenizer: Any = None, number_on_device: bool = False, graph_cascade: bool = False,
-                 parent_rerank: bool = False):
+                 parent_rerank: bool = False, diversify: Optional[float] = None):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's ``plainto_tsquery`` does
         (rag2_schema.sql:365); default is BM25's OR form, the north star's and the oracle's.
         image_index / image_rows: the legacy image channel (``kb_chunks_image_search``,
@@ -116,7 +118,18 @@ class GpuIndexClient(ClientIngest):
         reranks ``c.parent_text or c.text`` (retrieval.py:419).  ``store.parent_ids`` are numbered by first appearance
         (None -> -1) into the index's "parent" column (GpuIndex.set_parents; one the index already has is checked
         against the store's column), ``insert_children`` passes the column with each append.  Needs a token store in
-        the packed float16 or the FP8 layout.  Default False: the chunk's own tokens, the behaviour before the flag."""
+        the packed float16 or the FP8 layout.  Default False: the chunk's own tokens, the behaviour before the flag.
+        diversify: MMR's lambda in [0, 1], or None.  With a value the final cut of ``RAG2Retriever._apply_safety``
+        -- ``kept[:top_k]`` in the reference -- becomes ``mmr_order``: the top_k chosen greedily for relevance
+        (``_effective_score``, min-max normalised) and dissimilarity to what is already chosen, the similarities taken
+        from the index's dense rows on the device (GpuIndex.diversify).  Needs an index with dense rows.  Default
+        None: the truncation, the behaviour before the argument."""
+        if diversify is not None:
+            diversify = check_lam("GpuIndexClient", diversify)
+            if getattr(index, "docs", None) is None:
+                raise ValueError("GpuIndexClient(diversify=): the index has no dense rows (MMR takes its similarities "
+                                 "from them)")
+        self.diversify = diversify
         if graph_cascade and getattr(store, "entity_documents", None) is None:
             raise ValueError("graph_cascade=True needs the store's entity_documents column (rag_entities.document_id): "
                              "no entity row of this store carries a document_id")
@@ -569,6 +582,25 @@ class GpuIndexClient(ClientIngest):
         sc = self.index.maxsim(torch.from_numpy(qtok).to(self.index.device), cand,
                                **({"expand": "parent"} if self.parent_rerank else {}))[0]
         return [float(v) / qtok.shape[1] if np.isfinite(v) else 0.5 for v in sc.tolist()]
+
+    def mmr_order(self, child_ids: List[str], scores: List[float], top_k: int) -> List[int]:
+        """The diversified cut of a ranked list: positions into ``child_ids`` / ``scores`` (relevance, best first), at
+        most ``top_k`` of them, in the order MMR selects them under this client's ``diversify`` value.  An unknown
+        child id goes in as -1: it stays selectable and is similar to nothing.  A score that is not finite is never
+        selected."""
+        if self.diversify is None:
+            raise RuntimeError("this client was made without diversify=: no MMR order")
+        n = len(child_ids)
+        if n == 0 or top_k < 1:
+            return []
+        if len(scores) != n:
+            raise ValueError("mmr_order: one score per child id")
+        rows = [self.store.row_index(c) for c in child_ids]
+        dev = self.index.device
+        ids = torch.tensor([[self.store.doc_base + i if i is not None else -1 for i in rows]], dtype=torch.int64, device=dev)
+        sc = torch.tensor([[float(s) for s in scores]], dtype=torch.float64, device=dev)
+        _, _, cnt, pos, _ = self.index.diversify(ids, sc, None, top_k=min(int(top_k), n), lam=self.diversify)
+        return pos[0, :int(cnt[0])].tolist()
 
     def text_to_child_id(self, text: str) -> Optional[str]:
         if self._by_text is None:

@@ -20,6 +20,7 @@ import torch.distributed as dist
 from . import _native as N
 from .index import BatchResult, GpuIndex
 from .index_parent import refuse_on_shards
+from .index_diversify import refuse_diversify_on_shards
 
 
 def shard_range(n_docs: int, rank: int, world: int) -> Tuple[int, int]:
@@ -207,15 +208,18 @@ class ShardedIndex:
                        semantic_top_k: int = 100, lexical_top_k: int = 50, graph_top_k: int = 50,
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
                        qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100, scopes=None,
-                       parents: Optional[str] = None) -> BatchResult:
+                       parents: Optional[str] = None, diversify: Optional[float] = None) -> BatchResult:
         """Per channel: this shard's exact top-k -> all-gather -> merge; fusion on every rank (the
         merged lists are identical everywhere); rerank: every rank scores the fused
         candidates it OWNS with thr_maxsim (-inf for the others), a second all-gather of the
         [nq, rerank_top_k] float32 scores, then thr_rerank_order takes the maximum per candidate
         and applies the reference's stable sort.
         parents: refused (GpuIndex.retrieve_batch's child -> parent expansion is not built for shards: a family
-        can straddle them)."""
+        can straddle them).
+        diversify: refused (GpuIndex.retrieve_batch's MMR selection reads the dense rows of every candidate of a
+        query: they lie on several shards)."""
         refuse_on_shards("ShardedIndex.retrieve_batch", parents=parents)
+        refuse_diversify_on_shards("ShardedIndex.retrieve_batch", diversify)
         if scopes is not None:
             raise N.NativeError(SCOPES_REFUSED)
         w = {"lexical": 0.7, "semantic": 0.8, "graph": 1.0}

@@ -43,6 +43,7 @@ from .index_entities import EntitySearch
 from .index_text import TextSearch
 from .index_scope import ScopedSearch, ScopePlan
 from .index_parent import PARENT_MODES, ParentSearch
+from .index_diversify import DiversifiedSearch, check_lam
 
 log = logging.getLogger(__name__)
 
@@ -69,7 +70,7 @@ class BatchResult:
     parents: Optional[torch.Tensor] = None
 
 
-class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableIndex):
+class GpuIndex(ScopedSearch, ParentSearch, DiversifiedSearch, EntitySearch, TextSearch, MutableIndex):
     # what an index has before anything sets it (also: one made without __init__, as the host tests do)
     _side = None                # the second HIP stream of side_channels, made on first use
     _shortlist_of = None        # what the candidate lists in the dense workspace belong to (dense_shortlist)
@@ -687,7 +688,8 @@ class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableInde
                        weights: Optional[Dict[str, float]] = None, hops: int = 2,
                        qtok: Optional[torch.Tensor] = None, rerank_top_k: int = 100,
                        rescue: bool = True, scopes=None, scope_rows_max: Optional[int] = None,
-                       scope_graph: bool = False, parents: Optional[str] = None) -> BatchResult:
+                       scope_graph: bool = False, parents: Optional[str] = None,
+                       diversify: Optional[float] = None) -> BatchResult:
         """plan.semantic/lexical/graph_top_k = 100/50/50 and weights 0.7/0.8/1.0 are the
         reference's QueryPlan defaults (src/voice_agent/rag2/query_planner.py:23-50).
         scopes: as dense_search, resolved once for the batch; the dense and the lexical channel
@@ -704,7 +706,15 @@ class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableInde
         its PARENT (maxsim(expand="parent")); siblings tie and keep their fused order.  Needs ``qtok`` and a token
         store.  "collapse": max(rerank_top_k, top_k) candidates are fused, of each parent only the best-fused child
         stays (with its RRF score), then the parent-score rerank when ``qtok`` is given, then top_k: no two returned
-        ids share a parent.  Either way ``BatchResult.parents`` holds the parent number of each returned id."""
+        ids share a parent.  Either way ``BatchResult.parents`` holds the parent number of each returned id.
+        diversify: None, or MMR's lambda in [0, 1] (index_diversify.DiversifiedSearch): max(rerank_top_k, top_k)
+        candidates are fused, the collapse and the rerank run over all of them, and the ``top_k`` are then SELECTED
+        for relevance and mutual dissimilarity over the index's dense rows rather than cut off the top
+        (``diversify(ids, scores, counts, top_k, lam)``).  ``ids`` / ``scores`` / ``counts`` are the selection, in
+        selection order, the scores the candidates' own (no longer descending).  None: today's path."""
+        if diversify is not None:
+            diversify = check_lam("retrieve_batch", diversify)
+            self._dense_rows_for("retrieve_batch(diversify=)")
         if parents not in PARENT_MODES:
             raise ValueError(f"retrieve_batch: parents must be one of {list(PARENT_MODES)}, got {parents!r}")
         if parents is not None:
@@ -733,7 +743,8 @@ class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableInde
             ch["graph"] = gra
             Ig = gra[1]
         rerank = qtok is not None and self.tokens is not None
-        n_fused = max(rerank_top_k, top_k) if rerank or parents == "collapse" else top_k
+        n_fused = max(rerank_top_k, top_k) if rerank or parents == "collapse" or diversify is not None else top_k
+        n_kept = top_k if diversify is None else n_fused     # what the collapse and the rerank leave for the cut
         ids, sc, _, cnt = N.rrf_fuse(Il, Is, Ig, n_fused, w["lexical"], w["semantic"], w["graph"])
         if parents == "collapse":
             # the leaders only: the best-fused child stands for its parent, with its RRF score
@@ -743,12 +754,14 @@ class GpuIndex(ScopedSearch, ParentSearch, EntitySearch, TextSearch, MutableInde
             live = torch.arange(n_fused, device=cnt.device)[None, :] < cnt[:, None]
             sc = torch.where(live, torch.gather(sc, 1, at), torch.full_like(sc, float("-inf")))
             if not rerank:
-                ids, sc = ids[:, :top_k].contiguous(), sc[:, :top_k].contiguous()
-                cnt = torch.clamp(cnt, max=top_k)
+                ids, sc = ids[:, :n_kept].contiguous(), sc[:, :n_kept].contiguous()
+                cnt = torch.clamp(cnt, max=n_kept)
         if rerank:
             # MaxSim of the fused top rerank_top_k, then the reference's stable descending sort
             # on ``rerank_score or 0`` (retrieval.py:449-455), on the device
             expand = None if parents is None else "parent"
-            ids, sc, cnt = N.rerank_order(self.maxsim(qtok, ids, expand=expand), ids, cnt, top_k)
+            ids, sc, cnt = N.rerank_order(self.maxsim(qtok, ids, expand=expand), ids, cnt, n_kept)
+        if diversify is not None:
+            ids, sc, cnt, _, _ = self.diversify(ids, sc, cnt, top_k=top_k, lam=diversify)
         return BatchResult(ids, sc, cnt, ch, nres, None if parents is None else self.parents_of(ids))
 

@@ -313,7 +313,20 @@ class RAG2Retriever:
             return [], True, f"Max score {best:.2f} below threshold {threshold}", best
         floor = SETTINGS.rag2_denoise_alpha * best
         kept = [c for c in candidates if _effective_score(c) >= floor]
-        return kept[:top_k], False, None, best
+        return self._final_cut(kept, top_k), False, None, best
+
+    def _final_cut(self, kept: List[RetrievalCandidate], top_k: int) -> List[RetrievalCandidate]:
+        """The reference's ``kept[:top_k]`` (:495) -- or, when the backend client carries a ``diversify`` value
+        (GpuIndexClient(diversify=)), the top_k its MMR hook selects from ``kept`` on ``_effective_score``.  A failure
+        of the hook falls back to the truncation, the reranker's convention (:405-459)."""
+        client = self._supabase
+        if len(kept) > 1 and getattr(client, "diversify", None) is not None:
+            try:
+                order = client.mmr_order([c.child_id for c in kept], [_effective_score(c) for c in kept], top_k)
+                return [kept[i] for i in order]
+            except Exception as exc:  # noqa: BLE001
+                log.warning("Diversified cut failed: %s", exc)
+        return kept[:top_k]
 
 
 async def retrieve(org_id: str, query: str, **kwargs: Any) -> RetrievalResult:

@@ -43,6 +43,7 @@ import torch.distributed as dist
 from . import _native as N
 from .backend import GpuIndexClient
 from .distributed import gather_rows, gather_topk
+from .index_diversify import refuse_diversify_on_shards
 from .index_parent import refuse_on_shards
 from .store import CorpusStore
 
@@ -69,7 +70,7 @@ class _ShardEndpoint(GpuIndexClient):
                  collection_names: Optional[Sequence[str]] = None, org_id: Optional[str] = None,
                  token_embedder: Any = None, lexical_and: bool = False,
                  max_token_words: int = 32 * 128 // 2, merge_fn: Optional[Callable] = None,
-                 graph_cascade: bool = False, parent_rerank: bool = False):
+                 graph_cascade: bool = False, parent_rerank: bool = False, diversify: Optional[float] = None):
         """front: rank (within ``group``) that receives the requests.
         max_token_words: int32 words reserved for a query's float16 token matrix (32 x 128).
         merge_fn(scores [W, 1, k], ids [W, 1, k], k) -> (scores [1, k], ids [1, k]): the per-query
@@ -77,6 +78,7 @@ class _ShardEndpoint(GpuIndexClient):
         CPU-only box inject their own)."""
         if parent_rerank:
             refuse_on_shards("a sharded index client", parent_rerank=True)
+        refuse_diversify_on_shards("a sharded index client", diversify)
         if graph_cascade:
             raise N.NativeError("graph_cascade is not supported through a sharded index client: rebuild the shards "
                                 "(graph deletes from a document-sharded index are out of scope)")
