@@ -108,7 +108,21 @@ int thr_doc_norms(const float *docs, int64_t n_docs, int dim, double *dnorm, flo
  * from the float32 rows and orders it.
  * out_flags[q] has THR_FLAG_CERTIFIED when the float32 error bound proves the
  * top-k exact; otherwise call thr_dense_topk_exact for that query.
- * Outputs are padded with (-inf, -1) beyond out_counts[q]. */
+ * Outputs are padded with (-inf, -1) beyond out_counts[q].
+ *
+ * Query values.  For every FINITE float32 query, of any magnitude, a scan entry point followed by
+ * thr_dense_rescue returns the bits of the float64 oracle (thr_dense_topk_exact), and whatever a scan
+ * certifies on its own is already that.  A query outside the range a scan's arithmetic covers gets a
+ * threshold no row passes, stays uncertified and is answered by the exhaustive path alone, without
+ * costing the other queries of its tile a candidate slot: a query with no non-zero value, every scan;
+ * the f16 scans (thr_dense_topk_f16 and the shards' calls), a query whose float16 image is all zero
+ * (every |v| <= 2^-25) or holds an infinity (some |v| >= 65520) -- between the two the measured
+ * rounding error of the image, which reaches 1 in float16's subnormals, widens the certificate until
+ * it fails; this scan, a query with every |v| < 2^-96 or some |v| >= 2^96 (products with the rows
+ * would leave float32's range).  Its lower bounds in the shards' exchange are all -inf: no floor.
+ * A query that holds a NaN or an infinity has no defined answer: the call returns, the query is never
+ * certified by a scan, its out_counts is at most k, its ids are real rows or -1, and the other queries
+ * of the batch are unaffected. */
 size_t thr_dense_workspace_bytes(int64_t n_docs, int dim, int n_queries, int kprime);
 /* Collection filter of the RPC (``AND (p_collection IS NULL OR d.collection = p_collection)``,
  * rag2_schema.sql:404-408), applied BEFORE the ranking on the device: doc_coll int32 [n_docs]

@@ -55,10 +55,11 @@ def planted_oracle(n, d, k, nq=70):
     return CO.dense_topk_exact(x, q, k, doc_id_base=DOC_BASE)
 
 
-def floor_search(T, x, q, k, n_shards, shortlist):
+def floor_search(T, x, q, k, n_shards, shortlist, seen=None):
     """The dense channel of a document-sharded index with every shard in this process: shortlist on every
     shard -> the lower bounds stacked (what the all-gather delivers) -> thr_dense_floor -> finish on every
-    shard -> thr_merge_topk.  -> merged (S, I, cnt), the flags the finishes wrote [G, nq], rescued per shard."""
+    shard -> thr_merge_topk.  -> merged (S, I, cnt), the flags the finishes wrote [G, nq], rescued per shard.
+    seen: a dict that receives what was exchanged, "lbs" [G, nq, m] and "gfloor" [nq]."""
     n = x.shape[0]
     shards = [T.GpuIndex(doc_base=s * n // n_shards).set_dense(x[s * n // n_shards:(s + 1) * n // n_shards],
                                                               shortlist=shortlist) for s in range(n_shards)]
@@ -66,6 +67,8 @@ def floor_search(T, x, q, k, n_shards, shortlist):
     lbs = torch.stack([ix.dense_shortlist(qd, k, n_shards) for ix in shards])
     assert lbs.shape == (n_shards, q.shape[0], T.index.floor_width(k, n_shards))
     gfloor = T._native.dense_floor(lbs, k)
+    if seen is not None:
+        seen.update(lbs=lbs, gfloor=gfloor)
     # the floor as thr_dense_floor's output on the even shards, as the gathered bounds on the odd ones
     outs = [ix.dense_finish(qd, k, lb_all=lbs) if si % 2 else ix.dense_finish(qd, k, gfloor)
             for si, ix in enumerate(shards)]

@@ -1365,6 +1365,22 @@ def test_dense_floor_kernel_known_answers(T):
             flat = np.sort(v[:, i, :].ravel())[::-1]
             exp = flat[k - 1] if flat.size >= k and np.isfinite(flat[k - 1]) else -np.inf
             assert got[i] == exp, (g, m, k, i)
+    # bounds that are not finite: a NaN (a shard whose error bound was NaN) is no bound at all and counts
+    # like an empty slot, +inf is the largest value, -inf the empty slot it always was
+    g, m, k = 4, 16, 10
+    v = rng.standard_normal((g, 6, m)).astype(np.float32)
+    v[:, 0, :] = np.nan                          # nothing but NaN: no floor
+    v[1:, 1, :] = np.nan                         # one shard's 16 values beside 48 NaN
+    v[:, 2, ::2] = np.nan                        # every other slot
+    v[0, 3, :3] = np.inf                         # three +inf at the top
+    v[:, 4, :] = np.inf                          # all +inf
+    v[:, 5, :] = -np.inf
+    v[0, 5, :k - 1] = np.nan                     # k - 1 NaN, the rest empty: no floor
+    got = T._native.dense_floor(dev(v), k).cpu().numpy()
+    for i in range(6):
+        flat = np.sort(np.where(np.isnan(v[:, i, :]), -np.inf, v[:, i, :]).ravel())[::-1]
+        assert got[i] == flat[k - 1], (i, got[i], flat[k - 1])
+    assert got[0] == -np.inf and got[4] == np.inf and got[5] == -np.inf and np.isfinite(got[[1, 2, 3]]).all()
     with pytest.raises(T._native.NativeError):
         T._native.dense_floor(dev(np.zeros((65, 2, 128), dtype=np.float32)), 10)
 

@@ -163,21 +163,39 @@ __device__ __forceinline__ float coarse_value(uint32_t key) {
     return v == v ? v : -INFINITY;
 }
 
-// true when the block's query is a padding row of its tile or an all-zero vector: such a query
-// must never emit (every row ties at 0 and would flood the tile's candidate list); a real zero
-// query therefore ends up uncertified and is answered by the exhaustive path.
-__device__ bool query_is_void(const float* __restrict__ queries, int n_queries, int dim, int q,
-                              int* flag) {
+// The queries a scan must not emit for, judged on the values THE SCAN multiplies (half_image: their
+// float16 image, as every f16 scan rounds them; else the float32 values of the fp32 scan).  Such a
+// query gets a threshold nothing passes, ends up uncertified and is answered by the exhaustive path,
+// which works in float64 from the float32 values.
+//   Q_VOID  a padding row of the tile, or no value the scan can tell from zero: an all-zero vector
+//           (-0.0 included), a float16 image that is all zero (every |v| <= 2^-25), float32 values
+//           all below 2^-96 (their products with the rows underflow, which eps32 does not cover).
+//           Every row would tie at 0 and flood the tile's candidate list: tau = +inf.
+//   Q_WILD  a value the scan's arithmetic leaves finite range with: a float16 image that holds an
+//           infinity or a NaN (|v| >= 65520), a float32 value of 2^96 or more (or not finite: ||q||
+//           x ||d|| may then overflow float32).  Scores of +inf would pass tau = +inf: tau = NaN,
+//           which `score >= tau` is false for whatever the score.
+constexpr int Q_LIVE = 0, Q_VOID = 1, Q_WILD = 2;
+constexpr float F32_SCAN_LO = 0x1p-96f, F32_SCAN_HI = 0x1p96f;
+__device__ int query_kind(const float* __restrict__ queries, int n_queries, int dim, int q,
+                          bool half_image, int* flag) {
     if (threadIdx.x == 0) *flag = 0;
     __syncthreads();
     if (q < n_queries) {
-        int nz = 0;
-        for (int i = threadIdx.x; i < dim; i += blockDim.x) nz |= queries[(int64_t)q * dim + i] != 0.f;
-        if (nz) *flag = 1;
+        int f = 0;   // 1: a value that counts, 2: a value out of range
+        for (int i = threadIdx.x; i < dim; i += blockDim.x) {
+            const float v = queries[(int64_t)q * dim + i];
+            const float a = fabsf(half_image ? (float)(_Float16)v : v);
+            f |= (half_image ? a > 0.f : a >= F32_SCAN_LO) ? 1 : 0;
+            f |= a < (half_image ? INFINITY : F32_SCAN_HI) ? 0 : 2;   // (NaN: out of range)
+        }
+        if (f) atomicOr(flag, f);
     }
     __syncthreads();
-    return *flag == 0;
+    const int f = *flag;
+    return (f & 2) ? Q_WILD : (f & 1) ? Q_LIVE : Q_VOID;
 }
+__device__ __forceinline__ float tau_of_kind(int kind) { return kind == Q_VOID ? INFINITY : __builtin_nanf(""); }
 
 // K2: tau[q] = kk-th largest of sample_scores[q][0..n_sample)  (+inf for void queries;
 // n_sample == 0 means "no sample pass": tau = -inf, every row is a candidate)
@@ -189,7 +207,7 @@ __global__ __launch_bounds__(256) void kth_select(const float* __restrict__ samp
                                                   int64_t sample_ld, int n_sample, int kk,
                                                   const float* __restrict__ queries, int n_queries,
                                                   int dim, float* __restrict__ tau,
-                                                  float* __restrict__ qerr,
+                                                  float* __restrict__ qerr, int half_image,
                                                   const int32_t* __restrict__ doc_coll,
                                                   const int32_t* __restrict__ query_coll, int unit,
                                                   int64_t stride, int64_t n_docs) {
@@ -223,8 +241,10 @@ __global__ __launch_bounds__(256) void kth_select(const float* __restrict__ samp
             qerr[q] = __uint_as_float(__float_as_uint(rel) + 1u);
         }
     }
-    if (query_is_void(queries, n_queries, dim, q, &flag)) {
-        if (threadIdx.x == 0) tau[q] = INFINITY;
+    // (half_image: the call is an f16 scan's -- also the copy scan's on a corpus too small to sample,
+    // which asks for no qerr here)
+    if (const int kind = query_kind(queries, n_queries, dim, q, half_image != 0, &flag)) {
+        if (threadIdx.x == 0) tau[q] = tau_of_kind(kind);
         return;
     }
     if (n_sample < kk) {
@@ -318,8 +338,8 @@ __global__ __launch_bounds__(256) void kth_select_top(const float* __restrict__ 
     __shared__ int bc[2];
     __shared__ int flag;
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (query_is_void(queries, n_queries, dim, q, &flag)) {
-        if (t == 0) tau[q] = INFINITY;
+    if (const int kind = query_kind(queries, n_queries, dim, q, true, &flag)) {
+        if (t == 0) tau[q] = tau_of_kind(kind);
         return;
     }
     if (n_vals < kk) {
@@ -811,8 +831,8 @@ int launch_threshold(const DensePlan& P, const DenseIndex& X, const DenseBatch& 
     hipLaunchKernelGGL(kth_select, dim3(P.qpad), dim3(256), 0, B.st,
                        P.sampled ? (const float*)P.sample : nullptr, P.sample_docs, (int)P.sample_docs,
                        P.ksample, B.queries, B.n_queries, X.dim, P.tau, P.packed ? nullptr : P.qerr,
-                       X.doc_coll, B.query_coll, MF_ROWS, P.sampled ? P.sample_stride : (int64_t)1,
-                       X.n_docs);
+                       P.kind == KIND_F16 ? 1 : 0, X.doc_coll, B.query_coll, MF_ROWS,
+                       P.sampled ? P.sample_stride : (int64_t)1, X.n_docs);
     return launch_status();
 }
 
