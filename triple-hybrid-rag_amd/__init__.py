@@ -10,7 +10,7 @@ from . import _build, _native, synth  # noqa: F401
 from ._native import NativeError  # noqa: F401
 from .index import BatchResult, GpuIndex  # noqa: F401
 from .index_scope import SCOPE_MAX_GENERAL, Between, In, Not, ScopePlan  # noqa: F401
-from .index_text import Analyzer, TextTable  # noqa: F401
+from .index_text import Analyzer, Fuzzy, TextTable  # noqa: F401
 from . import backend, config, core, rag2, retrieval  # noqa: F401,E402
 from .backend import CorpusStore, GpuIndexClient  # noqa: F401,E402
 from .rag2.retrieval import RAG2Retriever, RetrievalCandidate, RetrievalResult, retrieve  # noqa: F401,E402

@@ -32,7 +32,7 @@ def _headers():
     include = os.path.join(os.path.dirname(PKG_DIR), "include")
     return sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + \
         [os.path.join(include, h) for h in ("thr_hip.h", "thr_hip_graph.h", "thr_hip_text.h", "thr_hip_rerank.h",
-                                                "thr_hip_parent.h", "thr_hip_diversify.h")]
+                                                "thr_hip_parent.h", "thr_hip_diversify.h", "thr_hip_fuzzy.h")]
 
 
 def _obj(src: str) -> str:

@@ -47,6 +47,8 @@ THR_TEXT_MAX_BYTES = 0x7FFFFFFF   # bytes of one thr_text_tokens call
 THR_TEXT_WORD, THR_TEXT_EXC = 1 << 16, 1 << 17   # bits of a TextTable entry above the lowered code point
 # bits of the text flags: redo on the host; (thr_query_terms) an unknown token occurred; more than 32 distinct terms
 THR_TEXT_EXCEPTIONAL, THR_TEXT_UNKNOWN, THR_TEXT_TOO_MANY = 1, 2, 4
+# thr_hip_fuzzy.h THR_TEXT_CORRECTED: (thr_query_terms_fuzzy) an unknown token was replaced by its nearest terms
+TEXT_CORRECTED = 8
 THR_VOCAB_MIN_SLOTS, THR_VOCAB_MAX_SLOTS = 16, 1 << 30
 # bits of thr_vocab_grow's status word: two tokens under one masked hash; new_bytes_capacity below n_new_bytes
 THR_VOCAB_GROW_COLLISION, THR_VOCAB_GROW_OVERFLOW = 1, 2
@@ -191,6 +193,16 @@ _SIGNATURES_DIVERSIFY = {
     "thr_mmr_select": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i64, _dbl, _i32, _vp, _vp, _vp, _vp, _vp,
                               _vp]),
 }
+# include/thr_hip_fuzzy.h: the nearest vocabulary terms of unknown tokens, and the query table with them (additive as well)
+_SIGNATURES_FUZZY = {
+    "thr_vocab_nearest_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "thr_vocab_nearest": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp,
+                                 _sz, _vp]),
+    "thr_query_terms_fuzzy_workspace_bytes": (_sz, [_i32]),
+    "thr_query_terms_fuzzy": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+# thr_hip_fuzzy.h's #defines: code points of a needle, corrections kept per token, key bytes a workgroup stages
+FUZZY_MAX_LEN, FUZZY_MAX_BEST, FUZZY_SLICE_BYTES, FUZZY_MAX_EDITS = 32, 4, 8192, 2
 
 
 def lib_path() -> str:
@@ -213,7 +225,7 @@ def load(build_if_missing: bool = True):
         raise NativeError(f"cannot load {path}: {e}") from e
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_SIGNATURES_GRAPH.items()) + list(_SIGNATURES_TEXT.items())
                               + list(_SIGNATURES_RERANK.items()) + list(_SIGNATURES_PARENT.items())
-                              + list(_SIGNATURES_DIVERSIFY.items())):
+                              + list(_SIGNATURES_DIVERSIFY.items()) + list(_SIGNATURES_FUZZY.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -1432,6 +1444,90 @@ def vocab_grow(text_bytes, text_ptr, n_bytes: int, table, rows: dict, n_unknown:
                                  out["new_ptr"].data_ptr(), out["n_new"].data_ptr(), out["n_new_bytes"].data_ptr(),
                                  out["status"].data_ptr(), ws.data_ptr(), nbytes, _stream()), "thr_vocab_grow")
     return out
+
+
+# ------------------------------------------------- typo-tolerant lexical queries (thr_hip_fuzzy.h)
+def fuzzy_check(what: str, max_edits, n_best) -> None:
+    """THE refusal of an edit budget or a correction count outside the header's ranges, by name."""
+    if isinstance(max_edits, bool) or not isinstance(max_edits, int) or not 1 <= max_edits <= FUZZY_MAX_EDITS:
+        raise NativeError(f"{what}: max_edits {max_edits!r} outside 1 .. {FUZZY_MAX_EDITS}")
+    if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= FUZZY_MAX_BEST:
+        raise NativeError(f"{what}: n_best {n_best!r} outside 1 .. THR_FUZZY_MAX_BEST ({FUZZY_MAX_BEST})")
+
+
+def vocab_nearest_workspace_bytes(n_bytes: int, unknown_capacity: int, n_vocab: int, n_term_bytes: int, n_best: int) -> int:
+    return int(load().thr_vocab_nearest_workspace_bytes(n_bytes, unknown_capacity, n_vocab, n_term_bytes, n_best))
+
+
+def query_terms_fuzzy_workspace_bytes(n_queries: int) -> int:
+    return int(load().thr_query_terms_fuzzy_workspace_bytes(n_queries))
+
+
+def vocab_nearest(text_bytes, n_bytes: int, table, unknown_off, unknown_len, n_unknown, term_bytes, term_ptr,
+                  n_term_bytes: int, term_rowptr=None, max_edits: int = 2, n_best: int = 2, workspace=None,
+                  near_term=None, near_dist=None):
+    """thr_vocab_nearest over the unknown list of a text_tokens call (unknown_off i64 / unknown_len i32 [cap],
+    n_unknown i32 [1], on the device) -> (near_term, near_dist) int32 [cap, n_best] on the device: rows at or behind
+    n_unknown are NOT written (``near_term`` / ``near_dist``: the arrays to write into, else fresh ones filled with
+    -1).  term_rowptr i64 [n_vocab + 1] (the postings' row pointer) or None: no document frequencies.  No host
+    read-back."""
+    fuzzy_check("vocab_nearest", max_edits, n_best)
+    pb = _dev(text_bytes, torch.uint8, "text_bytes", 1)
+    pt = _dev(table, torch.int32, "table", 1)
+    po = _dev(unknown_off, torch.int64, "unknown_off", 1)
+    pl = _dev(unknown_len, torch.int32, "unknown_len", 1)
+    pn = _dev(n_unknown, torch.int32, "n_unknown", 1)
+    pk = _dev(term_bytes, torch.uint8, "term_bytes", 1)
+    pkp = _dev(term_ptr, torch.int64, "term_ptr", 1)
+    pr = _dev(term_rowptr, torch.int64, "term_rowptr", 1)
+    cap = min(unknown_off.shape[0], unknown_len.shape[0])
+    n_vocab = term_ptr.shape[0] - 1
+    if table.shape[0] != 65536 or n_unknown.shape[0] != 1:
+        raise NativeError("vocab_nearest: table is [65536], n_unknown [1]")
+    if not 0 <= n_bytes <= min(THR_TEXT_MAX_BYTES, text_bytes.shape[0]):
+        raise NativeError(f"vocab_nearest: {n_bytes} text bytes, the array holds {text_bytes.shape[0]}")
+    if not 1 <= cap <= THR_TEXT_MAX_BYTES:
+        raise NativeError(f"vocab_nearest: an unknown list of 1 .. {THR_TEXT_MAX_BYTES} entries, got {cap}")
+    if n_vocab < 0 or not 0 <= n_term_bytes <= term_bytes.shape[0]:
+        raise NativeError(f"vocab_nearest: {n_term_bytes} key bytes, the array holds {term_bytes.shape[0]}; term_ptr is [n_vocab + 1]")
+    if term_rowptr is not None and term_rowptr.shape[0] < n_vocab + 1:
+        raise NativeError(f"vocab_nearest: term_rowptr holds {term_rowptr.shape[0]} entries for {n_vocab} terms")
+    dev = text_bytes.device
+    for name, arr in (("near_term", near_term), ("near_dist", near_dist)):
+        if arr is not None and (_dev(arr, torch.int32, name, 2) == 0 or tuple(arr.shape) != (cap, n_best)):
+            raise NativeError(f"vocab_nearest: {name} is int32 [{cap}, {n_best}]")
+    if near_term is None:
+        near_term = torch.full((cap, n_best), -1, dtype=torch.int32, device=dev)
+    if near_dist is None:
+        near_dist = torch.full((cap, n_best), -1, dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(workspace, vocab_nearest_workspace_bytes(n_bytes, cap, n_vocab, n_term_bytes, n_best), dev)
+    _check(load().thr_vocab_nearest(pb, n_bytes, pt, po, pl, pn, cap, pk, pkp, n_vocab, n_term_bytes, pr or None, max_edits,
+                                    n_best, near_term.data_ptr(), near_dist.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+           "thr_vocab_nearest")
+    return near_term, near_dist
+
+
+def query_terms_fuzzy(rows: dict, near_term, n_use: int, workspace=None):
+    """thr_query_terms_fuzzy: ``query_terms`` with the corrections ``near_term`` (int32 [cap, n_best], vocab_nearest's)
+    folded in, the first ``n_use`` of each unknown token -> (terms, n_distinct, flags).  No host read-back."""
+    nq = rows["n_tokens"].shape[0]
+    dev = rows["term"].device
+    pnear = _dev(near_term, torch.int32, "near_term", 2)
+    n_best = near_term.shape[1]
+    fuzzy_check("query_terms_fuzzy", 1, n_best)
+    if isinstance(n_use, bool) or not isinstance(n_use, int) or not 1 <= n_use <= n_best:
+        raise NativeError(f"query_terms_fuzzy: n_use {n_use!r} outside 1 .. n_best ({n_best})")
+    if near_term.shape[0] < 1:
+        raise NativeError("query_terms_fuzzy: near_term holds no row")
+    ws, nbytes = _workspace(workspace, query_terms_fuzzy_workspace_bytes(nq), dev)
+    terms = torch.empty((nq, THR_BM25_MAX_TERMS), dtype=torch.int32, device=dev)
+    nd = torch.empty(nq, dtype=torch.int32, device=dev)
+    fl = torch.empty(nq, dtype=torch.int32, device=dev)
+    _check(load().thr_query_terms_fuzzy(_dev(rows["term"], torch.int32, "term", 1), _dev(rows["n_tokens"], torch.int32, "n_tokens", 1),
+                                        _dev(rows["flags"], torch.int32, "flags", 1), _dev(rows["n_total"], torch.int32, "n_total", 1),
+                                        rows["capacity"], nq, pnear, near_term.shape[0], n_best, n_use, terms.data_ptr(),
+                                        nd.data_ptr(), fl.data_ptr(), ws.data_ptr(), nbytes, _stream()), "thr_query_terms_fuzzy")
+    return terms, nd, fl
 
 
 def graph_transpose_mentions(men_rowptr, men_chunk, men_conf, chunk_base: int, n_chunks: int):

@@ -54,7 +54,7 @@ from .index import GpuIndex
 from .index_diversify import check_lam
 from .index_entities import match_names, name_trigrams
 from .index_scope import In
-from .index_text import _TOKEN, TextTable, host_query_row, tokenize, tokenizer_table  # noqa: F401
+from .index_text import _TOKEN, TextTable, check_fuzzy, host_query_row, tokenize, tokenizer_table  # noqa: F401
 from .store import CorpusStore
 
 
@@ -85,7 +85,7 @@ class GpuIndexClient(ClientIngest):
                  image_index: Optional[GpuIndex] = None, image_rows: Any = None,
                  collection_names: Optional[Sequence[str]] = None, device_text: bool = False,
                  tokenizer: Any = None, number_on_device: bool = False, graph_cascade: bool = False,
-                 parent_rerank: bool = False, diversify: Optional[float] = None):
+                 parent_rerank: bool = False, diversify: Optional[float] = None, fuzzy: Any = None):
         """lexical_and: rank only chunks holding EVERY query term, as the reference's ``plainto_tsquery`` does
         (rag2_schema.sql:365); default is BM25's OR form, the north star's and the oracle's.
         image_index / image_rows: the legacy image channel (``kb_chunks_image_search``,
@@ -123,7 +123,17 @@ class GpuIndexClient(ClientIngest):
         -- ``kept[:top_k]`` in the reference -- becomes ``mmr_order``: the top_k chosen greedily for relevance
         (``_effective_score``, min-max normalised) and dissimilarity to what is already chosen, the similarities taken
         from the index's dense rows on the device (GpuIndex.diversify).  Needs an index with dense rows.  Default
-        None: the truncation, the behaviour before the argument."""
+        None: the truncation, the behaviour before the argument.
+        fuzzy: (with device_text) an ``index_text.Fuzzy``, or None.  With one, a query token the vocabulary does not
+        hold is replaced by the vocabulary terms nearest to it (GpuIndex.query_terms(fuzzy=): within 1 .. 2 edits,
+        ranked by distance, then document frequency): ``_lexical``, the lexical and hybrid RPCs' lexical leg and
+        ``query_terms_batch`` take that route; under ``lexical_and`` the best correction alone stands in for the
+        token, else up to ``fuzzy.n_best``.  Without device_text it is refused by name.  Default None: a misspelt
+        word is unknown, the behaviour before the argument."""
+        check_fuzzy("GpuIndexClient", fuzzy)
+        if fuzzy is not None and not device_text:
+            raise ValueError("fuzzy= needs device_text=True: the corrections are sought behind the device tokenizer")
+        self.fuzzy = fuzzy
         if diversify is not None:
             diversify = check_lam("GpuIndexClient", diversify)
             if getattr(index, "docs", None) is None:
@@ -241,7 +251,9 @@ class GpuIndexClient(ClientIngest):
         if not self.device_text:
             raise ValueError("query_terms_batch: the client was made without device_text=True")
         self._sync_vocabulary()
-        return self.index.query_terms(list(queries), conjunctive=self.lexical_and)[0]
+        if self.fuzzy is None:
+            return self.index.query_terms(list(queries), conjunctive=self.lexical_and)[0]
+        return self.index.query_terms(list(queries), conjunctive=self.lexical_and, fuzzy=self.fuzzy)[0]
 
     def _scope(self, org, collection=None, index=None):
         """Multi-tenant: the ScopePlan of a one-query call inside ``org`` (and ``collection``), made

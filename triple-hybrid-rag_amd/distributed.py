@@ -140,6 +140,14 @@ SCOPES_REFUSED = ("scopes= is not supported on a document-sharded index: scoped 
                   "per single-GPU GpuIndex (the shard-floor exchange takes collection ids only)")
 
 
+def refuse_fuzzy_on_shards(what: str, fuzzy) -> None:
+    """THE refusal of typo-tolerant queries on a document-sharded index, by name."""
+    if fuzzy is not None:
+        raise N.NativeError(f"fuzzy= is not supported through {what}: the document frequencies that rank the "
+                            "corrections are per shard, and so would the corrections be (typo-tolerant queries over a "
+                            "document-sharded index are out of scope)")
+
+
 class ShardedIndex:
     """A GpuIndex holding this rank's document shard + the cross-rank merge."""
 
@@ -189,6 +197,16 @@ class ShardedIndex:
         on all ranks at once (Graph delete)."""
         raise N.NativeError("delete_graph is not supported on a ShardedIndex: rebuild the shards "
                             "(graph deletes from a document-sharded index are out of scope)")
+
+    def query_terms(self, texts, conjunctive: bool = False, fuzzy=None):
+        """The local index's exact lookup.  ``fuzzy`` is refused: the corrections are ranked by document frequency,
+        which a shard knows for its own rows only, so two shards would correct one token differently."""
+        refuse_fuzzy_on_shards("ShardedIndex.query_terms", fuzzy)
+        return self.local.query_terms(texts, conjunctive=conjunctive)
+
+    def nearest_terms(self, *_a, **_kw):
+        """Not supported, as query_terms(fuzzy=)."""
+        refuse_fuzzy_on_shards("ShardedIndex.nearest_terms", True)
 
     def _floor_exchange(self):
         if self.world == 1 or not self.floor or self.local.shortlist not in ("f16", "f16-inline", "f16-anydim"):

@@ -30,6 +30,11 @@ texts, and the strings of unknown tokens (an ingest numbers them: GpuIndexClient
 without a -1, the new keys stay on the device as a ``PendingVocabulary`` until the commit appends them to the key
 store and inserts them, and their strings are decoded once per distinct term when the store's vocabulary wants
 them.  A batch with an exceptional text, or two new tokens under one hash, takes the host route above.
+
+``query_terms(fuzzy=Fuzzy(...))`` / ``nearest_terms`` add "did you mean" (thr_hip_fuzzy.h): a query token the
+vocabulary does not hold is replaced by the vocabulary terms within a small edit distance of it, found by one scan
+of the key store on the device (thr_vocab_nearest) and folded into the query table (thr_query_terms_fuzzy).
+``nearest_terms_host`` / ``host_query_row_fuzzy`` below are the definition.
 """
 from __future__ import annotations
 
@@ -354,6 +359,98 @@ def host_query_row(tokens: Sequence[str], ids: Dict[str, int]) -> Tuple[List[int
     return list(seen), len(seen), flags
 
 
+# ---------------------------------------------------------------- typo-tolerant queries: the definition (thr_hip_fuzzy.h)
+THR_FUZZY_MAX_LEN = N.FUZZY_MAX_LEN      # code points of a needle; longer tokens are never corrected
+THR_FUZZY_MAX_BEST = N.FUZZY_MAX_BEST    # corrections kept per token
+THR_TEXT_CORRECTED = N.TEXT_CORRECTED   # flag bit beside THR_TEXT_UNKNOWN / THR_TEXT_TOO_MANY
+
+
+def levenshtein(a: str, b: str) -> int:
+    """Insert / delete / substitute at unit cost, over code points (the two-row dynamic programme)."""
+    prev = list(range(len(b) + 1))
+    for i, ca in enumerate(a, 1):
+        cur = [i]
+        for j, cb in enumerate(b, 1):
+            cur.append(min(prev[j - 1] + (ca != cb), prev[j] + 1, cur[j - 1] + 1))
+        prev = cur
+    return prev[-1]
+
+
+def fuzzy_edits(n: int, max_edits: int) -> int:
+    """The edit budget of a needle of n code points: Lucene's AUTO rule, capped."""
+    return min(max_edits, 0 if n < 3 else 1 if n < 6 else 2)
+
+
+def nearest_terms_host(needle: str, terms: Sequence[str], df, max_edits: int, n_best: int) -> List[Tuple[int, int]]:
+    """THE DEFINITION of a correction (thr_vocab_nearest is held to it exactly).  needle: the lowered token (with an
+    Analyzer: the stem); terms[i] the key of term i; df[i] its document frequency, or df None
+    -> [(distance, term id)], best first: distance ascending, then frequency descending, then id ascending."""
+    n = len(needle)
+    d = fuzzy_edits(n, max_edits)
+    if n > THR_FUZZY_MAX_LEN or (d == 0 and max_edits > 0 and n < 3):
+        return []
+    out = []
+    for i, key in enumerate(terms):
+        if abs(len(key) - n) > d:
+            continue
+        if df is not None and df[i] <= 0:       # a term without postings corrects nothing
+            continue
+        dist = levenshtein(needle, key)
+        if dist <= d:
+            out.append((dist, -min(int(df[i]), 2 ** 31 - 1) if df is not None else 0, i))
+    return [(dist, i) for dist, _, i in sorted(out)[:n_best]]
+
+
+def host_query_row_fuzzy(tokens: Sequence[str], ids: Dict[str, int], terms: Sequence[str], df, max_edits: int,
+                         n_best: int, conjunctive: bool) -> Tuple[List[int], int, int]:
+    """``host_query_row`` with an unknown token replaced, at its place, by its nearest terms: the best one alone
+    in an AND query (the BM25 AND has no "t or t'" clause), up to n_best in an OR query.  A token with no
+    correction keeps THR_TEXT_UNKNOWN; a corrected one sets THR_TEXT_CORRECTED instead."""
+    seen: Dict[int, None] = {}
+    flags = 0
+    for tok in tokens:
+        t = ids.get(tok)
+        if t is not None:
+            seen[t] = None
+            continue
+        near = nearest_terms_host(tok, terms, df, max_edits, 1 if conjunctive else n_best)
+        if near:
+            flags |= THR_TEXT_CORRECTED
+            for _, i in near:
+                seen.setdefault(i)
+        else:
+            flags |= N.THR_TEXT_UNKNOWN
+    if len(seen) > N.THR_BM25_MAX_TERMS:
+        return list(seen)[:N.THR_BM25_MAX_TERMS], N.THR_BM25_MAX_TERMS + 1, flags | N.THR_TEXT_TOO_MANY
+    return list(seen), len(seen), flags
+
+
+class Fuzzy:
+    """The typo tolerance of a lexical query: an unknown token is replaced by the ``n_best`` (1 .. THR_FUZZY_MAX_BEST)
+    vocabulary terms nearest to it, within min(``max_edits`` (1 .. 2), the budget of its length) edits."""
+
+    def __init__(self, max_edits: int = 2, n_best: int = 2):
+        if isinstance(max_edits, bool) or not isinstance(max_edits, int) or not 1 <= max_edits <= N.FUZZY_MAX_EDITS:
+            raise ValueError(f"Fuzzy: max_edits {max_edits!r} outside 1 .. {N.FUZZY_MAX_EDITS}")
+        if isinstance(n_best, bool) or not isinstance(n_best, int) or not 1 <= n_best <= THR_FUZZY_MAX_BEST:
+            raise ValueError(f"Fuzzy: n_best {n_best!r} outside 1 .. THR_FUZZY_MAX_BEST ({THR_FUZZY_MAX_BEST})")
+        self.max_edits, self.n_best = max_edits, n_best
+
+    def __repr__(self) -> str:
+        return f"Fuzzy(max_edits={self.max_edits}, n_best={self.n_best})"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Fuzzy) and (self.max_edits, self.n_best) == (other.max_edits, other.n_best)
+
+    def __hash__(self) -> int:
+        return hash((self.max_edits, self.n_best))
+
+
+def check_fuzzy(what: str, fuzzy) -> None:
+    if fuzzy is not None and not isinstance(fuzzy, Fuzzy):
+        raise ValueError(f"{what}: fuzzy is an index_text.Fuzzy or None, not {type(fuzzy).__name__}")
+
+
 class TextRows(NamedTuple):
     doc: torch.Tensor            # int32 [T] on the device: the text of each token, ascending
     term: torch.Tensor           # int32 [T] on the device: its term id, -1 for a token outside the vocabulary
@@ -401,6 +498,7 @@ class TextSearch:
     _ws_text: Optional[torch.Tensor] = None     # thr_text_tokens' workspace, grown on demand and kept
     _ws_qterms: Optional[torch.Tensor] = None
     _ws_grow: Optional[torch.Tensor] = None     # thr_vocab_grow's
+    _ws_fuzzy: Optional[torch.Tensor] = None    # thr_vocab_nearest's
 
     # ------------------------------------------------------------ the vocabulary
     def set_vocabulary(self, terms: Sequence[str], table: Optional[TextTable] = None) -> "TextSearch":
@@ -593,16 +691,65 @@ class TextSearch:
         rows["bytes_dev"], rows["ptr_dev"] = bytes_dev, ptr_dev      # (thr_vocab_grow reads the batch again)
         return rows
 
-    def query_terms(self, texts: Sequence[str], conjunctive: bool = False):
+    def _term_rowptr(self) -> Optional[torch.Tensor]:
+        """The document frequencies of the vocabulary as thr_vocab_nearest takes them: the postings' row pointer
+        (a term the lexical index does not hold yet has no postings: the pointer is extended flat), or None for
+        an index without a lexical index."""
+        L = getattr(self, "lex", None)
+        if L is None:
+            return None
+        rowptr, v = L["rowptr"], self.text["term_ptr"].shape[0] - 1
+        if rowptr.shape[0] < v + 1:
+            rowptr = torch.cat([rowptr, rowptr[-1:].expand(v + 1 - rowptr.shape[0])])
+        return rowptr
+
+    def _nearest(self, bytes_dev, n_bytes: int, unknown_off, unknown_len, n_unknown, fuzzy: Fuzzy, df: bool):
+        X = self.text
+        cap = min(unknown_off.shape[0], unknown_len.shape[0])
+        need = N.vocab_nearest_workspace_bytes(n_bytes, cap, X["term_ptr"].shape[0] - 1, X["n_bytes"], fuzzy.n_best)
+        return N.vocab_nearest(bytes_dev, n_bytes, X["table_dev"], unknown_off, unknown_len, n_unknown, X["term_bytes"],
+                               X["term_ptr"], X["n_bytes"], term_rowptr=self._term_rowptr() if df else None,
+                               max_edits=fuzzy.max_edits, n_best=fuzzy.n_best,
+                               workspace=self._scratch("_ws_fuzzy", max(need, 16)))
+
+    def nearest_terms(self, tokens: Sequence[str], fuzzy: Optional[Fuzzy] = None, df: bool = True):
+        """"Did you mean": the vocabulary terms nearest to each of the already-lowered token strings -> (ids int32
+        [n, n_best], dist int32 [n, n_best]) on the device, best first, padded with -1 (``nearest_terms_host`` is
+        the definition; thr_vocab_nearest alone).  ``df``: rank equal distances by the lexical index's document
+        frequencies and pass over terms without postings (an index without a lexical index has none to give).  A
+        token the table calls exceptional, one of fewer than 3 or more than THR_FUZZY_MAX_LEN code points, gets a
+        row of -1; a token that is itself a key finds that key at distance 0."""
+        if self.text is None:
+            raise N.NativeError("nearest_terms: the index has no vocabulary (set_vocabulary)")
+        fuzzy = Fuzzy() if fuzzy is None else fuzzy
+        check_fuzzy("nearest_terms", fuzzy)
+        tokens = list(tokens)
+        if not tokens:
+            empty = torch.empty((0, fuzzy.n_best), dtype=torch.int32, device=self.device)
+            return empty, empty.clone()
+        blob, ptr = pack_texts(tokens)
+        n_bytes = int(ptr[-1])
+        return self._nearest(self._t(blob, torch.uint8), n_bytes, self._t(ptr[:-1].copy(), torch.int64),
+                             self._t(np.diff(ptr).astype(np.int32), torch.int32),
+                             self._t(np.asarray([len(tokens)], dtype=np.int32), torch.int32), fuzzy, df)
+
+    def query_terms(self, texts: Sequence[str], conjunctive: bool = False, fuzzy: Optional[Fuzzy] = None):
         """The BM25 term table of a batch of query texts -> (terms int32 [nq, THR_BM25_MAX_TERMS] padded with
         -1, flags int32 [nq]), both on the device: per query GpuIndexClient._query_terms' answer -- the distinct
         known term ids in order of first appearance.  flags: THR_TEXT_EXCEPTIONAL (the row was computed on
         the host through the table's tokenizer and patched in), THR_TEXT_UNKNOWN, THR_TEXT_TOO_MANY.
         ``conjunctive``: a row with an unknown token or more than 32 distinct terms becomes all -1 (no chunk
         can hold every term: _query_terms' None; thr_bm25_topk answers an all -1 row with no rows in both
-        forms).  The device path reads nothing back."""
+        forms).  The device path reads nothing back.
+        ``fuzzy`` (a ``Fuzzy``; None: exactly the calls above): a token the vocabulary does not hold is replaced,
+        at its place, by the vocabulary terms nearest to it (``host_query_row_fuzzy`` is the definition:
+        thr_vocab_nearest over the unknown list, with the lexical index's document frequencies when there is
+        one, then thr_query_terms_fuzzy) -- the best one alone when ``conjunctive``, up to ``fuzzy.n_best``
+        otherwise; such a row carries THR_TEXT_CORRECTED, and THR_TEXT_UNKNOWN only when a token found no
+        correction.  The exceptional queries keep their host rows, uncorrected."""
         if self.text is None:
             raise N.NativeError("query_terms: the index has no vocabulary (set_vocabulary)")
+        check_fuzzy("query_terms", fuzzy)
         texts = list(texts)
         nq = len(texts)
         if nq == 0:
@@ -610,8 +757,15 @@ class TextSearch:
                     torch.empty(0, dtype=torch.int32, device=self.device))
         X = self.text
         rows = self._text_tokens(texts)
-        need = N.query_terms_workspace_bytes(nq)
-        terms, _, flags = N.query_terms(rows, workspace=self._scratch("_ws_qterms", max(need, 8)))
+        if fuzzy is None:
+            need = N.query_terms_workspace_bytes(nq)
+            terms, _, flags = N.query_terms(rows, workspace=self._scratch("_ws_qterms", max(need, 8)))
+        else:
+            near, _ = self._nearest(rows["bytes_dev"], int(rows["ptr"][-1]), rows["unknown_off"], rows["unknown_len"],
+                                    rows["n_unknown"], fuzzy, True)
+            need = N.query_terms_fuzzy_workspace_bytes(nq)
+            terms, _, flags = N.query_terms_fuzzy(rows, near, 1 if conjunctive else fuzzy.n_best,
+                                                  workspace=self._scratch("_ws_qterms", max(need, 8)))
         redo = X["table"].exceptional_among(texts)
         if redo:
             host = np.full((len(redo), N.THR_BM25_MAX_TERMS), -1, dtype=np.int32)

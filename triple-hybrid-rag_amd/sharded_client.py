@@ -42,7 +42,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from .backend import GpuIndexClient
-from .distributed import gather_rows, gather_topk
+from .distributed import gather_rows, gather_topk, refuse_fuzzy_on_shards
 from .index_diversify import refuse_diversify_on_shards
 from .index_parent import refuse_on_shards
 from .store import CorpusStore
@@ -70,7 +70,8 @@ class _ShardEndpoint(GpuIndexClient):
                  collection_names: Optional[Sequence[str]] = None, org_id: Optional[str] = None,
                  token_embedder: Any = None, lexical_and: bool = False,
                  max_token_words: int = 32 * 128 // 2, merge_fn: Optional[Callable] = None,
-                 graph_cascade: bool = False, parent_rerank: bool = False, diversify: Optional[float] = None):
+                 graph_cascade: bool = False, parent_rerank: bool = False, diversify: Optional[float] = None,
+                 fuzzy: Any = None):
         """front: rank (within ``group``) that receives the requests.
         max_token_words: int32 words reserved for a query's float16 token matrix (32 x 128).
         merge_fn(scores [W, 1, k], ids [W, 1, k], k) -> (scores [1, k], ids [1, k]): the per-query
@@ -79,6 +80,7 @@ class _ShardEndpoint(GpuIndexClient):
         if parent_rerank:
             refuse_on_shards("a sharded index client", parent_rerank=True)
         refuse_diversify_on_shards("a sharded index client", diversify)
+        refuse_fuzzy_on_shards("a sharded index client", fuzzy)
         if graph_cascade:
             raise N.NativeError("graph_cascade is not supported through a sharded index client: rebuild the shards "
                                 "(graph deletes from a document-sharded index are out of scope)")
